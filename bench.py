@@ -16,6 +16,14 @@ bootstrap that reads the launcher's RANK / WORLD_SIZE / MASTER_PORT).
 Per-kernel numbers come from hipEvents recorded around every launch on the
 library's compute stream inside the timed region (LZ_FLAG_PROFILE);
 `roofline.achieved` = algorithmic bytes / event time.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full`
+adds what takes work of its own after the timed steps: the Ritz back-transform
+and Gram records, the extra arms (partial re-orthogonalisation, halo overlap,
+one-reduce, uncoded SpMV, class surface) and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (alpha.npy,
+beta.npy, V_sample.npy: a fixed sample of basis rows) for output-for-output
+comparisons of two builds.
 """
 import argparse
 import json
@@ -96,6 +104,23 @@ def gram_record(tg, k):
                     "mfma_issue_floor_cycles_per_kstep": info["mfma_issue_floor_cycles_per_kstep"],
                     "mfma_issue_utilisation_in_cycles": round(info["mfma_issue_floor_cycles_per_kstep"] / max(info["cycles_per_kstep"], 1e-9), 4)})
     return rec
+
+
+def dump_outputs(out_dir, h, alpha, beta):
+    """What a caller of execute_Lanczos receives from the last timed step: the coefficients and the basis.  The basis (k x rows,
+    16 GB at the headline) stays on the device; a fixed sample of it is fetched: up to 16 blocks of 256 consecutive rows at seeded
+    offsets of this rank's block (all of it when it is no larger than the sample), at most ~48 MB.  float64 throughout."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "alpha.npy"), np.asarray(alpha, dtype=np.float64))
+    np.save(os.path.join(out_dir, "beta.npy"), np.asarray(beta, dtype=np.float64))
+    rows, blk = int(h.rows), 256
+    nblk = max(1, min(16, int(48e6 // (8 * h.n * blk))))
+    if rows <= nblk * blk:
+        V = h.get_basis_block(0, rows)
+    else:
+        starts = np.sort(np.random.default_rng(0).choice(rows // blk, size=nblk, replace=False)) * blk
+        V = np.concatenate([h.get_basis_block(r0, r0 + blk) for r0 in starts], axis=1)
+    np.save(os.path.join(out_dir, "V_sample.npy"), V)
 
 
 def spmv_format_arm(_capi, local, device, coding):
@@ -315,7 +340,12 @@ def main():
     ap.add_argument("--bootstrap", default="socket", choices=["socket", "torch"])
     ap.add_argument("--backend", default="rccl", choices=["rccl", "host"])
     ap.add_argument("--mode", default="auto", choices=["auto", "halo", "allgather"])
+    ap.add_argument("--full", action="store_true", help="also run the Ritz / Gram records, the extra arms and the CPU baseline (--no-partial, "
+                                                        "--no-overlap-arm, --no-class-surface and --no-cpu-baseline leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Plain `python bench.py --gpus N`: this process becomes the launcher.  It has made no HIP call (and makes
@@ -404,35 +434,41 @@ def main():
         elapsed = max(boot.allgather_obj(elapsed))
     tm = solver.timings()
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver.h, alpha, beta)
+
     # sanity of the result (cheap): Ritz values finite, extreme one inside the Gershgorin bound
-    try:
-        theta = solver.get_H_eigs(fetch=False)
-        tr_first = solver.timings()["ritz"]  # first call of the process: includes the kernel's code-object load
-        theta = solver.get_H_eigs(fetch=False)
-        tr = solver.timings()["ritz"]
-        tr["ms_first_call"] = tr_first["ms"]
-        tr["info"] = solver.h.ritz_info()  # chunked? + the back-transform kernel's own clock record of THIS call
-        if tr["info"]["chunk_rows"] > 0:
-            # No room for a second M x k array beside the basis (C4 on one GPU): lz_ritz_vectors only kept S.  What get_H_eigs
-            # then runs is the Gram matrix accumulated chunk by chunk (every chunk: Y rows = V^T-layout x S, then Y^T Y) - time that.
-            G = solver.h.ritz_gram()
-            assert np.abs(G - np.eye(k)).max() < 1e-10
-            tr = dict(solver.timings()["ritz"], ms_first_call=0.0, info=solver.h.ritz_info(), chunked_pass="back-transform of every row chunk + its Gram accumulation")
-        # the n x n Gram matrix of the Ritz vectors (the two checks of get_H_eigs, Lanczos.py:157-158), resident Y only: second call
-        tg = None
-        if tr["info"]["chunk_rows"] == 0:
-            G = solver.h.ritz_gram()
-            solver.timings()
-            G = solver.h.ritz_gram()
-            tg = solver.timings()["ritz"]
-            tg["info"] = solver.h.gram_info() if world == 1 else None
-            tg["max_dev_from_identity"] = float(np.abs(G - np.eye(k)).max())
-            assert tg["max_dev_from_identity"] < 1e-10 and np.array_equal(G, G.T)
-    except _capi.LanczosHipError as e:  # e.g. no room for a second M x k array next to the basis
-        tg = None
-        print(f"[rank {rank}] Ritz back-transform skipped: {e}", file=sys.stderr)
-        theta = np.linalg.eigvalsh(solver.H_eff)
-        tr = {"ms": 0.0, "flops": 0.0, "ms_first_call": 0.0}
+    theta = np.linalg.eigvalsh(solver.H_eff)
+    tr = tg = None
+    if args.full:  # the Ritz back-transform and Gram records: work of their own on the device after the timed steps
+        try:
+            theta = solver.get_H_eigs(fetch=False)
+            tr_first = solver.timings()["ritz"]  # first call of the process: includes the kernel's code-object load
+            theta = solver.get_H_eigs(fetch=False)
+            tr = solver.timings()["ritz"]
+            tr["ms_first_call"] = tr_first["ms"]
+            tr["info"] = solver.h.ritz_info()  # chunked? + the back-transform kernel's own clock record of THIS call
+            if tr["info"]["chunk_rows"] > 0:
+                # No room for a second M x k array beside the basis (C4 on one GPU): lz_ritz_vectors only kept S.  What get_H_eigs
+                # then runs is the Gram matrix accumulated chunk by chunk (every chunk: Y rows = V^T-layout x S, then Y^T Y) - time that.
+                G = solver.h.ritz_gram()
+                assert np.abs(G - np.eye(k)).max() < 1e-10
+                tr = dict(solver.timings()["ritz"], ms_first_call=0.0, info=solver.h.ritz_info(), chunked_pass="back-transform of every row chunk + its Gram accumulation")
+            # the n x n Gram matrix of the Ritz vectors (the two checks of get_H_eigs, Lanczos.py:157-158), resident Y only: second call
+            tg = None
+            if tr["info"]["chunk_rows"] == 0:
+                G = solver.h.ritz_gram()
+                solver.timings()
+                G = solver.h.ritz_gram()
+                tg = solver.timings()["ritz"]
+                tg["info"] = solver.h.gram_info() if world == 1 else None
+                tg["max_dev_from_identity"] = float(np.abs(G - np.eye(k)).max())
+                assert tg["max_dev_from_identity"] < 1e-10 and np.array_equal(G, G.T)
+        except _capi.LanczosHipError as e:  # e.g. no room for a second M x k array next to the basis
+            tg = None
+            print(f"[rank {rank}] Ritz back-transform skipped: {e}", file=sys.stderr)
+            theta = np.linalg.eigvalsh(solver.H_eff)
+            tr = {"ms": 0.0, "flops": 0.0, "ms_first_call": 0.0}
     assert np.isfinite(theta).all()
     assert not getattr(solver, "breakdown", False), "Lanczos breakdown in the timed runs: the coefficients are rounding noise"
 
@@ -509,11 +545,18 @@ def main():
                                    "bound": "mfma", "peak_tflops": FP64_MFMA_PEAK_TFLOPS,
                                    "frac": round(tr["flops"] / max(tr["ms"], 1e-9) / 1e9 / FP64_MFMA_PEAK_TFLOPS, 4),
                                    "note": "Y = V^T-layout x S (M x k x k) FP64 MFMA GEMM, outside the timed steps; second call of the process (ms_first_call: the first)",
-                                   **({"chunked_pass": tr["chunked_pass"]} if "chunked_pass" in tr else {}), **ritz_clock(tr.get("info"))},
+                                   **({"chunked_pass": tr["chunked_pass"]} if "chunked_pass" in tr else {}), **ritz_clock(tr.get("info"))} if tr else None,
             "ritz_gram": gram_record(tg, k),
         }
     else:
         line = None
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            boot.barrier()
+        return
 
     # ---- extra arms, reported separately and NEVER part of `value`.  They contain collectives; a watchdog prints the
     # main line and ends every rank if an arm stalls, so the headline result cannot be lost to an experiment.

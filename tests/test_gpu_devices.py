@@ -283,7 +283,7 @@ def test_bench_self_spawn_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2` without a launcher: the parent (which never touches the GPU) spawns both ranks, rank 0
     prints ONE JSON line - the plumbing the driver's first multi-GPU run will go through."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "host", "--device", "0", "--workload", "lap2d_5pt_M1e6_k100",
-           "--steps", "1", "--warmup", "1", "--prewarm-s", "0.1", "--arm-timeout", "600"]
+           "--steps", "1", "--warmup", "1", "--prewarm-s", "0.1", "--arm-timeout", "600", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
@@ -305,6 +305,41 @@ def test_bench_self_spawn_two_ranks_on_one_gpu():
     pa = arm["partial"]
     assert pa["engine"] == "partial-one-reduce" and pa["lookahead_misses"] == 0 and pa["max_rel_ritz_diff_vs_full"] < 1e-10, pa
     assert abs(pa["comm_calls_per_iteration"]["allreduce"] - 1.0) < 0.02 and abs(pa["comm_calls_per_iteration"]["exchange"] - 1.0) < 0.02, pa
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """`python bench.py` without --full: one line with the timed steps' record and none of the --full records; --dump-outputs holds
+    the last timed solve's coefficients and basis sample - the oracle's, sampled at the same rows."""
+    import bench
+
+    out = tmp_path / "bench"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1", "--prewarm-s", "0.1",
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "iterations/s" and line["dtype"] == "f64"
+    assert line["partial_reorth"] is None and line["ritz_backtransform"] is None and line["ritz_gram"] is None
+    assert not {"cpu_baseline", "class_surface", "spmv_uncoded_arm"} & set(line)
+
+    H = synthetic.laplacian_2d_5pt(256, 128).to_scipy()
+    a, b, V = oracle.execute_lanczos(H, 24)
+
+    class OracleBasis:
+        rows, n = V.shape[1], V.shape[0]
+
+        def get_basis_block(self, r0, r1):
+            return V[:, r0:r1]
+
+    bench.dump_outputs(str(tmp_path / "oracle"), OracleBasis(), a, b)
+    scale = max(np.abs(a).max(), np.abs(b).max())
+    for name, atol in (("alpha", 1e-10 * scale), ("beta", 1e-10 * scale), ("V_sample", 1e-10)):
+        got, want = np.load(out / f"{name}.npy"), np.load(tmp_path / "oracle" / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == want.shape, (name, got.dtype, got.shape, want.shape)
+        assert np.abs(got - want).max() <= atol, name
+    assert np.load(out / "V_sample.npy").shape == (24, 4096)
 
 
 def test_a_dying_worker_ends_the_pool_and_is_reported():

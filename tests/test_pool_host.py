@@ -139,7 +139,11 @@ buf = C.create_string_buffer(8)
 assert lib.lz_runtime_info(buf, 8) == 0  # truncated, never overrun
 print("ASAN-OK")
 """ % (ROOT, os.path.join(ROOT, "lanczos_amd", "liblanczos_hip_asan.so"))
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    # the sanitizer runtime must come first; whatever the environment already preloads stays preloaded.  The child sees no GPU
+    # on any machine: with a device visible the HIP runtime's device-memory allocations would go through ASan's HSA interceptors,
+    # a GPU sanitizer - this test checks host code only.
+    env = dict(os.environ, LD_PRELOAD=" ".join(filter(None, (rt, os.environ.get("LD_PRELOAD")))), ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1",
+               ROCR_VISIBLE_DEVICES="-1", HIP_VISIBLE_DEVICES="-1")
     p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "ASAN-OK" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr
