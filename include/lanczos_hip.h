@@ -127,7 +127,9 @@ int lz_set_options(lz_handle h, int flags);
  *   10  irregular SpMV: entries per row block   12  1 = no row-stride skew
  *   13  1 = NaN-poison a fresh basis allocation before the required parts are cleared (test knob)
  *   14  irregular SpMV plan (0 auto: the column-blocked two-phase kernels for matrices without column locality, 1 never, 2 always)
- *   15  loop structure (0 auto: three launches per step for small problems, five up to 4e6 rows per rank, else six; 1 six always)
+ *   15  loop structure (0 auto: three launches per step for small problems, five up to 4e6 rows per rank, above that on one rank
+ *       the one-sweep loop - one walk over the basis per step, lz_last_engine 9 -, else six; 1 six always; 6 the one-sweep loop
+ *       at any size (one rank, fused-norm full re-orthogonalisation, default kernels, n <= 1536))
  *   16  rows per chunk of the CHUNKED Ritz mode (0 auto: chunked only when Y does not fit beside the basis; > 0 forces it: tests)
  *   11  two-sided Gram-Schmidt links (0 / 1: streaming kernel + fold kernel per link)
  *   17  fixed-K (stencil) SpMV layout: 0 auto (CSR-order kernel with products staged through LDS; the ELL-ordered second copy -
@@ -360,6 +362,15 @@ int lz_last_sweep_misses(lz_handle h, int* misses);
  * one-launch-per-step engines of the kernel-bench build (retired from the product library in round 3: bit-identical, not
  * faster - LAB_NOTEBOOK.md section 4). */
 int lz_last_engine(lz_handle h, int* engine);
+/* One-sweep loop (lz_last_engine 9): the steps of the last lz_run whose predicted coefficients missed the measured ones by more
+ * than the gate (1e-14 in units of the new vector) and that therefore ran the correcting sweep; 0 after any other loop. */
+int lz_last_gate_trips(lz_handle h, int* trips);
+/* Host evaluation of the one-sweep loop's per-step arithmetic (the device kernels' expressions and order), for checks
+ * without a GPU.  G (symmetric) and H are n x n with column i at [i * n].  predict: chat[0..j] of step j + 1 from alpha_j, the
+ * norm beta_j that formed v_j and nrm2 = ||w_{j+1}||^2.  post: col[0..j) = G[:j, j] of the v_j formed with chat from the
+ * measured dots d[i] = V_i . u_j, nrm2 = ||w_j||^2. */
+int lz_one_sweep_host_predict(int n, int j, const double* H, const double* G, double alpha_j, double beta_j, double nrm2, double* chat);
+int lz_one_sweep_host_post(int n, int j, const double* G, const double* d, const double* chat, double nrm2, double* col);
 /* Host <-> device synchronisations lz_run made between its first and its last launch (the final wait for alpha / beta is not
  * counted).  0 for every loop on one rank and over RCCL - including, since round 4, the partial re-orthogonalisation mode
  * (engine 7: Simon's omega-recurrence and the sweep decision live on the device; lz_set_tuning(h, 18, 1) selects the former

@@ -46,7 +46,7 @@ TUNE_BI_LINKS = 11          # two-sided Gram-Schmidt links
 TUNE_NO_SKEW = 12           # 1 = no row-stride skew
 TUNE_POISON_BASIS = 13      # 1 = NaN-poison a fresh basis allocation (test knob)
 TUNE_SPMV_PLAN = 14         # irregular SpMV plan (0 auto, 1 never two-phase, 2 always)
-TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always)
+TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size)
 TUNE_RITZ_CHUNK_ROWS = 16   # rows per chunk of the chunked Ritz mode (> 0 forces it)
 TUNE_FIXED_LAYOUT = 17      # fixed-K SpMV layout (0 auto: row-class coded ELL where the rows fall into classes, else CSR order and ELL only in the partial loop;
                             # 1 never ELL; 2 / 3 uncoded ELL always, one / two rows per lane; 4 offsets-only coding)
@@ -136,6 +136,9 @@ SIGNATURES = {
     "lz_last_sweep_log": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),
     "lz_comm_counts": (C.c_int, [_P, _I64, _I64]),
     "lz_last_engine": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_gate_trips": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_one_sweep_host_predict": (C.c_int, [C.c_int, C.c_int, _D, _D, C.c_double, C.c_double, C.c_double, _D]),
+    "lz_one_sweep_host_post": (C.c_int, [C.c_int, C.c_int, _D, _D, _D, C.c_double, _D]),
     "lz_last_host_syncs": (C.c_int, [_P, _I64]),
     "lz_basis_alloc": (C.c_int, [_P, C.c_int]),
     "lz_basis_set_row": (C.c_int, [_P, C.c_int, _D]),
@@ -634,11 +637,19 @@ class Handle:
         "one-reduce": LZ_FLAG_ONE_REDUCE; "one-reduce-repeated": such a run whose cancellation guard fired and that was
         repeated on the default loop; "partial-device": LZ_FLAG_REORTH_PARTIAL with the omega-recurrence and the sweep decision on
         the device (no host synchronisation inside the run); "partial-one-reduce": the same with ONE all-reduce per step
-        (LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE, look-ahead sweep decision); "step" / "small": the retired one-launch-per-step / one-kernel
-        engines (kernel-bench build)."""
+        (LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE, look-ahead sweep decision); "one-sweep": one walk over the basis per step,
+        coefficients predicted from V^T V and checked in the same walk (the default above 4e6 rows on one rank); "step" / "small": the
+        retired one-launch-per-step / one-kernel engines (kernel-bench build)."""
         k = C.c_int()
         self.check(self.lib.lz_last_engine(self._h, C.byref(k)))
-        return ("kernels", "small", "fused", "three-term-fused", "step", "one-reduce-repeated", "one-reduce", "partial-device", "partial-one-reduce")[k.value]
+        return ("kernels", "small", "fused", "three-term-fused", "step", "one-reduce-repeated", "one-reduce", "partial-device", "partial-one-reduce",
+                "one-sweep")[k.value]
+
+    def last_gate_trips(self):
+        """one-sweep loop: steps of the last run whose predicted coefficients missed by more than the gate (they ran a correcting sweep)"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_gate_trips(self._h, C.byref(k)))
+        return k.value
 
     def last_host_syncs(self):
         """host <-> device synchronisations inside the last lz_run (between its first and its last launch)"""

@@ -141,6 +141,10 @@ struct lz_context {
   int r_state = 0;      // what d_r holds after the last run: 0 nothing usable, 1 the residual entering step n, 2 y = A v_{n-1} (three-term pending)
   Xfer* xfer = nullptr;        // staging ring of the large device -> host copies (lz_xfer.hip), created at the first one
   double* h_pinned = nullptr;  // 8 pinned doubles for the per-step scalar read-back of the host-decided partial-reorth loop (tune[18] == 1)
+  double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n); os_n = its n
+  int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run
+  int os_n = 0;
+  int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
   double* d_om = nullptr;      // device-resident partial re-orthogonalisation: omega-recurrence state (omega_state_doubles)
   int* d_omi = nullptr;        //   ... gate of the coming step, sweep count, per-step sweep log (omega_state_ints)
   int om_n = 0;

@@ -182,6 +182,47 @@ void launch_update(double* V, int64_t ldv, int64_t len, int nrows, int j, const 
                    const double* usub = nullptr, const double* asub = nullptr);
 // gate != nullptr: runs only when gate[0] == 0 (the step without a sweep)
 void launch_scale_store(double* vj, const double* r, const double* nrm2, double* beta_slot, int64_t len, hipStream_t s, const int* gate = nullptr);
+
+// ---- one-sweep full re-orthogonalisation (run_loop_one_sweep, lz_loops.hip) ----
+// G = V^T V and H (A V_i = sum_l H[l, i] V_l to rounding) are n x n, column-major (column i at [i * n]).  Per step j, in the
+// units of u_j = w_j / beta_j: the sweep applies the predicted c_hat and measures d_i = V_i . u_j from the same loads; post
+// forms e_i = d_i - c_hat_i and G[:, j]; predict forms the next step's c_hat from G, H, alpha and beta.  The per-entry
+// arithmetic below is shared by the kernels and the host check (lz_one_sweep_host, tools/one_sweep_prototype.py).
+constexpr double kOneSweepTau = 1e-14;  // gate: max |e| above this runs one correcting sweep (profiles/one_sweep_prototype.md)
+constexpr int kOneSweepMaxN = 1536;     // the sweep parks 4 x qtw_ldp(n) per-wave dots in LDS (48 KiB)
+// c_hat_i of step j + 1 (i <= j): ((A V_i) . v_j - alpha_j G[i, j] - beta_j G[i, j-1]) / sqrt(nrm2)
+__host__ __device__ inline double os_predict_one(int i, int j, int n, const double* H, const double* G, double a, double bj, double bn) {
+  double s;
+  if (i < j) {
+    s = 0.0;
+    for (int l = 0; l <= i + 1; ++l) s += H[(int64_t)i * n + l] * G[(int64_t)j * n + l];
+  } else {
+    s = a;  // V_j . A v_j: the SpMV's own dot
+  }
+  s = s - a * G[(int64_t)j * n + i];
+  if (j > 0) s = s - bj * G[(int64_t)(j - 1) * n + i];
+  return s / bn;
+}
+// G[i, j] (i < j) of v_j = (2 - cs) u_j - sum_{l<j} c_hat_l V_l: (2 - cs) d_i - sum_l c_hat_l G[i, l]
+__host__ __device__ inline double os_post_one(int i, int j, int n, const double* G, const double* d, const double* chat, double cs) {
+  double s = (2.0 - cs) * d[i];
+  for (int l = 0; l < j; ++l) s -= chat[l] * G[(int64_t)l * n + i];
+  return s;
+}
+// sweep (mode 0): V[j] = 2 u - (sum_{i<j} coef_i V_i + cs u), u = r / sqrt(nrm2) (beta stored to beta_slot); part[b * ldp + i] =
+// block b's share of V_i . u (i < j) and, at i = j, of V[j] . V[j] (ldp = qtw_ldp(j + 1)).  Mode 1 (correction, runs only when
+// gate[0] != 0): V[j] -= sum_{i<j} coef_i V_i, no dots.  Returns the number of blocks (the partial runs).
+int os_sweep_blocks(int64_t len);
+int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const double* coef, const double* r, const double* nrm2,
+                    double* beta_slot, double* part, const int* gate, hipStream_t s);
+// post (one block): d = [V_i . u_j (i < j), v_j . v_j] (the second-stage sums); writes G[:, j] / G[j, :], H[:, j-1]'s update
+// part, and when max |e| > tau the correction g (= G[:j, j]) with the corrected column; ist[0] = gate, ist[1] += trips,
+// elog[j] = max |e|
+void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, const double* nrm2, double tau,
+                    double* g, int* ist, double* elog, hipStream_t s);
+// predict (one block, after step j's three-term recurrence): chat[0..j] of step j + 1, and H[:, j]'s alpha / beta entries
+void launch_os_predict(const double* G, double* H, int n, int j, const double* alpha_j, const double* beta_j, const double* nrm2,
+                       double* chat, hipStream_t s);
 // ---- device-resident partial re-orthogonalisation (Simon's omega-recurrence in a one-block kernel) ----
 // State: st[0] = ||A|| estimate, st[1] = force_next, st[2 .. 2 + n + 2) = hb (hb[k] = the norm that formed V[k]), then three
 // rows of n + 1 doubles (omega_{j,:} lives in row j % 3); ist[0] = the gate of the coming step (1: sweep), ist[1] = number of

@@ -404,6 +404,71 @@ int run_small_engine(lz_handle h, int n, const double* v0_local, bool steps, boo
 }
 #endif  // LZ_KBENCH
 
+// ---- one-sweep full re-orthogonalisation: ONE walk over the basis per step ------------------------------------------------
+// The six-launch loop streams V twice per step (pass 1: c = V^T w, pass 2: v_j = 2 w/beta - sum c_i V_i), 16 j M bytes.  Here
+// the coefficients are PREDICTED from G = V^T V and H (A V_i = sum_l H[l, i] V_l to rounding, A symmetric):
+//   V_i . w_{j+1} = (A V_i) . v_j - alpha_j G[i, j] - beta_j G[i, j-1],  (A V_i) . v_j = sum_l H[l, i] G[l, j],  V_j . A v_j = alpha_j
+// (k_os_predict, one block), applied by ONE sweep that also measures the true dots V_i . u_j from the same loads (k_os_sweep),
+// and checked afterwards (k_os_post, one block): e = d - c_hat is, to rounding, how far v_j is from what the two-pass step
+// would have formed, and G[:, j] follows from d, c_hat and the old G.  When max |e| > kOneSweepTau a correcting sweep
+// v_j -= sum_i G[i, j] V_i runs before the SpMV (always enqueued, returns at once when the gate is 0), so the basis is never
+// more than tau from orthogonal and every step's orthogonality is measured, not assumed.  8 j M + 40 M bytes per step
+// (sweep 8 j M + 16 M, three-term 24 M) plus the SpMV.  The coefficients equal the two-pass loop's to rounding (not bit
+// for bit: the dots that decide them are summed in another order, and ||w||^2 comes from the three-term kernel).
+// One rank, fused-norm mode, full re-orthogonalisation, default kernels; lz_run_resume continues on the two-pass loop.
+int run_loop_one_sweep(lz_handle h, int n) {
+  const double M = (double)h->rows;
+  const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8;
+  if (h->os_n < n) {
+    LZ_TRY(dev_alloc(h, h->d_os, os_doubles));
+    LZ_TRY(dev_alloc(h, h->d_osi, 4));
+    h->os_n = n;
+  }
+  const int nb = os_sweep_blocks(h->rows_pad);
+  LZ_TRY(ensure_part(h, (size_t)nb * qtw_ldp(n) + 64));
+  double* G = h->d_os;
+  double* H = G + (size_t)n * n;
+  double* chat = H + (size_t)n * n;
+  double* g = chat + n + 1;
+  double* elog = g + 2 * n + 2;
+  LZ_HIP(h, hipMemsetAsync(h->d_os, 0, os_doubles * sizeof(double), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));
+  // warm-up (Lanczos.py:108-110): r = A v0; alpha0 = r.v0; r = r - alpha0 v0, ||r||^2
+  LZ_TRY(step_spmv(h, 0));
+  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
+  for (int j = 0; j < n; ++j) {
+    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
+    h->prof_iter = (j % pstride) == pstride / 2;
+    const int bidx = (j + n - 2) % (n - 1);  // beta[j-1] with Python's negative index at j = 0
+    {
+      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 4.0 * (j + 1) * M);
+      launch_os_sweep(0, h->d_V, h->ldv, h->rows_pad, j, chat, h->d_r, h->d_nrm2, h->d_beta + bidx, h->d_part, nullptr, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep"));
+    }
+    {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_final_rows_t(h->d_part, nb, qtw_ldp(j + 1), j + 1, h->d_c, h->stream);
+      LZ_TRY(check_launch(h, "final_rows(one-sweep)"));
+      launch_os_post(h->d_c, chat, G, H, n, j, h->d_nrm2, kOneSweepTau, g, h->d_osi, elog, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep post"));
+    }
+    {
+      Scope sc(h, LZ_K_QTW, 0, 0);  // (bytes are not counted: the correction runs in almost no step)
+      launch_os_sweep(1, h->d_V, h->ldv, h->rows_pad, j, g, nullptr, nullptr, nullptr, nullptr, h->d_osi, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep correction"));
+    }
+    LZ_TRY(step_spmv(h, j));
+    // at j = 0 the reference subtracts beta * V[-1], the still-zero last row: a no-op
+    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, true));
+    if (j + 1 < n) {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_os_predict(G, H, n, j, h->d_alpha + j, h->d_beta + bidx, h->d_nrm2, chat, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep predict"));
+    }
+  }
+  return LZ_OK;
+}
+
 // ---- which loop structure runs the Krylov iteration --------------------------------------------------------------------
 // (the values are what lz_last_engine reports)
 enum Loop {
@@ -415,7 +480,8 @@ enum Loop {
   LOOP_ONE_REDUCE_REPEATED = 5,  // a one-reduce run whose cancellation guard fired: repeated on the default loop
   LOOP_ONE_REDUCE = 6,        // LZ_FLAG_ONE_REDUCE: one all-reduce per iteration
   LOOP_PARTIAL_DEVICE = 7,    // LZ_FLAG_REORTH_PARTIAL, default: the omega-recurrence and the sweep decision live on the device
-  LOOP_PARTIAL_ONE_REDUCE = 8 // LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE: the same with one all-reduce per iteration (look-ahead gate)
+  LOOP_PARTIAL_ONE_REDUCE = 8, // LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE: the same with one all-reduce per iteration (look-ahead gate)
+  LOOP_ONE_SWEEP = 9          // above kThreeTermFusedMaxRows rows on one rank: one walk over the basis per step (run_loop_one_sweep)
 };
 
 Loop choose_loop(lz_handle h, int n) {
@@ -438,9 +504,13 @@ Loop choose_loop(lz_handle h, int n) {
 #else
   const bool knob_auto = h->tune[15] == 0;
 #endif
+  // one-sweep loop: one rank, full fused-norm re-orthogonalisation, default kernels, no overlap; tune[15] == 6 forces it at any size
+  const bool one_sweep_ok = one_rank && full_fused && default_kernels && !(f & LZ_FLAG_OVERLAP_HALO) && n >= 2 && n <= kOneSweepMaxN;
+  if (h->tune[15] == 6 && one_sweep_ok) return LOOP_ONE_SWEEP;
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
   if (one_rank && h->qplan.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)h->qplan.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;
+  if (one_sweep_ok) return LOOP_ONE_SWEEP;
   return LOOP_SIX;
 }
 
@@ -955,10 +1025,11 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
     case LOOP_ONE_REDUCE: LZ_TRY(run_loop_onereduce(h, n)); break;
     case LOOP_PARTIAL_DEVICE: LZ_TRY(run_loop_partial_device(h, n)); break;
     case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
+    case LOOP_ONE_SWEEP: LZ_TRY(run_loop_one_sweep(h, n)); break;
     default: LZ_TRY(run_loop_six(h, n, &sweeps)); break;
   }
   h->last_sweeps = sweeps;
-  h->r_state = (h->last_engine == LOOP_SIX || h->last_engine == LOOP_PARTIAL_DEVICE) ? 1
+  h->r_state = (h->last_engine == LOOP_SIX || h->last_engine == LOOP_PARTIAL_DEVICE || h->last_engine == LOOP_ONE_SWEEP) ? 1
                : (h->last_engine == LOOP_FUSED_SMALL || h->last_engine == LOOP_THREE_TERM_FUSED) ? 2 : 0;
   h->prof_iter = true;
   LZ_HIP(h, hipEventRecord(h->run_b, h->stream));
@@ -968,6 +1039,8 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   LZ_HIP(h, hipMemcpyAsync(beta_out, h->d_beta, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   double onered_bad = 0.0;
   if (one_reduce) LZ_HIP(h, hipMemcpyAsync(&onered_bad, h->d_nrm2 + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  int gate_trips = 0;
+  if (loop == LOOP_ONE_SWEEP) LZ_HIP(h, hipMemcpyAsync(&gate_trips, h->d_osi + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   std::vector<int> sweep_log;
   if (loop == LOOP_PARTIAL_DEVICE || loop == LOOP_PARTIAL_ONE_REDUCE) {
     sweep_log.resize(loop == LOOP_PARTIAL_DEVICE ? omega_state_ints(n) : omega_onered_ints(n));
@@ -975,6 +1048,7 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   }
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   h->last_misses = 0;
+  h->last_gate_trips = gate_trips;
   h->sweep_log.assign((size_t)n, 1);  // which steps ran the sweep (lz_last_sweep_log): all of them unless a partial loop says otherwise
   if (loop == LOOP_SIX && (h->flags & LZ_FLAG_REORTH_PARTIAL)) h->sweep_log.clear();  // (the host-decided loop keeps no per-step record)
   if (loop == LOOP_PARTIAL_DEVICE) {
@@ -1074,6 +1148,7 @@ int lz_run_resume_partial(lz_handle h, int n, int j0, const double* V_rows, int6
   LZ_HIP(h, hipMemcpyAsync(sweep_log.data(), h->d_omi, sweep_log.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   h->last_misses = 0;
+  h->last_gate_trips = 0;
   h->sweep_log.assign((size_t)n, 0);  // (the steps of the first leg are not on this record)
   account_partial_device(h, n, sweep_log, &h->last_sweeps);
   for (int j = j0; j < n; ++j) h->sweep_log[(size_t)j] = sweep_log[(size_t)2 + j] != 0;
@@ -1107,6 +1182,7 @@ int lz_run_resume(lz_handle h, int n, int j0, const double* V_rows, int64_t ldv_
   LZ_TRY(run_loop_six(h, n, &sweeps, j0));
   h->last_sweeps = sweeps;
   h->last_misses = 0;
+  h->last_gate_trips = 0;
   h->sweep_log.assign((size_t)n, 1);
   h->r_state = 1;
   h->prof_iter = true;

@@ -1336,4 +1336,248 @@ void launch_gather(const double* x, const int32_t* idx, int64_t n, double* buf, 
   hipLaunchKernelGGL(k_gather, dim3((int)((n + kTPB - 1) / kTPB)), dim3(kTPB), 0, s, x, idx, n, buf);
 }
 
+// ------------------------------------------------------------------ one-sweep full re-orthogonalisation
+// One walk over the basis per step instead of two (run_loop_one_sweep, lz_loops.hip): the coefficients are predicted from
+// G = V^T V and H (k_os_predict) and applied here, and the dots V_i . u that pass 1 would form are measured from the SAME
+// loads, so k_os_post can check the prediction (e = d - c_hat) and correct in the rare step that needs it.  The walk is
+// k_update_slice's: a block owns kTPB * P consecutive double2 positions, RU rows x P positions of non-temporal loads in flight
+// per lane, running sums in registers, the new row written in bursts at the end.  Per row each wave adds up its share of the
+// dot with one shuffle tree and parks it in LDS; the four waves' runs leave as one contiguous run per block (k_final_rows_t
+// adds them up).  Per row and lane: P 16-byte loads against 4P FMAs + a 6-step shuffle tree - still far below the VALU
+// rate at the HBM rate.
+template <int P, int RU, int MODE>
+__global__ __launch_bounds__(kTPB) void k_os_sweep(double* __restrict__ V, int64_t ldv, int64_t n2, int j, const double* __restrict__ coef,
+                                                  const double* __restrict__ r, const double* __restrict__ nrm2,
+                                                  double* __restrict__ beta_slot, int ldp, double* __restrict__ part,
+                                                  const int* __restrict__ gate) {
+  if (MODE == 1 && gate[0] == 0) return;  // no correction due on this step
+  extern __shared__ double keep[];        // [kTPB / 64][ldp]: this block's per-wave dots
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
+  const int64_t ld2 = ldv >> 1;
+  const double2* V2 = reinterpret_cast<const double2*>(V);
+  double2* out = reinterpret_cast<double2*>(V) + (int64_t)j * ld2;
+  int64_t pos[P];
+  bool ok[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    pos[p] = base + (int64_t)p * kTPB;
+    ok[p] = pos[p] < n2;
+    if (!ok[p]) pos[p] = n2 - 1;  // valid address, result discarded
+  }
+  double2 w[P];
+  double b = 1.0, cs = 0.0;
+  if (MODE == 0) {
+    const double s2 = nrm2[0];
+    b = sqrt(s2);
+    cs = s2 / (b * b);  // the self term c_j = ||w||^2 / beta^2 (k_update_slice's raw_c arithmetic)
+    if (blockIdx.x == 0 && threadIdx.x == 0) beta_slot[0] = b;
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    if (MODE == 0) {
+      w[p] = reinterpret_cast<const double2*>(r)[pos[p]];
+      w[p].x = w[p].x / b;
+      w[p].y = w[p].y / b;
+    } else {
+      w[p] = out[pos[p]];
+    }
+    if (!ok[p]) w[p] = make_double2(0.0, 0.0);  // so the clamped duplicates add nothing to the dots
+  }
+  double tx[P], ty[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) tx[p] = ty[p] = 0.0;
+  for (int k = 0; k < j; k += RU) {
+    double2 q[RU][P];
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < j) {  // block-uniform
+        const double2* row = V2 + (int64_t)(k + u) * ld2;
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(row + pos[p]);
+      }
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < j) {
+        const double ck = coef[k + u];
+        double d = 0.0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          tx[p] = tx[p] + ck * q[u][p].x;
+          ty[p] = ty[p] + ck * q[u][p].y;
+          if (MODE == 0) {
+            d = fma(q[u][p].x, w[p].x, d);
+            d = fma(q[u][p].y, w[p].y, d);
+          }
+        }
+        if (MODE == 0) {
+          d = wave_sum(d);
+          if (lane == 0) keep[wv * ldp + k + u] = d;
+        }
+      }
+  }
+  double vv = 0.0;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    double2 o;
+    if (MODE == 0) {
+      tx[p] = tx[p] + cs * w[p].x;  // row j (u itself) is the last term of the sum, as in k_update_slice
+      ty[p] = ty[p] + cs * w[p].y;
+      o = make_double2(2.0 * w[p].x - tx[p], 2.0 * w[p].y - ty[p]);
+    } else {
+      o = make_double2(w[p].x - tx[p], w[p].y - ty[p]);
+    }
+    if (ok[p]) {
+      st_stream<1>(out + pos[p], o);
+      vv = fma(o.x, o.x, vv);
+      vv = fma(o.y, o.y, vv);
+    }
+  }
+  if (MODE == 1) return;
+  vv = wave_sum(vv);
+  if (lane == 0) keep[wv * ldp + j] = vv;
+  __syncthreads();
+  double* mine = part + (int64_t)blockIdx.x * ldp;
+  for (int i = threadIdx.x; i <= j; i += kTPB)
+    __builtin_nontemporal_store(((keep[i] + keep[ldp + i]) + keep[2 * ldp + i]) + keep[3 * ldp + i], mine + i);
+}
+
+// positions per lane: k_update_slice's choice (the P whose block count spreads most evenly over the CUs, ties to the larger
+// P; 16 loads in flight per lane), and one position per lane for short vectors
+static int os_sweep_p(int64_t n2) {
+  if (n2 <= 16384) return 1;
+  for (int cand : {16, 8, 4, 2}) {
+    const int64_t G = (n2 + (int64_t)kTPB * cand - 1) / ((int64_t)kTPB * cand);
+    const double g = (double)G / kNumCU;
+    if (g / std::ceil(g) >= 0.93) return cand;
+  }
+  double best = -1.0;
+  int P = 2;
+  for (int cand : {16, 8, 4, 2}) {
+    const int64_t G = (n2 + (int64_t)kTPB * cand - 1) / ((int64_t)kTPB * cand);
+    const double g = (double)G / kNumCU, bal = g / std::ceil(g);
+    if (bal > best) {
+      best = bal;
+      P = cand;
+    }
+  }
+  return P;
+}
+
+int os_sweep_blocks(int64_t len) {
+  const int64_t n2 = len >> 1;
+  const int P = os_sweep_p(n2);
+  return (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+}
+
+int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const double* coef, const double* r, const double* nrm2,
+                    double* beta_slot, double* part, const int* gate, hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  const int P = os_sweep_p(n2);
+  const int grid = (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+  const int ldp = qtw_ldp(j + 1);
+  const size_t lds = mode == 0 ? (size_t)(kTPB / 64) * ldp * sizeof(double) : 0;
+#define LZ_OS_GO(PP, RR)                                                                                                          \
+  do {                                                                                                                            \
+    if (mode == 0)                                                                                                                \
+      hipLaunchKernelGGL((k_os_sweep<PP, RR, 0>), dim3(grid), dim3(kTPB), lds, s, V, ldv, n2, j, coef, r, nrm2, beta_slot, ldp, part, gate); \
+    else                                                                                                                          \
+      hipLaunchKernelGGL((k_os_sweep<PP, RR, 1>), dim3(grid), dim3(kTPB), lds, s, V, ldv, n2, j, coef, r, nrm2, beta_slot, ldp, part, gate); \
+  } while (0)
+  switch (P) {
+    case 16: LZ_OS_GO(16, 1); break;
+    case 8: LZ_OS_GO(8, 2); break;
+    case 4: LZ_OS_GO(4, 4); break;
+    case 2: LZ_OS_GO(2, 8); break;
+    default: LZ_OS_GO(1, 16); break;
+  }
+#undef LZ_OS_GO
+  return grid;
+}
+
+// k_os_post: one block.  max |e| is a max (order-free); every other sum runs in index order (os_post_one).
+__global__ __launch_bounds__(kFinalThreads) void k_os_post(const double* __restrict__ d, const double* __restrict__ chat, double* __restrict__ G,
+                                                          double* __restrict__ H, int n, int j, const double* __restrict__ nrm2, double tau,
+                                                          double* __restrict__ g, int* __restrict__ ist, double* __restrict__ elog) {
+  extern __shared__ double col[];  // [j + 1]
+  __shared__ double smax[kFinalThreads / 64];
+  __shared__ int s_trip;
+  const double s2 = nrm2[0];
+  const double b = sqrt(s2), cs = s2 / (b * b);
+  double em = 0.0;
+  for (int i = threadIdx.x; i < j; i += kFinalThreads) {
+    em = fmax(em, fabs(d[i] - chat[i]));
+    col[i] = os_post_one(i, j, n, G, d, chat, cs);
+  }
+  if (threadIdx.x == 0) col[j] = d[j];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) em = fmax(em, __shfl_down(em, off, 64));
+  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = em;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double m = 0.0;
+    for (int k = 0; k < kFinalThreads / 64; ++k) m = fmax(m, smax[k]);
+    const int trip = (j > 0 && !(m <= tau)) ? 1 : 0;  // (a NaN leftover trips the gate too)
+    s_trip = trip;
+    elog[j] = m;
+    ist[0] = trip;
+    ist[1] += trip;
+  }
+  __syncthreads();
+  const int trip = s_trip;
+  if (trip) {
+    // correction v_j -= sum_i g_i V_i with g = G[:j, j]: new G[i, j] = G[i, j] - sum_l G[i, l] g_l, new v.v from the old column
+    for (int i = threadIdx.x; i < j; i += kFinalThreads) g[i] = col[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < j; i += kFinalThreads) {
+      double s = g[i];
+      for (int l = 0; l < j; ++l) s -= G[(int64_t)l * n + i] * g[l];
+      double t = -2.0 * g[i];
+      for (int l = 0; l < j; ++l) t += G[(int64_t)l * n + i] * g[l];
+      col[i] = s;
+      g[n + i] = g[i] * t;  // this row's share of the change of v.v (g has 2n doubles)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double vv = col[j];
+      for (int i = 0; i < j; ++i) vv += g[n + i];
+      col[j] = vv;
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i <= j; i += kFinalThreads) {
+    G[(int64_t)j * n + i] = col[i];
+    G[(int64_t)i * n + j] = col[i];
+  }
+  if (j > 0) {  // w_j = b / (2 - cs) (v_j + sum_{l<j} c_l V_l), c the applied coefficients: column j - 1 of H
+    const double f = b / (2.0 - cs);
+    double* hc = H + (int64_t)(j - 1) * n;
+    for (int l = threadIdx.x; l < j; l += kFinalThreads) {
+      const double c = trip ? chat[l] + g[l] : chat[l];
+      hc[l] = hc[l] + f * c;
+    }
+    if (threadIdx.x == 0) hc[j] = f;
+  }
+}
+
+void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, const double* nrm2, double tau,
+                    double* g, int* ist, double* elog, hipStream_t s) {
+  hipLaunchKernelGGL(k_os_post, dim3(1), dim3(kFinalThreads), (size_t)(j + 1) * sizeof(double), s, d, chat, G, H, n, j, nrm2, tau, g, ist, elog);
+}
+
+__global__ __launch_bounds__(kFinalThreads) void k_os_predict(const double* __restrict__ G, double* __restrict__ H, int n, int j,
+                                                             const double* __restrict__ alpha_j, const double* __restrict__ beta_j,
+                                                             const double* __restrict__ nrm2, double* __restrict__ chat) {
+  const double a = alpha_j[0], bj = j > 0 ? beta_j[0] : 0.0, bn = sqrt(nrm2[0]);
+  for (int i = threadIdx.x; i <= j; i += kFinalThreads) chat[i] = os_predict_one(i, j, n, H, G, a, bj, bn);
+  // column j of H: alpha_j on the diagonal, beta_j above it; k_os_post of step j + 1 adds the w_{j+1} terms
+  double* hc = H + (int64_t)j * n;
+  for (int l = threadIdx.x; l < n; l += kFinalThreads) hc[l] = l == j ? a : (l == j - 1 ? bj : 0.0);
+}
+
+void launch_os_predict(const double* G, double* H, int n, int j, const double* alpha_j, const double* beta_j, const double* nrm2,
+                       double* chat, hipStream_t s) {
+  hipLaunchKernelGGL(k_os_predict, dim3(1), dim3(kFinalThreads), 0, s, G, H, n, j, alpha_j, beta_j, nrm2, chat);
+}
+
 }  // namespace lz
