@@ -76,6 +76,8 @@ enum lz_flags {
                                  recurrence taken from reduced sums only, so every rank agrees (lz_last_sweep_misses counts
                                  the vectors the look-ahead should have swept and did not; they are swept one step late).
                                  Same guard; a repeat runs the three-collective partial loop (engine 5).              */
+  LZ_FLAG_TRL_PASS2_ALWAYS = 512, /* thick-restart Lanczos (lz_trl_extend): run the second Gram-Schmidt pass at every step instead of
+                                     only where the DGKS criterion asks for it (tests) */
   LZ_FLAG_REORTH_PARTIAL = 64 /* opt-in: partial re-orthogonalisation (Simon 1984).  The reference sweeps the whole basis
                                  every step; with this flag the sweep (same kernels, same arithmetic) runs only when the
                                  omega-recurrence estimate of the loss of orthogonality exceeds sqrt(eps), on that and the
@@ -398,6 +400,34 @@ int lz_step_reorth(lz_handle h, int j, int nrows, int scale, double* beta_out, d
 int lz_step_three_term(lz_handle h, int j, int jm1, double alpha, double beta, double* norm2_out);
 /* y = A x on host vectors (length rows_local / ncols_ext handled internally; single rank) */
 int lz_spmv_host(lz_handle h, const double* x, double* y);
+
+/* ---- thick-restart Lanczos (lanczos_amd.eigsh; Wu & Simon 2000) ----------------------------------------------------------------
+ * Replaces the host ARPACK call of find_exact_eigs (Lanczos.py:68-71: scipy.sparse.linalg.eigsh) for matrices that live on the device.
+ * The host runs the outer loop (restart policy, eigh of the m x m projected matrix T, stopping test: lanczos_amd/eigsh.py); these calls
+ * do every pass over the basis.  The basis is a buffer of its own - m + 1 rows of the padded row length - so a fixed-n run's V / Y on
+ * the same handle are left alone.  One rank only: a handle with a communicator, LZ_FLAG_REORTH_PARTIAL or LZ_FLAG_ONE_REDUCE gets
+ * LZ_ERR_STATE.  LZ_FLAG_TRL_PASS2_ALWAYS forces the second Gram-Schmidt pass of every extension step (tests). */
+/* allocate the basis for m (2 <= m <= min(128, rows)) vectors plus the residual row, zero it, V[0] = v0 / |v0| */
+int lz_trl_begin(lz_handle h, int m, const double* v0);
+/* steps j = k .. m-1 without a host synchronisation: w = A V[j]; c = V[0..j] . w, w -= sum c_i V_i (classical Gram-Schmidt); a second
+ * such pass only when |w| fell below |w_before| / sqrt 2 (DGKS; the decision is taken on the device); beta_j = |w|, V[j + 1] = w / beta_j.
+ * proj_out (m x m row-major): row j receives the measured projection T[0..j, j] (both passes' sums), rows k .. m-1 only;
+ * beta_out[m]: beta_j at [j] (beta_{m-1} is the norm of the residual row V[m]).  Either may be NULL. */
+int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out);
+/* in place: V[0..kk) = S^T V[0..m) with S (m x kk, row-major: column i = the i-th kept Ritz vector of T), then V[kk] = V[m]
+ * (1 <= kk < m).  Reads (m + kk) rows and writes kk + 1; the padding of every row is left as it is. */
+int lz_trl_restart(lz_handle h, int m, int kk, const double* S);
+/* V[k] = x (rows_local doubles) made orthogonal to V[0..k) by two classical Gram-Schmidt passes and normalised (0 <= k <= m): the
+ * probe direction and the fresh start after a breakdown */
+int lz_trl_probe(lz_handle h, int k, const double* x);
+/* the first k basis rows (after the final restart: the Ritz vectors) as an (rows_local, k) row-major array, through the staging ring */
+int lz_trl_get_vectors(lz_handle h, int k, double* Y_out);
+/* out[i] = |A V[i] - theta[i] V[i]| for i < k: one fused SpMV-and-norm launch (CSR, the assembled stencil included); dense: the GEMV */
+int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out);
+/* raw basis rows j0 .. j0 + count - 1 (0 <= j0, j0 + count <= m + 1) including their padding (lz_padded_rows(rows) doubles each), host
+ * rows ld >= that apart: tests of the restart kernel */
+int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
+int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
 
 /* ---- two-sided (bi-orthogonal) Lanczos: the Irregular copy's execute_Lanczos --------------------------------
  * Replaces Python/Irregular/IrrLanczos.py:77-187 (driver loop) and :408-441 (bireorthogonalize, default branch).

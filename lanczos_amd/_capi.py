@@ -29,6 +29,7 @@ FLAG_SPMV_STREAM = 32
 FLAG_REORTH_PARTIAL = 64
 FLAG_OVERLAP_HALO = 128
 FLAG_ONE_REDUCE = 256
+FLAG_TRL_PASS2_ALWAYS = 512  # thick-restart Lanczos: the second Gram-Schmidt pass at every extension step (default: where DGKS asks for it)
 
 # lz_set_tuning knob indices (the legend lives in include/lanczos_hip.h)
 TUNE_QTW_SLICE = 0          # Q^T w slice length per block
@@ -157,6 +158,14 @@ SIGNATURES = {
     "lz_bi_get_row": (C.c_int, [_P, C.c_int, C.c_int, _D]),
     "lz_step_bireorth": (C.c_int, [_P, C.c_int]),
     "lz_step_bireorth_mem_safe": (C.c_int, [_P, C.c_int]),
+    "lz_trl_begin": (C.c_int, [_P, C.c_int, _D]),
+    "lz_trl_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_trl_restart": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_trl_probe": (C.c_int, [_P, C.c_int, _D]),
+    "lz_trl_get_vectors": (C.c_int, [_P, C.c_int, _D]),
+    "lz_trl_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_trl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_trl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
 }
 
 
@@ -755,6 +764,47 @@ class Handle:
 
     def step_bireorth_mem_safe(self, j):
         self.check(self.lib.lz_step_bireorth_mem_safe(self._h, int(j)))
+
+    # -- thick-restart Lanczos (lanczos_amd.eigsh): a basis of its own, never the fixed-n run's V / Y
+    def trl_begin(self, m, v0):
+        self.trl_m = int(m)
+        self.check(self.lib.lz_trl_begin(self._h, int(m), dptr(f64(v0))))
+
+    def trl_extend(self, k, m):
+        """steps k .. m-1 -> (proj (m, m): row j = T[0..j, j] for j >= k, beta (m,))"""
+        proj = np.zeros((m, m))
+        beta = np.zeros(m)
+        self.check(self.lib.lz_trl_extend(self._h, int(k), int(m), dptr(proj), dptr(beta)))
+        return proj, beta
+
+    def trl_restart(self, m, kk, S):
+        S = f64(S)
+        assert S.shape == (m, kk)
+        self.check(self.lib.lz_trl_restart(self._h, int(m), int(kk), dptr(S)))
+
+    def trl_probe(self, k, x):
+        self.check(self.lib.lz_trl_probe(self._h, int(k), dptr(f64(x))))
+
+    def trl_get_vectors(self, k):
+        Y = np.empty((self.rows, int(k)))
+        self.check(self.lib.lz_trl_get_vectors(self._h, int(k), dptr(Y)))
+        return Y
+
+    def trl_residuals(self, k, theta):
+        th = f64(theta)[: int(k)]
+        out = np.empty(int(k))
+        self.check(self.lib.lz_trl_residuals(self._h, int(k), dptr(th), dptr(out)))
+        return out
+
+    def trl_set_rows(self, j0, rows):
+        """raw basis rows j0 .. j0 + len(rows) - 1 including their padding: rows is (count, >= padded_rows(M))"""
+        rows = f64(rows)
+        self.check(self.lib.lz_trl_set_rows(self._h, int(j0), rows.shape[0], dptr(rows), rows.shape[1]))
+
+    def trl_get_rows(self, j0, count):
+        out = np.empty((int(count), self.padded_rows(self.rows)))
+        self.check(self.lib.lz_trl_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
+        return out
 
     def spmv_host(self, x, ncols=None):
         x = f64(x)

@@ -169,6 +169,8 @@ class LanczosBase:
     strict_use_cuda = False  # True: use_cuda=False raises NotImplementedError instead of running the HIP path with a notice
     cache_matrix = True  # keep H on the device across execute_Lanczos calls while its content hash is unchanged
     _check_eigs = ("normalized", "orthogonal")  # which asserts get_H_eigs runs (Lanczos.py:157-158)
+    exact_eigs = "scipy"  # what find_exact_eigs runs: "scipy" = the reference's host ARPACK call; "device" = lanczos_amd.eigsh on a
+                          # handle of its own (thick-restart Lanczos on the GPU; H is never assembled on the host)
 
     def __init__(self, H):
         self.H = H
@@ -264,6 +266,17 @@ class LanczosBase:
         return self._timings
 
     def find_exact_eigs(self, nr_vecs=20):
+        if self.exact_eigs == "device":
+            if self._multi():
+                raise ValueError("exact_eigs = 'device' runs on one GPU: it cannot be combined with a devices list of more than one GPU")
+            from .eigsh import eigsh
+
+            self._say("+++ Calculating exact eigs using scipy.sparse.linalg.eigsh.")
+            self._H_eigvals_actual, self._H_eigvecs_actual = eigsh(self.H, k=nr_vecs, which="SM", device_id=self.device_id)
+            self._say("+++ Finished calculating exact eigs.")
+            return
+        if self.exact_eigs != "scipy":
+            raise ValueError(f"exact_eigs must be 'scipy' or 'device', not {self.exact_eigs!r}")
         self._say("+++ Calculating exact eigs using scipy.sparse.linalg.eigsh.")
         H = self.H.to_scipy() if hasattr(self.H, "to_scipy") else self.H  # (a StencilOperator / synthetic.CSR is materialised for SciPy)
         self._H_eigvals_actual, self._H_eigvecs_actual = scipy.sparse.linalg.eigsh(H, k=nr_vecs, which="SM")

@@ -511,6 +511,11 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_omi);
   big_free(h->res_V);
   big_free(h->res_Y);
+  big_free(h->d_trl);
+  big_free(h->d_tw);
+  big_free(h->d_tsm);
+  big_free(h->d_tgate);
+  big_free(h->d_tpart);
   if (h->h_pinned) hipHostFree(h->h_pinned);
   xfer_free(h->xfer);
   if (h->cstream) {

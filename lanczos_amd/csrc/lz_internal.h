@@ -296,6 +296,20 @@ int launch_ritz_quality(const CsrDev& A, const double* Y, int64_t ldy, int n, do
 // x[r] = Y[r * ldy + col] for r < rows, 0 for rows <= r < rows_pad
 void launch_extract_column(const double* Y, int64_t ldy, int col, int64_t rows, int64_t rows_pad, double* x, hipStream_t s);
 
+// ---- thick-restart Lanczos (lz_trl.hip; C ABI in lz_trl_api.hip) ----
+// V[0..kk) = S^T V[0..m) in place (S: m x kk row-major, m <= 128, kk < m), then V[kk] = V[m]; positions >= rows are not written
+hipError_t launch_trl_restart(double* V, int64_t ldv, int64_t rows, int m, int kk, const double* S, hipStream_t s);
+// r = r - sum_{i < nrows} c_i V_i and part[b] = block b's share of |r|^2; runs only when gate == nullptr or gate[0] != 0.  Returns the
+// number of partials (trl_cgs_blocks(len)).
+int launch_trl_cgs(const double* V, int64_t ldv, int64_t len, int nrows, const double* c, double* r, double* part, const int* gate, hipStream_t s);
+int trl_cgs_blocks(int64_t len);
+// one block between the passes of an extension step (mode 0: after pass 1, sets the gate of pass 2; 1: after the gated pass 2; 2: norm only)
+void launch_trl_post(int mode, const double* part, int np, const double* c, int j, double* nrm2, double* proj, int* gate, int force, hipStream_t s);
+// squares of A y_i - theta_i y_i, block partials at part[i * G + b]; return G
+int launch_trl_resid_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* theta, double* part, hipStream_t s);
+int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s);
+void launch_trl_rownorm(const double* part, int G, int k, double* out, hipStream_t s);
+
 // ---- small-problem engine (lz_small.hip): the whole run as one cooperative kernel
 struct SmallArgs {
   int kind;  // 1 CSR, 2 dense

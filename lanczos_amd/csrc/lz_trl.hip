@@ -1,0 +1,253 @@
+// Kernels of the thick-restart Lanczos solver (lz_trl_api.hip, lanczos_amd/eigsh.py): the in-place restart V[0..kk) <- S^T V[0..m),
+// the classical Gram-Schmidt update of r, the one-block bookkeeping between the passes, and the fused residual norms.
+#include "lz_device.h"
+
+namespace lz {
+
+// ------------------------------------------------------------------ restart: V[k][p] = sum_{i < m} S[i][k] V[i][p] (k < kk), V[kk] = V[m]
+// v_mfma_f64_16x16x4_f64 (lane layout: lz_gemm.hip): D (16 outputs k x 16 positions) += A (16 x 4: S^T, from LDS) B (4 basis rows x 16
+// positions).  A wave owns a 32-position tile (one 16-byte load per lane and k-step: rows 4t..4t+3 x 256 contiguous bytes; the even
+// positions feed accE, the odd ones accO) and keeps all kk outputs of the tile in its accumulators, so it has read all m input rows of
+// the tile before it writes any output row of it: tiles are disjoint, so the transform is race-free in place without a second buffer.
+// Positions >= rows (the padding of a row) are read - they only reach their own output columns - and never written.
+template <int KT>
+__global__ __launch_bounds__(kTPB) void k_trl_restart(double* __restrict__ V, int64_t ldv, int64_t rows, int64_t ntiles, int m, int kk,
+                                                      const double* __restrict__ S) {
+  extern __shared__ double sS[];  // [KS][KT][64]: lane l of the A fragment of k-step t, output tile q = S[4t + (l >> 4)][16q + (l & 15)]
+  const int KS = (m + 3) >> 2;
+  for (int f = threadIdx.x; f < KS * KT * 64; f += kTPB) {
+    const int t = f / (KT * 64), q = (f / 64) % KT, l = f & 63;
+    const int i = 4 * t + (l >> 4), c = 16 * q + (l & 15);
+    sS[f] = (i < m && c < kk) ? S[(int64_t)i * kk + c] : 0.0;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  for (int64_t tile = (int64_t)blockIdx.x * (kTPB / 64) + w; tile < ntiles; tile += (int64_t)gridDim.x * (kTPB / 64)) {
+    const int64_t p = tile * 32 + 2 * lr;
+    double4_t accE[KT], accO[KT];
+#pragma unroll
+    for (int q = 0; q < KT; ++q) accE[q] = accO[q] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    for (int t0 = 0; t0 < KS; t0 += 8) {
+      d2v_t b[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        int i = 4 * (t0 + u) + lk;
+        i = i < m ? i : m - 1;  // rows past m: any valid row, its S entries are 0
+        b[u] = t0 + u < KS ? __builtin_nontemporal_load(reinterpret_cast<const d2v_t*>(V + (int64_t)i * ldv + p)) : (d2v_t){0.0, 0.0};
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (t0 + u < KS) {
+#pragma unroll
+          for (int q = 0; q < KT; ++q) {
+            const double a = sS[((t0 + u) * KT + q) * 64 + lane];
+            accE[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].x, accE[q], 0, 0, 0);
+            accO[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].y, accO[q], 0, 0, 0);
+          }
+        }
+    }
+    // every load of the tile has been consumed by the MFMAs above: the rows may now be overwritten
+    const bool both = p + 1 < rows, one = p < rows;
+#pragma unroll
+    for (int q = 0; q < KT; ++q)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int k = 16 * q + lk + 4 * g;
+        if (k < kk) {
+          double* dst = V + (int64_t)k * ldv + p;
+          if (both)
+            *reinterpret_cast<double2*>(dst) = make_double2(accE[q][g], accO[q][g]);
+          else if (one)
+            dst[0] = accE[q][g];
+        }
+      }
+    if (lk == 0) {
+      const double2 r = *reinterpret_cast<const double2*>(V + (int64_t)m * ldv + p);
+      double* dst = V + (int64_t)kk * ldv + p;
+      if (both)
+        *reinterpret_cast<double2*>(dst) = r;
+      else if (one)
+        dst[0] = r.x;
+    }
+  }
+}
+
+template <int KT>
+static hipError_t launch_trl_restart_t(double* V, int64_t ldv, int64_t rows, int m, int kk, const double* S, hipStream_t s) {
+  const int64_t ntiles = (rows + 31) / 32;
+  const size_t lds = (size_t)((m + 3) / 4) * KT * 64 * sizeof(double);
+  hipError_t err = hipSuccess;
+  if (lds > 65536) err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_trl_restart<KT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (err != hipSuccess) return err;
+  const int64_t grid = std::min<int64_t>((ntiles + 3) / 4, 8 * kNumCU);
+  hipLaunchKernelGGL(k_trl_restart<KT>, dim3((unsigned)grid), dim3(kTPB), lds, s, V, ldv, rows, ntiles, m, kk, S);
+  return hipSuccess;
+}
+
+hipError_t launch_trl_restart(double* V, int64_t ldv, int64_t rows, int m, int kk, const double* S, hipStream_t s) {
+  switch ((kk + 15) / 16) {
+    case 1: return launch_trl_restart_t<1>(V, ldv, rows, m, kk, S, s);
+    case 2: return launch_trl_restart_t<2>(V, ldv, rows, m, kk, S, s);
+    case 3: return launch_trl_restart_t<3>(V, ldv, rows, m, kk, S, s);
+    case 4: return launch_trl_restart_t<4>(V, ldv, rows, m, kk, S, s);
+    case 5: return launch_trl_restart_t<5>(V, ldv, rows, m, kk, S, s);
+    case 6: return launch_trl_restart_t<6>(V, ldv, rows, m, kk, S, s);
+    case 7: return launch_trl_restart_t<7>(V, ldv, rows, m, kk, S, s);
+    case 8: return launch_trl_restart_t<8>(V, ldv, rows, m, kk, S, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ------------------------------------------------------------------ CGS update: r = r - sum_{i < nrows} c_i V_i, part[b] = block b's share of r.r
+// A lane owns P double2 positions and walks the rows RU at a time (P * RU 16-byte loads in flight); the sum is formed in row order
+// (products and sums rounded separately, as k_update_slice does) and subtracted once.  gate: runs only when gate[0] != 0.
+template <int P, int RU>
+__global__ __launch_bounds__(kTPB) void k_trl_cgs(const double* __restrict__ V, int64_t ldv, int64_t n2, int nrows, const double* __restrict__ c,
+                                                  double* __restrict__ r, double* __restrict__ part, const int* __restrict__ gate) {
+  if (gate && gate[0] == 0) return;
+  __shared__ double sm[kTPB / 64];
+  const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
+  const int64_t ld2 = ldv >> 1;
+  const double2* V2 = reinterpret_cast<const double2*>(V);
+  double2* r2 = reinterpret_cast<double2*>(r);
+  int64_t pos[P];
+  bool ok[P];
+  double tx[P], ty[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    pos[p] = base + (int64_t)p * kTPB;
+    ok[p] = pos[p] < n2;
+    if (!ok[p]) pos[p] = n2 - 1;
+    tx[p] = ty[p] = 0.0;
+  }
+  for (int k = 0; k < nrows; k += RU) {
+    double2 q[RU][P];
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < nrows)
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(V2 + (int64_t)(k + u) * ld2 + pos[p]);
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < nrows) {
+        const double ck = c[k + u];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          tx[p] = tx[p] + ck * q[u][p].x;
+          ty[p] = ty[p] + ck * q[u][p].y;
+        }
+      }
+  }
+  double ss = 0.0;
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+    if (ok[p]) {
+      double2 x = r2[pos[p]];
+      x.x = x.x - tx[p];
+      x.y = x.y - ty[p];
+      r2[pos[p]] = x;
+      ss = fma(x.x, x.x, ss);
+      ss = fma(x.y, x.y, ss);
+    }
+  ss = block_sum(ss, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = ss;
+}
+
+int launch_trl_cgs(const double* V, int64_t ldv, int64_t len, int nrows, const double* c, double* r, double* part, const int* gate,
+                   hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  if (n2 >= (int64_t)kTPB * 4 * kNumCU) {  // long rows: 4 positions x 4 rows in flight per lane
+    const int grid = (int)((n2 + kTPB * 4 - 1) / (kTPB * 4));
+    hipLaunchKernelGGL((k_trl_cgs<4, 4>), dim3(grid), dim3(kTPB), 0, s, V, ldv, n2, nrows, c, r, part, gate);
+    return grid;
+  }
+  const int grid = (int)((n2 + kTPB - 1) / kTPB);  // short rows: one position per lane, 16 rows in flight
+  hipLaunchKernelGGL((k_trl_cgs<1, 16>), dim3(grid), dim3(kTPB), 0, s, V, ldv, n2, nrows, c, r, part, gate);
+  return grid;
+}
+int trl_cgs_blocks(int64_t len) {
+  const int64_t n2 = len >> 1;
+  return n2 >= (int64_t)kTPB * 4 * kNumCU ? (int)((n2 + kTPB * 4 - 1) / (kTPB * 4)) : (int)((n2 + kTPB - 1) / kTPB);
+}
+
+// ------------------------------------------------------------------ between the passes (one block)
+// mode 0 (after pass 1): nrm2 = sum(part) in a fixed order, proj[0..j] = c[0..j], gate = force or |r|^2 < |w|^2 / 2 (c[j + 1] = w.w:
+// the DGKS criterion |r| < |w| / sqrt 2).  mode 1 (after the gated pass 2): returns when gate[0] == 0, else nrm2 = sum(part),
+// proj[0..j] += c[0..j].  mode 2: nrm2 = sum(part) only.
+__global__ __launch_bounds__(kTPB) void k_trl_post(int mode, const double* __restrict__ part, int np, const double* __restrict__ c, int j,
+                                                   double* __restrict__ nrm2, double* __restrict__ proj, int* __restrict__ gate, int force) {
+  if (mode == 1 && gate[0] == 0) return;
+  __shared__ double sm[kTPB / 64];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < np; b += kTPB) s += part[b];
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) {
+    nrm2[0] = s;
+    if (mode == 0) gate[0] = (force || s < 0.5 * c[j + 1]) ? 1 : 0;
+  }
+  if (mode == 2) return;
+  for (int i = threadIdx.x; i <= j; i += kTPB) proj[i] = mode == 0 ? c[i] : proj[i] + c[i];
+}
+
+void launch_trl_post(int mode, const double* part, int np, const double* c, int j, double* nrm2, double* proj, int* gate, int force,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(k_trl_post, dim3(1), dim3(kTPB), 0, s, mode, part, np, c, j, nrm2, proj, gate, force);
+}
+
+// ------------------------------------------------------------------ true residuals |A y_i - theta_i y_i|
+// CSR (the assembled stencil too: its CSR arrays stay beside the coded copy): one launch for all k vectors, blockIdx.y = i, a thread per
+// row forms (A y_i)_row - theta_i y_i[row] and the block adds the squares: part[i * G + b].
+__global__ __launch_bounds__(kTPB) void k_trl_resid_csr(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                        const double* __restrict__ vals, const double* __restrict__ Y, int64_t ldy, int64_t rows,
+                                                        const double* __restrict__ theta, double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const int i = blockIdx.y;
+  const double* x = Y + (int64_t)i * ldy;
+  const int64_t row = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+  double d = 0.0;
+  if (row < rows) {
+    double sum = 0.0;
+    for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) sum += vals[e] * x[colidx[e]];
+    const double t = sum - theta[i] * x[row];
+    d = t * t;
+  }
+  d = block_sum(d, sm);
+  if (threadIdx.x == 0) part[(int64_t)i * gridDim.x + blockIdx.x] = d;
+}
+int launch_trl_resid_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* theta, double* part, hipStream_t s) {
+  const int G = (int)((A.rows + kTPB - 1) / kTPB);
+  hipLaunchKernelGGL(k_trl_resid_csr, dim3(G, k), dim3(kTPB), 0, s, A.rowptr, A.colidx, A.vals, Y, ldy, A.rows, theta, part);
+  return G;
+}
+// dense: y = A y_i comes from the GEMV; this adds the squares of y - theta_i y_i (part[i * G + b])
+__global__ __launch_bounds__(kTPB) void k_trl_resid_diff(const double* __restrict__ y, const double* __restrict__ x, int64_t rows,
+                                                         const double* __restrict__ theta, int i, double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const int64_t row = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+  double d = 0.0;
+  if (row < rows) {
+    const double t = y[row] - theta[i] * x[row];
+    d = t * t;
+  }
+  d = block_sum(d, sm);
+  if (threadIdx.x == 0) part[(int64_t)i * gridDim.x + blockIdx.x] = d;
+}
+int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s) {
+  const int G = (int)((rows + kTPB - 1) / kTPB);
+  hipLaunchKernelGGL(k_trl_resid_diff, dim3(G), dim3(kTPB), 0, s, y, x, rows, theta, i, part);
+  return G;
+}
+// out[i] = sqrt(sum_b part[i * G + b]), one block per vector
+__global__ __launch_bounds__(kTPB) void k_trl_rownorm(const double* __restrict__ part, int G, double* __restrict__ out) {
+  __shared__ double sm[kTPB / 64];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < G; b += kTPB) s += part[(int64_t)blockIdx.x * G + b];
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) out[blockIdx.x] = sqrt(s);
+}
+void launch_trl_rownorm(const double* part, int G, int k, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_trl_rownorm, dim3(k), dim3(kTPB), 0, s, part, G, out);
+}
+
+}  // namespace lz

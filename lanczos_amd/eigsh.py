@@ -1,0 +1,284 @@
+"""``eigsh``: converged eigenpairs of a symmetric matrix by thick-restart Lanczos on the GPU.
+
+The Krylov basis (at most ``ncv + 1`` rows) and every pass over it live on the device (``lz_trl_*`` in
+include/lanczos_hip.h); the host keeps only the ``ncv x ncv`` projected matrix ``T`` and runs the outer loop below.
+
+Thick restart (Wu & Simon, 2000) is what ``scipy.sparse.linalg.eigsh`` does for a symmetric matrix in another form (ARPACK's
+implicit restart with exact shifts): after ``ncv`` steps the basis is compressed in place to the ``kk`` wanted Ritz vectors, the
+residual vector becomes row ``kk`` and the projected matrix becomes ``diag(theta)`` plus an arrow of couplings ``beta s``.
+
+Stopping rule.  A wanted pair is converged when ``beta |s_last| <= tol_eff * max|theta|`` (``tol_eff = tol``, or machine epsilon
+when ``tol == 0``).  ARPACK measures against ``tol * max(eps^(2/3), |theta|)`` instead; that bound never converges on Hamiltonians
+whose norm is many orders of magnitude above the wanted eigenvalues (the 1-D deuteron: ``||H|| = 2.7e5`` and eigenvalues of
+order 1), so the scale here is ``max|theta|``, the norm estimate of the run.
+
+Probe.  A single-vector Krylov method can miss a copy of a degenerate eigenvalue.  When all wanted pairs have converged, the loop
+locks them, adds one random direction orthogonal to the basis and asks for one more converged pair than before; it stops only
+when the lowest ``k`` wanted values are unchanged between two such rounds.
+
+Breakdown.  When a ``beta`` falls below ``10 eps max|theta|`` the Krylov space is invariant: the loop goes on from a fresh random
+vector orthogonal to the basis with a zero coupling instead of dividing by ``beta``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import scipy.sparse
+from scipy.sparse.linalg import ArpackNoConvergence
+
+_WHICH = ("LM", "SM", "LA", "SA", "BE")
+_EPS = np.finfo(np.float64).eps
+_MAX_NCV = 128  # rows of the restart's S held in LDS (lz_trl.hip)
+_SEED = 0x5EED  # the private generator of start and probe vectors: the same call gives the same bits
+
+
+def _order(theta, which):
+    """indices of theta, most wanted first"""
+    if which == "SA":
+        return np.argsort(theta, kind="stable")
+    if which == "LA":
+        return np.argsort(-theta, kind="stable")
+    if which == "SM":
+        return np.argsort(np.abs(theta), kind="stable")
+    return np.argsort(-np.abs(theta), kind="stable")
+
+
+class NumpyBackend:
+    """The six calls of the device backend (``lz_trl_*``) in NumPy: what the host tests drive the outer loop with."""
+
+    def __init__(self, A, force_second_pass=False):
+        self.A = A
+        self.n = A.shape[0]
+        self.force = force_second_pass
+
+    def begin(self, m, v0):
+        self.V = np.zeros((m + 1, self.n))
+        self.V[0] = v0 / np.linalg.norm(v0)
+
+    def _cgs(self, w, j):
+        c = self.V[: j + 1] @ w
+        return w - c @ self.V[: j + 1], c
+
+    def extend(self, k, m):
+        proj = np.zeros((m, m))
+        beta = np.zeros(m)
+        for j in range(k, m):
+            w = self.A @ self.V[j]
+            w0 = np.dot(w, w)
+            w, c = self._cgs(w, j)
+            if self.force or np.dot(w, w) < 0.5 * w0:  # DGKS: the second pass only when the first cancelled more than half of |w|
+                w, c2 = self._cgs(w, j)
+                c = c + c2
+            proj[j, : j + 1] = c
+            beta[j] = np.linalg.norm(w)
+            self.V[j + 1] = w / beta[j]
+        return proj, beta
+
+    def restart(self, m, kk, S):
+        self.V[:kk] = S.T @ self.V[:m]
+        self.V[kk] = self.V[m]
+
+    def probe(self, k, x):
+        for _ in range(2):
+            x = x - (self.V[:k] @ x) @ self.V[:k]
+        self.V[k] = x / np.linalg.norm(x)
+
+    def get_vectors(self, k):
+        return self.V[:k].T.copy()
+
+    def residuals(self, k, theta):
+        return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
+
+
+def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
+    """SciPy's argument errors, plus this solver's own limits.  Returns ncv."""
+    if M is not None or sigma is not None or Minv is not None or OPinv is not None:
+        raise NotImplementedError("eigsh on the device solves the standard problem only: M, sigma, Minv and OPinv must be None")
+    if mode != "normal":
+        raise NotImplementedError(f"mode={mode!r}: only mode='normal' is implemented")
+    if which not in _WHICH:
+        raise ValueError(f"which must be one of {' '.join(_WHICH)}")
+    if which == "BE":
+        raise NotImplementedError("which='BE' is not implemented")
+    if k <= 0:
+        raise ValueError("k must be greater than 0.")
+    if k >= n:
+        raise TypeError(f"k >= N for an N x N matrix (k={k}, N={n}): reduce k")
+    if ncv is None:
+        ncv = min(n, max(2 * k + 1, 20))
+    ncv = min(int(ncv), n)  # (as SciPy does)
+    if not k + 3 <= ncv <= min(n, _MAX_NCV):
+        raise ValueError(f"ncv must be k+3<=ncv<=min(n, {_MAX_NCV}), ncv={ncv} (stricter than SciPy's k<ncv<=n: the thick restart keeps "
+                         "two spare basis rows and one more for the probe direction)")
+    return ncv
+
+
+def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None):
+    """The thick-restart outer loop over a backend (``NumpyBackend`` or ``DeviceBackend``).
+
+    Returns ``(theta, info)``: the ``k`` wanted eigenvalues in ascending order (``backend.V[0..k)`` then holds their vectors) and
+    ``{"matvecs", "cycles", "probes", "breakdowns", "anorm"}`` (anorm: max|theta| over the run, the norm estimate).  Raises ``ArpackNoConvergence`` after ``maxiter`` cycles."""
+    m = check_args(n, k, which, ncv)
+    maxiter = n * 10 if maxiter is None else int(maxiter)
+    rng = np.random.default_rng(_SEED) if rng is None else rng
+    tol_eff = float(tol) if tol > 0 else _EPS
+    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
+    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
+        raise ValueError("v0 must be a non-zero vector of length n")
+    backend.begin(m, v0)
+    T = np.zeros((m, m))
+    kcur, nw, last = 0, k, None
+    anorm = 0.0
+    info = {"matvecs": 0, "cycles": 0, "probes": 0, "breakdowns": 0}
+    while True:
+        j0 = kcur
+        while True:  # one extension of the basis to m rows; a breakdown restarts it behind the invariant subspace
+            proj, beta = backend.extend(j0, m)
+            info["matvecs"] += m - j0
+            for j in range(j0, m):
+                T[: j + 1, j] = proj[j, : j + 1]
+                T[j, : j + 1] = proj[j, : j + 1]
+                if j + 1 < m:
+                    T[j + 1, j] = T[j, j + 1] = beta[j]
+            scale = max(anorm, np.abs(T).max())
+            bad = [j for j in range(j0, m - 1) if not beta[j] > 10 * _EPS * scale]
+            if not bad:
+                break
+            jb = bad[0]
+            info["breakdowns"] += 1
+            T[jb + 1:, :] = 0.0
+            T[:, jb + 1:] = 0.0
+            for j in range(j0, jb + 1):
+                T[: j + 1, j] = proj[j, : j + 1]
+                T[j, : j + 1] = proj[j, : j + 1]
+            backend.probe(jb + 1, rng.standard_normal(n))
+            j0 = jb + 1
+        info["cycles"] += 1
+        b_last = beta[m - 1]
+        theta, S = np.linalg.eigh((T + T.T) / 2)
+        anorm = max(np.abs(theta).max(), anorm)
+        res = b_last * np.abs(S[m - 1])
+        order = _order(theta, which)
+        want = order[:nw]
+        ok = res <= tol_eff * anorm
+        dead = not b_last > 10 * _EPS * anorm  # the last residual vanished: V[m] is noise, replace it after the restart
+        done = ok[want].all()
+        if done:
+            top = order[:k]
+            cur = np.sort(theta[top])
+            if not probe or (last is not None and np.abs(cur - last).max() <= 1e3 * tol_eff * anorm):
+                sel = top[np.argsort(theta[top], kind="stable")]
+                backend.restart(m, k, np.ascontiguousarray(S[:, sel]))
+                info["anorm"] = anorm
+                return theta[sel], info
+        if info["cycles"] >= maxiter:
+            conv = sorted((i for i in order[:k] if ok[i]), key=lambda i: theta[i])
+            vecs = np.zeros((n, 0))
+            if conv:
+                backend.restart(m, len(conv), np.ascontiguousarray(S[:, conv]))
+                vecs = backend.get_vectors(len(conv))
+            raise ArpackNoConvergence(f"No convergence ({info['cycles']} iterations, {len(conv)}/{k} eigenvectors converged)",
+                                      theta[conv], vecs)
+        if done:
+            last = cur
+            backend.restart(m, nw, np.ascontiguousarray(S[:, want]))
+            backend.probe(nw, rng.standard_normal(n))
+            info["probes"] += 1
+            T = np.zeros((m, m))
+            T[np.arange(nw), np.arange(nw)] = theta[want]
+            kcur, nw = nw, min(nw + 1, m - 3)
+        else:
+            nconv = int(ok[want].sum())
+            kk = min(m - 2, nw + max(nconv, (m - nw) // 2))
+            keep = order[:kk]
+            backend.restart(m, kk, np.ascontiguousarray(S[:, keep]))
+            T = np.zeros((m, m))
+            T[np.arange(kk), np.arange(kk)] = theta[keep]
+            if dead:
+                backend.probe(kk, rng.standard_normal(n))
+            else:
+                T[:kk, kk] = T[kk, :kk] = b_last * S[m - 1, keep]
+            kcur = kk
+
+
+class DeviceBackend:
+    """The six ``lz_trl_*`` calls on one ``_capi.Handle`` that already holds the matrix."""
+
+    def __init__(self, handle, n, force_second_pass=False):
+        self.h = handle
+        self.n = n
+        if force_second_pass:
+            from ._capi import FLAG_TRL_PASS2_ALWAYS
+
+            handle.set_options(FLAG_TRL_PASS2_ALWAYS)
+
+    def begin(self, m, v0):
+        self.h.trl_begin(m, v0)
+
+    def extend(self, k, m):
+        return self.h.trl_extend(k, m)
+
+    def restart(self, m, kk, S):
+        self.h.trl_restart(m, kk, S)
+
+    def probe(self, k, x):
+        self.h.trl_probe(k, x)
+
+    def get_vectors(self, k):
+        return self.h.trl_get_vectors(k)
+
+    def residuals(self, k, theta):
+        return self.h.trl_residuals(k, theta)
+
+
+def upload_matrix(h, A):
+    """A (SciPy sparse of any format, dense ndarray, ``synthetic.CSR`` or ``StencilOperator``) -> the handle; returns n."""
+    if hasattr(A, "dims") and hasattr(A, "points"):  # StencilOperator: assembled on the device, as LanczosBase._upload_matrix does
+        h.build_stencil3d_block(A.dims, A.points, A.T_factor, A.weights4, 0, A.shape[0], (), potential=A.potential,
+                                potential_params=A.potential_params, negate_T=A.negate_T)
+        return int(A.shape[0])
+    from ._solver import _pack_matrix
+
+    if scipy.sparse.issparse(A) and A.shape[0] != A.shape[1]:
+        raise ValueError(f"expected square matrix (shape={A.shape})")
+    packed = _pack_matrix(A)
+    if packed[0] == "csr":
+        n = len(packed[1]) - 1
+        h.set_csr(n, 0, packed[1], packed[2], packed[3])
+    else:
+        n = packed[1].shape[0]
+        h.set_dense(packed[1])
+    return int(n)
+
+
+def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=None, tol=0, return_eigenvectors=True, Minv=None,
+          OPinv=None, mode="normal", device_id=0, handle=None, info=None):
+    """Find ``k`` eigenvalues and eigenvectors of the real symmetric matrix ``A`` - ``scipy.sparse.linalg.eigsh``'s signature and
+    defaults, solved by thick-restart Lanczos on the GPU.
+
+    ``which``: ``"LM"``, ``"SM"``, ``"LA"`` or ``"SA"`` (``"BE"``, ``M``, ``sigma``, ``Minv``, ``OPinv`` and other modes raise
+    ``NotImplementedError``).  ``ncv`` (default ``min(n, max(2k + 1, 20))``) must satisfy ``k + 3 <= ncv <= min(n, 128)``.
+    ``A``: any SciPy sparse format, a dense ndarray, ``synthetic.CSR`` or ``StencilOperator`` (assembled on the device).
+    Eigenvalues come back in ascending order.  Start and probe vectors come from a private seeded generator (NumPy's global
+    RNG is never touched).  After ``maxiter`` restart cycles (default ``10 n``) ``ArpackNoConvergence`` carries the converged pairs.
+    Convergence: ``beta |s_last| <= tol * max|theta|`` (machine epsilon for ``tol = 0``), see the module docstring for why this
+    differs from ARPACK's ``tol * max(eps^(2/3), |theta|)``.
+    ``handle``: an open ``_capi.Handle`` to run on (its matrix is replaced); ``info``: a dict that receives the run's counts."""
+    from . import _capi
+
+    n = int(A.shape[0])
+    if len(A.shape) != 2 or A.shape[1] != n:
+        raise ValueError(f"expected square matrix (shape={A.shape})")
+    check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+    h = handle if handle is not None else _capi.Handle(device_id)
+    try:
+        upload_matrix(h, A)
+        theta, run = trl(DeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+        if info is not None:
+            info.update(run)
+            info["residuals"] = h.trl_residuals(k, theta)
+        if not return_eigenvectors:
+            return theta
+        return theta, h.trl_get_vectors(k)
+    finally:
+        if handle is None:
+            h.close()
