@@ -78,12 +78,15 @@ enum lz_flags {
                                  Same guard; a repeat runs the three-collective partial loop (engine 5).              */
   LZ_FLAG_TRL_PASS2_ALWAYS = 512, /* thick-restart Lanczos (lz_trl_extend): run the second Gram-Schmidt pass at every step instead of
                                      only where the DGKS criterion asks for it (tests) */
-  LZ_FLAG_REORTH_PARTIAL = 64 /* opt-in: partial re-orthogonalisation (Simon 1984).  The reference sweeps the whole basis
+  LZ_FLAG_REORTH_PARTIAL = 64, /* opt-in: partial re-orthogonalisation (Simon 1984).  The reference sweeps the whole basis
                                  every step; with this flag the sweep (same kernels, same arithmetic) runs only when the
                                  omega-recurrence estimate of the loss of orthogonality exceeds sqrt(eps), on that and the
                                  next step.  The recurrence and the decision live on the device (no host synchronisation
                                  inside lz_run: lz_last_host_syncs).  The basis stays semi-orthogonal (<= sqrt(eps)), which keeps T - and so the
                                  Ritz values - within O(eps ||A||) of the full-sweep run; V itself differs at that level. */
+  LZ_FLAG_TRL_FILTER_UNFUSED = 1024 /* thick-restart Lanczos with a Chebyshev filter (lz_trl_set_filter): form every filter step as the
+                                        plain SpMV plus the streaming recurrence kernel also where the SpMV has the fused epilogue
+                                        (fixed-K stencil matrices): same bits, 16 more bytes per row (A/B, tests) */
 };
 
 /* kernel classes reported by lz_get_timings */
@@ -424,6 +427,20 @@ int lz_trl_probe(lz_handle h, int k, const double* x);
 int lz_trl_get_vectors(lz_handle h, int k, double* Y_out);
 /* out[i] = |A V[i] - theta[i] V[i]| for i < k: one fused SpMV-and-norm launch (CSR, the assembled stencil included); dense: the GEMV */
 int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out);
+/* Chebyshev filter (lanczos_amd.eigsh(filter_degree=...); Zhou & Saad's filtered Lanczos): with degree > 0 every later lz_trl_extend
+ * forms w = p(A) V[j] instead of w = A V[j], p the polynomial of the scaled three-term recurrence
+ *   y_1 = a[0] (A x - c x),   y_i = a[i-1] (A y_{i-1} - c y_{i-1}) - b[i-1] y_{i-2}   (i = 2 .. degree, y_0 = x; b[0] is ignored as 0 x).
+ * a, b: degree doubles each, copied to the device (the kernels read them there); degree = 0 switches the filter off.  Needs lz_trl_begin
+ * first (LZ_ERR_STATE otherwise) and allocates two more work vectors of the padded row length, only when a filter is set; a later
+ * lz_trl_begin with the same m keeps the filter, a new matrix (lz_set_*, lz_build_*) or another m drops it.  All degree products and
+ * recurrence steps of all steps of an extension are enqueued without a host synchronisation. */
+int lz_trl_set_filter(lz_handle h, int degree, const double* a, const double* b, double c);
+/* y = p(A) x for host vectors of rows_local doubles (LZ_ERR_STATE without a filter): tests of the filter kernels.  The residual row
+ * V[m] is used as the staging row: it receives x (its padding is left as it is) and then the result with a zero padding. */
+int lz_trl_filter_apply(lz_handle h, const double* x, double* y);
+/* G_out (k x k row-major, 1 <= k < m) = V[0..k) A V[0..k)^T: per row one product with A itself (a filter is ignored) and one pass over
+ * the k rows.  The Rayleigh-Ritz step that turns the eigenvectors of p(A) into eigenpairs of A. */
+int lz_trl_rayleigh(lz_handle h, int k, double* G_out);
 /* raw basis rows j0 .. j0 + count - 1 (0 <= j0, j0 + count <= m + 1) including their padding (lz_padded_rows(rows) doubles each), host
  * rows ld >= that apart: tests of the restart kernel */
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);

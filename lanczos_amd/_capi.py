@@ -30,6 +30,7 @@ FLAG_REORTH_PARTIAL = 64
 FLAG_OVERLAP_HALO = 128
 FLAG_ONE_REDUCE = 256
 FLAG_TRL_PASS2_ALWAYS = 512  # thick-restart Lanczos: the second Gram-Schmidt pass at every extension step (default: where DGKS asks for it)
+FLAG_TRL_FILTER_UNFUSED = 1024  # thick-restart Lanczos: every Chebyshev filter step as SpMV + recurrence kernel, never the fused SpMV epilogue (A/B, tests)
 
 # lz_set_tuning knob indices (the legend lives in include/lanczos_hip.h)
 TUNE_QTW_SLICE = 0          # Q^T w slice length per block
@@ -164,6 +165,9 @@ SIGNATURES = {
     "lz_trl_probe": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_get_vectors": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_trl_set_filter": (C.c_int, [_P, C.c_int, _D, _D, C.c_double]),
+    "lz_trl_filter_apply": (C.c_int, [_P, _D, _D]),
+    "lz_trl_rayleigh": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_trl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
 }
@@ -795,6 +799,26 @@ class Handle:
         out = np.empty(int(k))
         self.check(self.lib.lz_trl_residuals(self._h, int(k), dptr(th), dptr(out)))
         return out
+
+    def trl_set_filter(self, coefficients, c=0.0):
+        """coefficients: the (a_i, b_i) pairs of ``ChebFilter.coefficients()``; None or empty switches the filter off"""
+        ab = np.zeros((0, 2)) if coefficients is None else f64(coefficients).reshape(-1, 2)
+        a, b = f64(ab[:, 0].copy()), f64(ab[:, 1].copy())
+        self.check(self.lib.lz_trl_set_filter(self._h, len(a), dptr(a) if len(a) else None, dptr(b) if len(b) else None, float(c)))
+
+    def trl_filter_apply(self, x):
+        """p(A) x through the device kernels; the residual row V[m] is overwritten"""
+        x = f64(x)
+        assert x.shape == (self.rows,)
+        y = np.empty(self.rows)
+        self.check(self.lib.lz_trl_filter_apply(self._h, dptr(x), dptr(y)))
+        return y
+
+    def trl_rayleigh(self, k):
+        """V[0..k) A V[0..k)^T, (k, k)"""
+        G = np.empty((int(k), int(k)))
+        self.check(self.lib.lz_trl_rayleigh(self._h, int(k), dptr(G)))
+        return G
 
     def trl_set_rows(self, j0, rows):
         """raw basis rows j0 .. j0 + len(rows) - 1 including their padding: rows is (count, >= padded_rows(M))"""

@@ -516,6 +516,8 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_tsm);
   big_free(h->d_tgate);
   big_free(h->d_tpart);
+  big_free(h->d_tf);
+  big_free(h->d_tcoef);
   if (h->h_pinned) hipHostFree(h->h_pinned);
   xfer_free(h->xfer);
   if (h->cstream) {

@@ -166,6 +166,13 @@ struct lz_context {
   int* d_tgate = nullptr;      // [0] gate of the second CGS pass
   double* d_tpart = nullptr;   // partials of the passes / SpMV / residual norms
   size_t tpart_cap = 0;
+  // Chebyshev filter of the thick-restart solver (lz_trl_set_filter): with trl_fdeg > 0 lz_trl_extend multiplies by p(A) instead of A
+  double* d_tf = nullptr;      // two more work vectors of trl_ld doubles each (allocated only when a filter is set); tf_ld = their length
+  int64_t tf_ld = 0;
+  double* d_tcoef = nullptr;   // a[0 .. degree), b[0 .. degree) of z = a_i (A y - c y) - b_i x; tcoef_cap doubles
+  int tcoef_cap = 0;
+  int trl_fdeg = 0;            // 0: no filter
+  double trl_fc = 0.0;         // c, the centre of the damped interval
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };

@@ -48,6 +48,11 @@ __device__ __forceinline__ double2 ld_stream(const double2* p) {
   }
   return *p;
 }
+// One entry of a Chebyshev filter step, z = a (w - c y) - b x (w = (A y)[r]): two fmas and one rounded product in this order, whoever
+// forms it - k_cheb_step (lz_trl.hip) on a stored w, or the ELL SpMV's epilogue (lz_spmv.hip) on the row sum in its registers.
+__device__ __forceinline__ double cheb_combine(double w, double y, double x, double a, double b, double c) {
+  return fma(a, fma(-c, y, w), -__dmul_rn(b, x));
+}
 // Non-temporal 16-byte store: results that are not re-read soon (the new basis row) should not sit dirty in L2 while the
 // other rows stream through it (tools/probes/hbm_read_peak.hip: a trailing plain store costs 17 % of the pass, an nt one 9 %).
 template <int VAR>

@@ -114,8 +114,19 @@ struct SpmvScale {
   double* beta_slot = nullptr;
   const int* gate = nullptr;
 };
+// The Chebyshev filter step as the SpMV's epilogue (thick-restart Lanczos, lz_trl_api.hip): the lane that owns row r forms
+// z[r] = a (sum - c x_own[r]) - b xprev[r] from its row sum (cheb_combine, lz_device.h: k_cheb_step's expression) and stores that instead
+// of y[r]; a = coef[i], b = coef[degree + i] are read on the device.  y is not written, no alpha partials are formed.  z must alias
+// neither x nor xprev.
+struct SpmvCheb {
+  const double* xprev = nullptr;
+  double* z = nullptr;
+  const double* coef = nullptr;
+  int i = 0, degree = 0;
+  double c = 0.0;
+};
 int launch_spmv_ell(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s,
-                    const SpmvScale* sc = nullptr);
+                    const SpmvScale* sc = nullptr, const SpmvCheb* ch = nullptr);
 struct StencilArgs {  // by-value kernel argument of the stencil assembly
   int Nx, Ny, Nz, negate, pot_kind, renumber, nranges;
   int64_t row0, rows_local;
@@ -309,6 +320,10 @@ void launch_trl_post(int mode, const double* part, int np, const double* c, int 
 int launch_trl_resid_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* theta, double* part, hipStream_t s);
 int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s);
 void launch_trl_rownorm(const double* part, int G, int k, double* out, hipStream_t s);
+// one step of the scaled Chebyshev recurrence, in place on wz (which holds w = A y): wz[r] = a (w[r] - c y[r]) - b x[r] for r < rows and
+// 0 for rows <= r < len; a = coef[i], b = coef[degree + i] are read on the device.  x may alias y (degree 1: b = 0).
+void launch_cheb_step(double* wz, const double* y, const double* x, const double* coef, int i, int degree, double c, int64_t rows,
+                      int64_t len, hipStream_t s);
 
 // ---- small-problem engine (lz_small.hip): the whole run as one cooperative kernel
 struct SmallArgs {

@@ -228,11 +228,13 @@ __device__ __forceinline__ T ld_nt(const T* p) {
 //   sit in LDS) instead of 4 bytes per entry, the values stream as before.  Where the values repeat with the offsets (constant
 //   coefficients) the whole matrix is that byte per row: k_spmv_cls below.  Products, their order and the alpha partials are exactly
 //   those of the uncoded kernel: same bits.
-template <int K, int RPT, int VEC, bool SC, int CODED>
+//   CH (the thick-restart solver's Chebyshev filter, SpmvCheb): the row sum goes through cheb_combine with the lane's own x and the
+//   previous vector of the recurrence and is stored to ch.z; y and the alpha partials are not formed.
+template <int K, int RPT, int VEC, bool SC, int CODED, bool CH = false>
 __global__ __launch_bounds__(kTPB) void k_spmv_ell(const int32_t* __restrict__ ec, const double* __restrict__ ev,
                                                   const double* __restrict__ x, const double* __restrict__ xown,
                                                   double* __restrict__ y, int rows, int rows_pad, double* __restrict__ part,
-                                                  SpmvScale sc, EllCode code) {
+                                                  SpmvScale sc, EllCode code, SpmvCheb ch) {
   constexpr int RB = kTPB * RPT * VEC;
   constexpr int NR = RPT * VEC;  // rows per lane
   __shared__ double sm[kTPB / 64];
@@ -314,6 +316,14 @@ __global__ __launch_bounds__(kTPB) void k_spmv_ell(const int32_t* __restrict__ e
   double own[NR];
 #pragma unroll
   for (int q = 0; q < NR; ++q) own[q] = lrow[q] < rows_pad ? xo[lrow[q]] : 0.0;
+  double prv[CH ? NR : 1];
+  double cha = 0.0, chb = 0.0;
+  if constexpr (CH) {
+    cha = ch.coef[ch.i];
+    chb = ch.coef[ch.degree + ch.i];
+#pragma unroll
+    for (int q = 0; q < NR; ++q) prv[q] = lrow[q] < rows ? ch.xprev[lrow[q]] : 0.0;
+  }
   if constexpr (SC) {
     if (scale) {
 #pragma unroll
@@ -332,10 +342,15 @@ __global__ __launch_bounds__(kTPB) void k_spmv_ell(const int32_t* __restrict__ e
 #pragma unroll
     for (int k = 0; k < K; ++k) sum += a[q][k] * xv[q][k];
     if (lrow[q] < rows) {
-      y[lrow[q]] = sum;
-      d += own[q] * sum;
+      if constexpr (CH) {
+        ch.z[lrow[q]] = cheb_combine(sum, own[q], prv[q], cha, chb, ch.c);
+      } else {
+        y[lrow[q]] = sum;
+        d += own[q] * sum;
+      }
     }
   }
+  if constexpr (CH) return;
   d = block_sum(d, sm);
   if (threadIdx.x == 0) part[blk] = d;
 }
@@ -345,9 +360,9 @@ __global__ __launch_bounds__(kTPB) void k_spmv_ell(const int32_t* __restrict__ e
 // order), so the bits do not depend on G - and a lane keeps G RPT rows in flight: the values are read from LDS only when the gathers
 // have landed, which leaves registers for twice the rows of the uncoded kernel (the kernel is bound by two dependent memory round
 // trips - class byte, then x - not by bytes: 17 per row).
-template <int K, int RPT, int G, bool SC, bool DIAG>
+template <int K, int RPT, int G, bool SC, bool DIAG, bool CH = false>
 __global__ __launch_bounds__(kTPB) void k_spmv_cls(EllCode code, const double* __restrict__ x, const double* __restrict__ xown, double* __restrict__ y,
-                                                  int rows, int rows_pad, int nunits, double* __restrict__ part, SpmvScale sc) {
+                                                  int rows, int rows_pad, int nunits, double* __restrict__ part, SpmvScale sc, SpmvCheb ch) {
   constexpr int RBU = kTPB * RPT;
   constexpr int NR = RPT * G;
   __shared__ double sm[G][kTPB / 64];
@@ -382,6 +397,14 @@ __global__ __launch_bounds__(kTPB) void k_spmv_cls(EllCode code, const double* _
   double own[NR];
 #pragma unroll
   for (int i = 0; i < NR; ++i) own[i] = lrow[i] < rows_pad ? xo[lrow[i]] : 0.0;  // (does not wait for the class)
+  double prv[CH ? NR : 1];
+  double cha = 0.0, chb = 0.0;
+  if constexpr (CH) {
+    cha = ch.coef[ch.i];
+    chb = ch.coef[ch.degree + ch.i];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) prv[i] = lrow[i] < rows ? ch.xprev[lrow[i]] : 0.0;
+  }
   const int nt = code.ncls * K;
   int* s_off = reinterpret_cast<int*>(s_tab + nt);
   for (int i = threadIdx.x; i < nt; i += kTPB) {
@@ -420,13 +443,20 @@ __global__ __launch_bounds__(kTPB) void k_spmv_cls(EllCode code, const double* _
           if constexpr (DIAG) a = s_off[cl[i] * K + k] == 0 ? dg[i] : a;
           sum += a * xv[i][k];
         }
-        y[lrow[i]] = sum;
-        d += own[i] * sum;
+        if constexpr (CH) {
+          ch.z[lrow[i]] = cheb_combine(sum, own[i], prv[i], cha, chb, ch.c);
+        } else {
+          y[lrow[i]] = sum;
+          d += own[i] * sum;
+        }
       }
     }
-    d = wave_sum(d);
-    if (lane == 0) sm[g][w] = d;
+    if constexpr (!CH) {
+      d = wave_sum(d);
+      if (lane == 0) sm[g][w] = d;
+    }
   }
+  if constexpr (CH) return;
   __syncthreads();
   if (threadIdx.x < G) {
     const int unit = blk * G + (int)threadIdx.x;
@@ -445,9 +475,9 @@ __global__ __launch_bounds__(kTPB) void k_spmv_cls(EllCode code, const double* _
 // the two class bytes one 2-byte load: four instructions per row.  Lanes whose two rows differ in class (a grid line's end) take two
 // 8-byte gathers.  The alpha partial must still be the one k_spmv_ell forms (lane L: rows L and L + 256 of the unit, in order): the
 // products own * sum go through LDS to that lane mapping, then the same wave sums.  Same bits.
-template <int K, bool SC, bool DIAG>
+template <int K, bool SC, bool DIAG, bool CH = false>
 __global__ __launch_bounds__(kTPB) void k_spmv_cls2(EllCode code, const double* __restrict__ x, const double* __restrict__ xown, double* __restrict__ y,
-                                                   int rows, int rows_pad, double* __restrict__ part, SpmvScale sc) {
+                                                   int rows, int rows_pad, double* __restrict__ part, SpmvScale sc, SpmvCheb ch) {
   constexpr int RBU = 2 * kTPB;  // one alpha partial unit per workgroup
   __shared__ double sm[kTPB / 64];
   __shared__ __attribute__((aligned(16))) double sp[RBU];
@@ -477,6 +507,13 @@ __global__ __launch_bounds__(kTPB) void k_spmv_cls2(EllCode code, const double* 
   }
   double2 own = make_double2(0.0, 0.0);
   if (ra + 1 < rows_pad) own = *reinterpret_cast<const double2*>(xo + ra);  // (rows_pad is even: both or neither)
+  double2 prv = make_double2(0.0, 0.0);
+  double cha = 0.0, chb = 0.0;
+  if constexpr (CH) {
+    cha = ch.coef[ch.i];
+    chb = ch.coef[ch.degree + ch.i];
+    if (ra + 1 < rows_pad) prv = *reinterpret_cast<const double2*>(ch.xprev + ra);
+  }
   const int nt = code.ncls * K;
   int* s_off = reinterpret_cast<int*>(s_tab + nt);
   for (int i = threadIdx.x; i < nt; i += kTPB) {
@@ -523,6 +560,14 @@ __global__ __launch_bounds__(kTPB) void k_spmv_cls2(EllCode code, const double* 
     double a = s_tab[cb * K + k];
     if constexpr (DIAG) a = s_off[cb * K + k] == 0 ? dg.y : a;
     sumb += a * xb[k];
+  }
+  if constexpr (CH) {
+    const double za = cheb_combine(suma, own.x, prv.x, cha, chb, ch.c), zb = cheb_combine(sumb, own.y, prv.y, cha, chb, ch.c);
+    if (live_b)
+      *reinterpret_cast<double2*>(ch.z + ra) = make_double2(za, zb);
+    else if (live_a)
+      ch.z[ra] = za;
+    return;
   }
   if (live_b)
     *reinterpret_cast<double2*>(y + ra) = make_double2(suma, sumb);
@@ -835,7 +880,8 @@ bool ell_usable(const CsrDev& A, int flags) {
 }
 
 template <int K, int RPT, int VEC, int CODED>
-static int launch_spmv_ell_c(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc) {
+static int launch_spmv_ell_c(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc,
+                             const SpmvCheb* ch) {
   constexpr int RB = kTPB * RPT * VEC;
   const int grid = (int)((A.rows + RB - 1) / RB);
   const int rows_pad = (int)round_up(A.rows, kPadDoubles);
@@ -847,14 +893,18 @@ static int launch_spmv_ell_c(const CsrDev& A, const double* x, double* y, const 
   const size_t lds = CODED == 0 ? 0 : (size_t)A.ell_ncls * K * 4 + 8;
   if (sc)
     hipLaunchKernelGGL((k_spmv_ell<K, RPT, VEC, true, CODED>), dim3(grid), dim3(kTPB), lds, s, A.ell_c, A.ell_v, x, x_own, y, (int)A.rows, rows_pad, part, *sc,
-                       code);
+                       code, SpmvCheb());
+  else if (ch)
+    hipLaunchKernelGGL((k_spmv_ell<K, RPT, VEC, false, CODED, true>), dim3(grid), dim3(kTPB), lds, s, A.ell_c, A.ell_v, x, x_own, y, (int)A.rows, rows_pad,
+                       part, SpmvScale(), code, *ch);
   else
     hipLaunchKernelGGL((k_spmv_ell<K, RPT, VEC, false, CODED>), dim3(grid), dim3(kTPB), lds, s, A.ell_c, A.ell_v, x, x_own, y, (int)A.rows, rows_pad, part,
-                       SpmvScale(), code);
+                       SpmvScale(), code, SpmvCheb());
   return grid;
 }
 template <int K, int RPT, int G>
-static int launch_spmv_cls(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc) {
+static int launch_spmv_cls(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc,
+                           const SpmvCheb* ch) {
   constexpr int RBU = kTPB * RPT;
   const int nunits = (int)((A.rows + RBU - 1) / RBU);  // one alpha partial per unit: the ELL copy's blocks
   const int grid = (nunits + G - 1) / G;
@@ -867,20 +917,26 @@ static int launch_spmv_cls(const CsrDev& A, const double* x, double* y, const do
   const size_t lds = (size_t)A.ell_ncls * K * 12 + 8;
   code.diag = A.cls_diag;
   const SpmvScale none;
+  const SpmvCheb noch;
   if (A.ell_coded == 3) {
     if (sc)
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc);
+      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc, noch);
+    else if (ch)
+      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
     else
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none);
+      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, noch);
   } else if (sc) {
-    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc);
+    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc, noch);
+  } else if (ch) {
+    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
   } else {
-    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none);
+    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, noch);
   }
   return nunits;
 }
 template <int K>
-static int launch_spmv_cls2(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc) {
+static int launch_spmv_cls2(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc,
+                            const SpmvCheb* ch) {
   const int nunits = (int)((A.rows + 2 * kTPB - 1) / (2 * kTPB));
   const int rows_pad = (int)round_up(A.rows, kPadDoubles);
   EllCode code;
@@ -891,48 +947,55 @@ static int launch_spmv_cls2(const CsrDev& A, const double* x, double* y, const d
   const size_t lds = (size_t)A.ell_ncls * K * 12 + 8;
   code.diag = A.cls_diag;
   const SpmvScale none;
+  const SpmvCheb noch;
   if (A.ell_coded == 3) {
     if (sc)
-      hipLaunchKernelGGL((k_spmv_cls2<K, true, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, *sc);
+      hipLaunchKernelGGL((k_spmv_cls2<K, true, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, *sc, noch);
+    else if (ch)
+      hipLaunchKernelGGL((k_spmv_cls2<K, false, true, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none, *ch);
     else
-      hipLaunchKernelGGL((k_spmv_cls2<K, false, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none);
+      hipLaunchKernelGGL((k_spmv_cls2<K, false, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none, noch);
   } else if (sc) {
-    hipLaunchKernelGGL((k_spmv_cls2<K, true, false>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, *sc);
+    hipLaunchKernelGGL((k_spmv_cls2<K, true, false>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, *sc, noch);
+  } else if (ch) {
+    hipLaunchKernelGGL((k_spmv_cls2<K, false, false, true>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none, *ch);
   } else {
-    hipLaunchKernelGGL((k_spmv_cls2<K, false, false>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none);
+    hipLaunchKernelGGL((k_spmv_cls2<K, false, false>), dim3(nunits), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, part, none, noch);
   }
   return nunits;
 }
 template <int K, int RPT, int VEC>
-static int launch_spmv_ell_t(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc) {
-  if (A.ell_coded == 1) return launch_spmv_ell_c<K, RPT, VEC, 1>(A, x, y, x_own, part, s, sc);
-  return launch_spmv_ell_c<K, RPT, VEC, 0>(A, x, y, x_own, part, s, sc);
+static int launch_spmv_ell_t(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc,
+                             const SpmvCheb* ch) {
+  if (A.ell_coded == 1) return launch_spmv_ell_c<K, RPT, VEC, 1>(A, x, y, x_own, part, s, sc, ch);
+  return launch_spmv_ell_c<K, RPT, VEC, 0>(A, x, y, x_own, part, s, sc, ch);
 }
 
-int launch_spmv_ell(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc) {
+int launch_spmv_ell(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, hipStream_t s, const SpmvScale* sc,
+                    const SpmvCheb* ch) {
   if (A.ell_coded == 2 || A.ell_coded == 3) {  // (always built with one row per lane and trip: ell_variant 0)
     // Which form runs (tools/spmv_coding_probe.py, partial_step_probe.py): 27 entries per row - one row per lane; 5 entries - two adjacent
     // rows per lane, also with the fused r / beta; 7 entries - two adjacent rows per lane for the plain SpMV, one row per lane for the
     // fused form.  Knob 23 = 1 / 3: the one-row-per-lane kernel with one / two 512-row units per workgroup (A/B: two units measured equal
     // in 2-D, 185 vs 191 us on a 300^3 grid, and 7 % slower for the fused form - 112 registers - which therefore always takes one).
     const int G = (!sc && A.cls_group == 3) ? 2 : 1;
-    if (A.fixed_k == 27) return launch_spmv_cls<27, 1, 1>(A, x, y, x_own, part, s, sc);
+    if (A.fixed_k == 27) return launch_spmv_cls<27, 1, 1>(A, x, y, x_own, part, s, sc, ch);
     if (A.cls_group != 1 && A.cls_group != 3) {  // (knob 23: 1 / 3 = the one-row-per-lane forms, A/B)
       // two adjacent rows per lane: headline 43.5 -> 35.1 us, C2 9.7 -> 8.7, 300^3 7-point 187 -> 178, 464^3 674 -> 624; the fused r / beta
       // form 54.5 -> 51.0 us (5-point) but 235 -> 254 (7-point: 82 registers, five waves) - that one keeps one row per lane
-      if (A.fixed_k == 5) return launch_spmv_cls2<5>(A, x, y, x_own, part, s, sc);
-      if (!sc) return launch_spmv_cls2<7>(A, x, y, x_own, part, s, sc);
+      if (A.fixed_k == 5) return launch_spmv_cls2<5>(A, x, y, x_own, part, s, sc, ch);
+      if (!sc) return launch_spmv_cls2<7>(A, x, y, x_own, part, s, sc, ch);
     }
-    if (A.fixed_k == 5) return G == 1 ? launch_spmv_cls<5, 2, 1>(A, x, y, x_own, part, s, sc) : launch_spmv_cls<5, 2, 2>(A, x, y, x_own, part, s, sc);
-    return G == 1 ? launch_spmv_cls<7, 2, 1>(A, x, y, x_own, part, s, sc) : launch_spmv_cls<7, 2, 2>(A, x, y, x_own, part, s, sc);
+    if (A.fixed_k == 5) return G == 1 ? launch_spmv_cls<5, 2, 1>(A, x, y, x_own, part, s, sc, ch) : launch_spmv_cls<5, 2, 2>(A, x, y, x_own, part, s, sc, ch);
+    return G == 1 ? launch_spmv_cls<7, 2, 1>(A, x, y, x_own, part, s, sc, ch) : launch_spmv_cls<7, 2, 2>(A, x, y, x_own, part, s, sc, ch);
   }
-  if (A.fixed_k == 27) return launch_spmv_ell_t<27, 1, 1>(A, x, y, x_own, part, s, sc);
+  if (A.fixed_k == 27) return launch_spmv_ell_t<27, 1, 1>(A, x, y, x_own, part, s, sc, ch);
   if (A.ell_variant == 1) {
-    if (A.fixed_k == 5) return launch_spmv_ell_t<5, 1, 2>(A, x, y, x_own, part, s, sc);
-    return launch_spmv_ell_t<7, 1, 2>(A, x, y, x_own, part, s, sc);
+    if (A.fixed_k == 5) return launch_spmv_ell_t<5, 1, 2>(A, x, y, x_own, part, s, sc, ch);
+    return launch_spmv_ell_t<7, 1, 2>(A, x, y, x_own, part, s, sc, ch);
   }
-  if (A.fixed_k == 5) return launch_spmv_ell_t<5, 2, 1>(A, x, y, x_own, part, s, sc);
-  return launch_spmv_ell_t<7, 2, 1>(A, x, y, x_own, part, s, sc);
+  if (A.fixed_k == 5) return launch_spmv_ell_t<5, 2, 1>(A, x, y, x_own, part, s, sc, ch);
+  return launch_spmv_ell_t<7, 2, 1>(A, x, y, x_own, part, s, sc, ch);
 }
 
 int launch_spmv_csr(const CsrDev& A, const double* x, double* y, const double* x_own, double* part, int flags,

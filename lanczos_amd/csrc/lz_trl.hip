@@ -195,6 +195,37 @@ void launch_trl_post(int mode, const double* part, int np, const double* c, int 
   hipLaunchKernelGGL(k_trl_post, dim3(1), dim3(kTPB), 0, s, mode, part, np, c, j, nrm2, proj, gate, force);
 }
 
+// ------------------------------------------------------------------ Chebyshev filter: one step of the scaled three-term recurrence
+// z = a (w - c y) - b x with w = A y already in place (the SpMV / GEMV wrote it): three 16-byte reads and one 16-byte write per two
+// rows, 32 B per row, a pure stream - no LDS, no atomics, grid sized as k_three_term's.  The arithmetic is cheb_combine (lz_device.h), shared with
+// the SpMV's fused epilogue (SpmvCheb, lz_spmv.hip): same bits on either path.
+// Rows >= rows (the padding the sweep kernels stream) are written as zero whatever the inputs hold there.
+__global__ __launch_bounds__(kTPB) void k_cheb_step(double* __restrict__ wz, const double* y, const double* x, const double* __restrict__ coef,
+                                                   int i, int degree, double c, int64_t rows, int64_t n2) {
+  const double a = coef[i];
+  const double b = coef[degree + i];
+  double2* z2 = reinterpret_cast<double2*>(wz);
+  const double2* y2 = reinterpret_cast<const double2*>(y);
+  const double2* x2 = reinterpret_cast<const double2*>(x);
+  for (int64_t p = (int64_t)blockIdx.x * kTPB + threadIdx.x; p < n2; p += (int64_t)gridDim.x * kTPB) {
+    const double2 w = z2[p];
+    const double2 yv = y2[p];  // plain loads: y is the next step's x, and x of the first step is the basis row the first pass re-reads
+    const double2 xv = x2[p];
+    double2 z;
+    z.x = 2 * p < rows ? cheb_combine(w.x, yv.x, xv.x, a, b, c) : 0.0;
+    z.y = 2 * p + 1 < rows ? cheb_combine(w.y, yv.y, xv.y, a, b, c) : 0.0;
+    z2[p] = z;  // plain store: the next SpMV (or the first Gram-Schmidt pass) reads it at once
+  }
+}
+void launch_cheb_step(double* wz, const double* y, const double* x, const double* coef, int i, int degree, double c, int64_t rows,
+                      int64_t len, hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  int64_t g = (n2 + kTPB - 1) / kTPB;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL(k_cheb_step, dim3((int)g), dim3(kTPB), 0, s, wz, y, x, coef, i, degree, c, rows, n2);
+}
+
 // ------------------------------------------------------------------ true residuals |A y_i - theta_i y_i|
 // CSR (the assembled stencil too: its CSR arrays stay beside the coded copy): one launch for all k vectors, blockIdx.y = i, a thread per
 // row forms (A y_i)_row - theta_i y_i[row] and the block adds the squares: part[i * G + b].

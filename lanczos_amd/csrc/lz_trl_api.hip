@@ -62,6 +62,47 @@ int trl_upload_x(lz_handle h, const double* x) {
   return LZ_OK;
 }
 
+// d_tw = A x or, with a filter set, p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never written).  The
+// filter runs the scaled Chebyshev recurrence through three rotating work vectors (d_tw and the two of d_tf) so that the last step
+// lands in d_tw; every product is the plain SpMV / GEMV launch, every recurrence step one k_cheb_step in place on that product.
+void trl_matvec(lz_handle h, const double* x, double* y) {
+  if (h->kind == 1)
+    launch_spmv_csr(h->csr, x, y, x, h->d_tpart, h->flags, h->stream);
+  else
+    launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, y, h->d_tpart, h->stream);
+}
+void trl_apply_op(lz_handle h, const double* x) {
+  const int d = h->trl_fdeg;
+  if (d == 0) {
+    trl_matvec(h, x, h->d_tw);
+    return;
+  }
+  // fixed-K stencil matrices whose SpMV is the ELL kernel: the step is that kernel's epilogue (24 B per row beside the matrix instead
+  // of 8 + 32), same bits; LZ_FLAG_TRL_FILTER_UNFUSED keeps the two launches
+  const bool fused = h->kind == 1 && h->csr.ell_default && ell_usable(h->csr, h->flags) && !(h->flags & LZ_FLAG_TRL_FILTER_UNFUSED);
+  double* bufs[3] = {h->d_tw, h->d_tf, h->d_tf + h->tf_ld};
+  const double* prev = x;  // x of the recurrence (degree 1: unused, b = 0)
+  const double* cur = x;   // y of the recurrence
+  for (int i = 1; i <= d; ++i) {
+    double* z = bufs[(i - d) % 3 == 0 ? 0 : 3 + (i - d) % 3];  // step d -> d_tw
+    if (fused) {
+      SpmvCheb ch;
+      ch.xprev = prev;
+      ch.z = z;
+      ch.coef = h->d_tcoef;
+      ch.i = i - 1;
+      ch.degree = d;
+      ch.c = h->trl_fc;
+      launch_spmv_ell(h->csr, cur, z, cur, h->d_tpart, h->stream, nullptr, &ch);
+    } else {
+      trl_matvec(h, cur, z);
+      launch_cheb_step(z, cur, prev, h->d_tcoef, i - 1, d, h->trl_fc, h->rows, h->rows_pad, h->stream);
+    }
+    prev = cur;
+    cur = z;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -78,6 +119,7 @@ int lz_trl_begin(lz_handle h, int m, const double* v0) {
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   const int64_t ld = skew_stride(h, h->rows_pad);
   if (!h->d_trl || h->trl_m != m || h->trl_ld != ld) {
+    h->trl_fdeg = 0;  // the filter's work vectors belong to the old row length
     LZ_TRY(dev_alloc(h, h->d_trl, (size_t)(m + 1) * (size_t)ld));
     LZ_TRY(dev_alloc(h, h->d_tw, (size_t)ld));
     LZ_TRY(dev_alloc(h, h->d_tsm, (size_t)trl_small_layout(m).total));
@@ -116,11 +158,7 @@ int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out)
   QtwFuse gated;
   gated.gate = h->d_tgate;
   for (int j = k; j < m; ++j) {
-    const double* x = V + (int64_t)j * ld;
-    if (h->kind == 1)
-      launch_spmv_csr(h->csr, x, h->d_tw, x, h->d_tpart, h->flags, h->stream);
-    else
-      launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, h->d_tw, h->d_tpart, h->stream);
+    trl_apply_op(h, V + (int64_t)j * ld);  // w = A V[j], or p(A) V[j] with a filter set
     // pass 1: c = V[0..j] . w (row j + 1 is the self slot: c[j + 1] = w.w), w -= sum c_i V_i
     LZ_HIP(h, launch_qtw(V, ld, h->rows_pad, j + 2, j + 1, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
     launch_final_rows(h->d_tpart, j + 2, plan.P, sm + L.c1, h->stream, plan.family == 2);
@@ -193,6 +231,62 @@ int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
   launch_trl_rownorm(h->d_tpart, G, k, h->d_tsm + L.res, h->stream);
   LZ_TRY(check_launch(h, "trl residuals"));
   LZ_HIP(h, hipMemcpyAsync(out, h->d_tsm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
+}
+
+int lz_trl_set_filter(lz_handle h, int degree, const double* a, const double* b, double c) {
+  LZ_TRY(trl_state(h, "lz_trl_set_filter"));
+  if (degree < 0 || degree > 4096 || (degree > 0 && (!a || !b))) return fail(h, LZ_ERR_ARG, "lz_trl_set_filter: need 0 <= degree <= 4096, a and b");
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  h->trl_fdeg = 0;
+  if (degree == 0) return LZ_OK;
+  if (!h->d_tf || h->tf_ld != h->trl_ld) {
+    LZ_TRY(dev_alloc(h, h->d_tf, 2 * (size_t)h->trl_ld));
+    h->tf_ld = h->trl_ld;
+  }
+  if (h->tcoef_cap < 2 * degree) {
+    LZ_TRY(dev_alloc(h, h->d_tcoef, 2 * (size_t)degree));
+    h->tcoef_cap = 2 * degree;
+  }
+  LZ_HIP(h, hipMemsetAsync(h->d_tf, 0, 2 * (size_t)h->trl_ld * sizeof(double), h->stream));
+  LZ_TRY(upload(h, h->d_tcoef, a, (size_t)degree * sizeof(double)));
+  LZ_TRY(upload(h, h->d_tcoef + degree, b, (size_t)degree * sizeof(double)));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  h->trl_fdeg = degree;
+  h->trl_fc = c;
+  return LZ_OK;
+}
+
+int lz_trl_filter_apply(lz_handle h, const double* x, double* y) {
+  LZ_TRY(trl_state(h, "lz_trl_filter_apply"));
+  if (!x || !y) return fail(h, LZ_ERR_ARG, "lz_trl_filter_apply: need x and y");
+  if (h->trl_fdeg == 0) return fail(h, LZ_ERR_STATE, "lz_trl_filter_apply: no filter set (lz_trl_set_filter first)");
+  double* vm = h->d_trl + (int64_t)h->trl_m * h->trl_ld;  // the residual row carries x and then the result
+  LZ_TRY(upload(h, vm, x, (size_t)h->rows * sizeof(double)));
+  trl_apply_op(h, vm);
+  LZ_TRY(check_launch(h, "trl filter apply"));
+  LZ_HIP(h, hipMemcpyAsync(vm, h->d_tw, (size_t)h->rows_pad * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(y, h->d_tw, (size_t)h->rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
+}
+
+int lz_trl_rayleigh(lz_handle h, int k, double* G_out) {
+  LZ_TRY(trl_state(h, "lz_trl_rayleigh"));
+  if (!G_out || k < 1 || k >= h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_rayleigh: need 1 <= k < m and G_out");
+  const TrlSmall L = trl_small_layout(h->trl_m);
+  double* V = h->d_trl;
+  double* G = h->d_tsm + L.S;  // k x k in the restart's S area
+  const QtwPlan plan = trl_plan(h);
+  for (int i = 0; i < k; ++i) {
+    trl_matvec(h, V + (int64_t)i * h->trl_ld, h->d_tw);  // A itself, filter or not
+    LZ_HIP(h, launch_qtw(V, h->trl_ld, h->rows_pad, k + 1, k, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
+    launch_final_rows(h->d_tpart, k + 1, plan.P, h->d_tsm + L.c1, h->stream, plan.family == 2);
+    LZ_HIP(h, hipMemcpyAsync(G + (int64_t)i * k, h->d_tsm + L.c1, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    LZ_TRY(check_launch(h, "trl rayleigh"));
+  }
+  LZ_HIP(h, hipMemcpyAsync(G_out, G, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   return LZ_OK;
 }

@@ -43,12 +43,30 @@ def _order(theta, which):
 
 
 class NumpyBackend:
-    """The six calls of the device backend (``lz_trl_*``) in NumPy: what the host tests drive the outer loop with."""
+    """The calls of the device backend (``lz_trl_*``) in NumPy: what the host tests drive the outer loop with."""
 
     def __init__(self, A, force_second_pass=False):
         self.A = A
         self.n = A.shape[0]
         self.force = force_second_pass
+        self.filter = None
+
+    def set_filter(self, coefficients, c=0.0):
+        """``coefficients``: the (a_i, b_i) of ``ChebFilter.coefficients()``; None: ``extend`` multiplies by A itself again"""
+        self.filter = None if coefficients is None else (np.asarray(coefficients, dtype=np.float64).reshape(-1, 2), float(c))
+
+    def _op(self, x):
+        if self.filter is None:
+            return self.A @ x
+        coef, c = self.filter
+        prev, cur = x, x
+        for a, b in coef:  # z = a (A y - c y) - b x, as k_cheb_step forms it
+            prev, cur = cur, a * (self.A @ cur - c * cur) - b * prev
+        return cur
+
+    def rayleigh(self, k):
+        Y = self.V[:k]
+        return Y @ np.stack([self.A @ Y[i] for i in range(k)]).T
 
     def begin(self, m, v0):
         self.V = np.zeros((m + 1, self.n))
@@ -62,7 +80,7 @@ class NumpyBackend:
         proj = np.zeros((m, m))
         beta = np.zeros(m)
         for j in range(k, m):
-            w = self.A @ self.V[j]
+            w = self._op(self.V[j])
             w0 = np.dot(w, w)
             w, c = self._cgs(w, j)
             if self.force or np.dot(w, w) < 0.5 * w0:  # DGKS: the second pass only when the first cancelled more than half of |w|
@@ -200,8 +218,172 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             kcur = kk
 
 
+class ChebFilter:
+    """The scaled Chebyshev polynomial ``p`` of degree ``degree`` that damps ``[lo, hi]`` and has ``p(anchor) = 1``:
+    ``p(t) = T_d((t - c) / e) / T_d((anchor - c) / e)`` with ``c = (lo + hi) / 2``, ``e = (hi - lo) / 2``.  ``anchor`` lies outside the
+    interval, on the side of the wanted eigenvalues; between the anchor and the far end of the interval ``|p| <= 1``, and ``p`` grows
+    monotonically from the near edge to the anchor.  ``ChebFilter(..., A=A) @ x`` is ``p(A) x``, so ``NumpyBackend`` takes it as a matrix."""
+
+    def __init__(self, lo, hi, anchor, degree, A=None):
+        self.lo, self.hi, self.anchor, self.degree = float(lo), float(hi), float(anchor), int(degree)
+        if not self.lo < self.hi or self.lo <= self.anchor <= self.hi or self.degree < 1:
+            raise ValueError("ChebFilter needs lo < hi, an anchor outside [lo, hi] and degree >= 1")
+        self.c = (self.lo + self.hi) / 2
+        self.e = (self.hi - self.lo) / 2
+        self.A = A
+        self.shape = None if A is None else A.shape
+
+    def apply(self, matvec, x):
+        """``p(A) x`` by the scaled three-term recurrence (Saad; Zhou & Saad 2007); ``matvec(v)`` is ``A v``"""
+        c, e = self.c, self.e
+        s1 = e / (self.anchor - c)
+        s = s1
+        y = (s1 / e) * (matvec(x) - c * x)
+        for _ in range(2, self.degree + 1):
+            s2 = 1.0 / (2.0 / s1 - s)
+            z = 2.0 * (s2 / e) * (matvec(y) - c * y) - (s * s2) * x
+            x, y, s = y, z, s2
+        return y
+
+    def __matmul__(self, x):
+        return self.apply(lambda v: self.A @ v, x)
+
+    def poly(self, lam):
+        """``p(lam)`` in closed form"""
+        d = self.degree
+
+        def cheb(t):
+            t = np.asarray(t, dtype=np.float64)
+            inside = np.abs(t) <= 1
+            out = np.cos(d * np.arccos(np.clip(t, -1, 1)))
+            big = np.cosh(d * np.arccosh(np.maximum(np.abs(t), 1))) * np.where((t < 0) & (d % 2 == 1), -1.0, 1.0)
+            return np.where(inside, out, big)
+
+        return cheb((np.asarray(lam, dtype=np.float64) - self.c) / self.e) / cheb((self.anchor - self.c) / self.e)
+
+    def coefficients(self):
+        """The ``degree`` pairs ``(a_i, b_i)`` of ``z = a_i (A y - c y) - b_i x`` as a ``(degree, 2)`` array: what the device takes as data"""
+        c, e = self.c, self.e
+        s1 = e / (self.anchor - c)
+        s = s1
+        out = [(s1 / e, 0.0)]
+        for _ in range(2, self.degree + 1):
+            s2 = 1.0 / (2.0 / s1 - s)
+            out.append((2.0 * (s2 / e), s * s2))
+            s = s2
+        return np.array(out)
+
+
+_RANGE_CAP = 1e4  # the filter may spread the k wanted eigenvalues of p(A) over at most this ratio (see filter_plan)
+
+
+def check_filter_args(which, filter_degree):
+    """The filter's own argument errors (``check_args`` keeps SciPy's).  Returns the degree as an int."""
+    if isinstance(filter_degree, bool) or not isinstance(filter_degree, (int, np.integer)):
+        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
+    if filter_degree < 2:
+        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
+    if which not in ("SA", "LA"):
+        raise ValueError(f"filter_degree needs which='SA' or 'LA' (got {which!r}): the Chebyshev filter serves one end of the spectrum")
+    return int(filter_degree)
+
+
+def filter_plan(theta, S_last, b_last, k, which, degree):
+    """The filter for ``which`` from stage 0's Ritz values ``theta`` (ascending), the last row of their vectors and the last ``beta``.
+
+    Outer bounds: ``theta_max + beta |s_max|`` and ``theta_min - beta |s_min|`` (an eigenvalue lies within ``beta |s|`` of a Ritz
+    value), each widened by 1e-3 of the width.  Inner edge: the Ritz value with index ``max(m // 2, k + 2)`` counted from the wanted
+    end - Ritz values never lie beyond the eigenvalues of the same index, so the ``k`` wanted ones stay outside the damped interval.
+    Range cap: the loop converges residuals of ``B = p(A)`` to ``eps |B|``; a wanted eigenvalue of ``B`` at ``rho |B|`` then has a
+    vector good to ``eps / rho`` only.  With ``t_a``, ``t_k`` the images ``|lam - c| / e`` of the anchor and of the ``k``-th wanted Ritz
+    value (which errs towards the damped interval), ``p(lam_k) >= ~exp(-d (acosh t_a - acosh t_k))``: the degree used is the largest
+    ``d' <= degree``, at least 2, that keeps this above 1e-4, i.e. true residuals near 1e-12 |A|."""
+    m = len(theta)
+    width = theta[-1] - theta[0]
+    top = theta[-1] + b_last * abs(S_last[-1]) + 1e-3 * width
+    bottom = theta[0] - b_last * abs(S_last[0]) - 1e-3 * width
+    idx = max(m // 2, k + 2)
+    if which == "SA":
+        lo, hi, anchor, th_k = theta[idx], top, bottom, theta[k - 1]
+    else:
+        lo, hi, anchor, th_k = bottom, theta[m - 1 - idx], top, theta[m - k]
+    c, e = (lo + hi) / 2, (hi - lo) / 2
+    gap = np.arccosh(abs(anchor - c) / e) - np.arccosh(max(abs(th_k - c) / e, 1.0))
+    used = degree if gap * degree <= np.log(_RANGE_CAP) else int(np.log(_RANGE_CAP) / gap)
+    return ChebFilter(lo, hi, anchor, max(2, min(degree, used)))
+
+
+def trl_filtered(backend, n, k, which, degree, ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None):
+    """Thick-restart Lanczos on ``B = p(A)``, ``p`` a Chebyshev filter that damps the unwanted part of the spectrum (Zhou & Saad's
+    filtered Lanczos): ``B`` has ``A``'s eigenvectors and its wanted eigenvalues are far better separated, so the loop takes far fewer
+    Gram-Schmidt steps at ``degree`` products with ``A`` each.
+
+    Stage 0: ``ncv`` plain steps give the bounds of the spectrum and the filter (``filter_plan``); a breakdown there (an invariant
+    Krylov space: ``ncv = n``, a handful of distinct eigenvalues) raises ``ValueError`` - the unfiltered loop is the one for such input.  Then the unchanged ``trl`` runs on
+    ``B`` for its largest eigenvalues, and one Rayleigh-Ritz step with ``A`` itself on the ``k`` vectors gives the eigenvalues of ``A``.
+    Acceptance is in ``A``-space: a pair whose true residual exceeds ``1e3 tol_eff 1e4 |A|`` (the range cap's error model with the
+    loop's factor 1e3) is not returned; ``ArpackNoConvergence`` then carries the pairs that pass.
+
+    Returns ``(theta, info)`` as ``trl`` does; ``info`` has ``"steps"`` (Gram-Schmidt steps, stage 0 included), ``"matvecs"`` (products
+    with ``A``: stage 0, ``degree`` per filtered step, Rayleigh-Ritz), ``"filter"`` and ``trl``'s other counts."""
+    degree = check_filter_args(which, degree)
+    m = check_args(n, k, which, ncv)
+    rng = np.random.default_rng(_SEED) if rng is None else rng
+    tol_eff = float(tol) if tol > 0 else _EPS
+    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
+    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
+        raise ValueError("v0 must be a non-zero vector of length n")
+    # stage 0: m plain steps
+    backend.begin(m, v0)
+    backend.set_filter(None)
+    T = np.zeros((m, m))
+    proj, beta = backend.extend(0, m)
+    for j in range(m):
+        T[: j + 1, j] = proj[j, : j + 1]
+        T[j, : j + 1] = proj[j, : j + 1]
+        if j + 1 < m:
+            T[j + 1, j] = T[j, j + 1] = beta[j]
+    if not beta[: m - 1].min() > 10 * _EPS * np.abs(T).max():
+        # the Krylov space of v0 is invariant before ncv steps: its Ritz values bound only that subspace, not the spectrum, so no safe
+        # filter can be built from them (the unfiltered loop handles such a start by itself)
+        raise ValueError("filter_degree: the start vector's Krylov space is invariant after fewer than ncv steps (breakdown in the "
+                         "bounds stage); run without filter_degree, or with another v0")
+    theta0, S0 = np.linalg.eigh((T + T.T) / 2)
+    filt = filter_plan(theta0, S0[m - 1], beta[m - 1], k, which, degree)
+    anorm = max(abs(filt.anchor), abs(filt.hi), abs(filt.lo))
+    # the loop on B = p(A): the wanted images are positive and the largest, the anchor lies on their side
+    backend.set_filter(filt.coefficients(), filt.c)
+    def ritz_in_A(kc):  # Rayleigh-Ritz with A itself on V[0..kc): ascending eigenvalues, their residuals; the rows are rotated in place
+        G = backend.rayleigh(kc)
+        lam, Q = np.linalg.eigh((G + G.T) / 2)
+        S = np.zeros((m, kc))
+        S[:kc] = Q
+        backend.restart(m, kc, S)
+        return lam, backend.residuals(kc, lam) <= 1e3 * tol_eff * _RANGE_CAP * anorm
+
+    try:
+        _, run = trl(backend, n, k, "LA", ncv=m, maxiter=maxiter, tol=tol, v0=v0, probe=probe, rng=rng)
+    except ArpackNoConvergence as e:  # its pairs are those of B: hand on what they give for A
+        kc = len(e.eigenvalues)
+        backend.set_filter(None)
+        lam, ok = ritz_in_A(kc) if kc else (np.zeros(0), np.zeros(0, dtype=bool))
+        vecs = backend.get_vectors(kc)[:, ok] if kc else np.zeros((n, 0))
+        raise ArpackNoConvergence(e.args[0], lam[ok], vecs) from None
+    backend.set_filter(None)
+    lam, ok = ritz_in_A(k)
+    info = dict(run)
+    info["steps"] = m + run["matvecs"]
+    info["matvecs"] = m + run["matvecs"] * filt.degree + k
+    info["anorm"] = anorm
+    info["filter"] = {"requested": degree, "degree": filt.degree, "lo": filt.lo, "hi": filt.hi, "anchor": filt.anchor}
+    if not ok.all():
+        raise ArpackNoConvergence(f"No convergence ({int(ok.sum())}/{k} eigenvectors pass the residual test of the filtered run)",
+                                  lam[ok], backend.get_vectors(k)[:, ok])
+    return lam, info
+
+
 class DeviceBackend:
-    """The six ``lz_trl_*`` calls on one ``_capi.Handle`` that already holds the matrix."""
+    """The ``lz_trl_*`` calls on one ``_capi.Handle`` that already holds the matrix."""
 
     def __init__(self, handle, n, force_second_pass=False):
         self.h = handle
@@ -229,6 +411,12 @@ class DeviceBackend:
     def residuals(self, k, theta):
         return self.h.trl_residuals(k, theta)
 
+    def set_filter(self, coefficients, c=0.0):
+        self.h.trl_set_filter(coefficients, c)
+
+    def rayleigh(self, k):
+        return self.h.trl_rayleigh(k)
+
 
 def upload_matrix(h, A):
     """A (SciPy sparse of any format, dense ndarray, ``synthetic.CSR`` or ``StencilOperator``) -> the handle; returns n."""
@@ -251,7 +439,7 @@ def upload_matrix(h, A):
 
 
 def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=None, tol=0, return_eigenvectors=True, Minv=None,
-          OPinv=None, mode="normal", device_id=0, handle=None, info=None):
+          OPinv=None, mode="normal", device_id=0, handle=None, info=None, filter_degree=None):
     """Find ``k`` eigenvalues and eigenvectors of the real symmetric matrix ``A`` - ``scipy.sparse.linalg.eigsh``'s signature and
     defaults, solved by thick-restart Lanczos on the GPU.
 
@@ -262,17 +450,25 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
     RNG is never touched).  After ``maxiter`` restart cycles (default ``10 n``) ``ArpackNoConvergence`` carries the converged pairs.
     Convergence: ``beta |s_last| <= tol * max|theta|`` (machine epsilon for ``tol = 0``), see the module docstring for why this
     differs from ARPACK's ``tol * max(eps^(2/3), |theta|)``.
-    ``handle``: an open ``_capi.Handle`` to run on (its matrix is replaced); ``info``: a dict that receives the run's counts."""
+    ``handle``: an open ``_capi.Handle`` to run on (its matrix is replaced); ``info``: a dict that receives the run's counts.
+    ``filter_degree`` (an integer >= 2, ``which`` ``"SA"`` or ``"LA"`` only; default None: no filter): run the loop on a Chebyshev
+    polynomial of ``A`` of at most this degree (``trl_filtered``) - several times fewer Gram-Schmidt steps for somewhat more products
+    with ``A``, which pays when a pass over the basis costs many products (long vectors, large ``ncv``, clustered wanted ends)."""
     from . import _capi
 
     n = int(A.shape[0])
     if len(A.shape) != 2 or A.shape[1] != n:
         raise ValueError(f"expected square matrix (shape={A.shape})")
     check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+    if filter_degree is not None:
+        check_filter_args(which, filter_degree)
     h = handle if handle is not None else _capi.Handle(device_id)
     try:
         upload_matrix(h, A)
-        theta, run = trl(DeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+        if filter_degree is None:
+            theta, run = trl(DeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+        else:
+            theta, run = trl_filtered(DeviceBackend(h, n), n, k, which, filter_degree, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
         if info is not None:
             info.update(run)
             info["residuals"] = h.trl_residuals(k, theta)

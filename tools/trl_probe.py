@@ -2,6 +2,9 @@
 gate next to the fixed-n loop's step, and one eigsh run on the device-assembled deuteron Hamiltonian.
 
     python tools/trl_probe.py [--out FILE]      (one JSON object; the record is profiles/r07/trl_probe.json)
+    python tools/trl_probe.py --filter [--out FILE]   the Chebyshev filter (eigsh(filter_degree=...)): the filter step fused into the
+                                                SpMV against SpMV + k_cheb_step, and filtered against unfiltered solves
+                                                (the record is profiles/r08/trl_filter_probe.json)
 
 Times are host wall clock around calls that end in a stream synchronisation, median of several repetitions: a call's fixed cost
 (~20 us: upload of S, launch, synchronisation) is included."""
@@ -15,7 +18,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from lanczos_amd import Hamiltonian, _capi, synthetic  # noqa: E402
-from lanczos_amd.eigsh import DeviceBackend, trl, upload_matrix  # noqa: E402
+from lanczos_amd.eigsh import ChebFilter, DeviceBackend, trl, trl_filtered, upload_matrix  # noqa: E402
 
 HBM_PEAK = 8.0e12  # MI355X HBM3E, bytes/s
 
@@ -57,11 +60,145 @@ def fixed_step(h, M, n0, n1, reps=3):
     return (t1 - t0) / (n1 - n0) * 1e6
 
 
+def filter_step_rates(A, label, matrix_bytes_per_row, reps=21, d_lo=4, d_hi=36):
+    """One filter step (product + recurrence) fused into the ELL SpMV against SpMV + k_cheb_step, on two handles that hold the same
+    matrix, arms interleaved.  A step's time is the difference of lz_trl_filter_apply at degrees d_hi and d_lo over d_hi - d_lo: the
+    upload of x and the download of y cancel.  k_cheb_step's own time: `--filter-trace` under a kernel trace."""
+    hs = {}
+    for arm, flags in (("fused", 0), ("unfused", _capi.FLAG_TRL_FILTER_UNFUSED)):
+        h = _capi.Handle(0)
+        h.set_options(flags)
+        n = upload_matrix(h, A)
+        x = np.random.default_rng(4).standard_normal(n)
+        m = 12
+        h.trl_begin(m, x)
+        hs[arm] = h
+    # the damped interval holds the whole spectrum, so |p| < 1 and nothing overflows while it is timed: bounds from m plain steps
+    # (theta_max + beta, theta_min - beta), widened by the width on either side
+    proj, beta = h.trl_extend(0, m)
+    T = np.triu(proj.T) + np.triu(proj.T, 1).T
+    T[np.arange(m - 1), np.arange(1, m)] = T[np.arange(1, m), np.arange(m - 1)] = beta[: m - 1]
+    th = np.linalg.eigvalsh(T)
+    w = th[-1] - th[0] + 2 * beta[m - 1]
+    lo, hi = th[0] - beta[m - 1] - w, th[-1] + beta[m - 1] + w
+    filt = {d: ChebFilter(lo, hi, lo - 0.05 * w, d) for d in (d_lo, d_hi)}
+    ts = {(arm, d): [] for arm in hs for d in filt}
+    for rep in range(reps + 2):  # two warm-up rounds
+        for arm, h in hs.items():
+            for d, f in filt.items():
+                h.trl_set_filter(f.coefficients(), f.c)
+                t = time.perf_counter()
+                y_last = h.trl_filter_apply(x)
+                if rep >= 2:
+                    ts[(arm, d)].append(time.perf_counter() - t)
+    for h in hs.values():
+        h.close()
+    out = {"matrix": label, "rows": n, "reps": reps, "degrees": [d_lo, d_hi], "matrix_bytes_per_row": matrix_bytes_per_row,
+           "filter": {"lo": lo, "hi": hi, "ritz_min": float(th[0]), "ritz_max": float(th[-1])}, "finite": bool(np.isfinite(y_last).all())}
+    for arm, vec_bytes in (("fused", 24), ("unfused", 40)):
+        step = (float(np.median(ts[(arm, d_hi)])) - float(np.median(ts[(arm, d_lo)]))) / (d_hi - d_lo)
+        nbytes = (vec_bytes + matrix_bytes_per_row) * n
+        out[arm] = {"us_per_step": step * 1e6, "vector_bytes_per_row": vec_bytes, "TBps": nbytes / step / 1e12, "frac_hbm_peak": nbytes / step / HBM_PEAK}
+    out["unfused_over_fused"] = out["unfused"]["us_per_step"] / out["fused"]["us_per_step"]
+    return out
+
+
+def solve_series(A, label, k, ncv, degrees, maxiter=None):
+    """eigsh(k, 'SA') unfiltered and at every degree, on one handle in this order; a run that does not converge within maxiter cycles is recorded as such"""
+    from scipy.sparse.linalg import ArpackNoConvergence
+
+    h = _capi.Handle(0)
+    n = upload_matrix(h, A)
+    v0 = np.random.default_rng(3).standard_normal(n)
+    runs = []
+    for d in [None] + list(degrees):
+        be = DeviceBackend(h, n)
+        t = time.perf_counter()
+        try:
+            if d is None:
+                theta, info = trl(be, n, k, "SA", ncv=ncv, v0=v0, maxiter=maxiter)
+                info = dict(info, steps=info["matvecs"])
+            else:
+                theta, info = trl_filtered(be, n, k, "SA", d, ncv=ncv, v0=v0, maxiter=maxiter)
+        except ArpackNoConvergence as e:
+            runs.append({"filter_degree": d, "converged": False, "wall_s": time.perf_counter() - t, "note": str(e)})
+            print(json.dumps(runs[-1]), flush=True)
+            continue
+        wall = time.perf_counter() - t
+        res = h.trl_residuals(k, theta)
+        runs.append({"filter_degree": d, "degree_used": info.get("filter", {}).get("degree"), "converged": True, "steps": info["steps"],
+                     "A_products": info["matvecs"], "cycles": info["cycles"], "probes": info["probes"], "wall_s": wall,
+                     "theta": theta.tolist(), "max_residual_over_anorm": float(res.max() / info["anorm"])})
+        print(json.dumps(runs[-1]), flush=True)
+    h.close()
+    base = runs[0]["wall_s"] if runs[0]["converged"] else None
+    for r in runs[1:]:
+        r["unfiltered_over_this"] = base / r["wall_s"] if base and r["converged"] else None
+    return {"matrix": label, "rows": n, "k": k, "which": "SA", "ncv": ncv, "maxiter": maxiter, "runs": runs}
+
+
+def filter_probe(a):
+    out = {}
+
+    def save():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+    Hamiltonian.verbose = False
+    N = a.deuteron_n
+    ham = Hamiltonian(N, 25, synthetic.DeuteronPotential(), 197.327**2 / (2 * 469.4592) / (25.0 / N) ** 2)
+    ham.device_potential = True
+    op = ham.operator("27")
+    H = synthetic.laplacian_2d_5pt(4000, a.rows // 4000)
+    # matrix bytes per row of the row-class coded copies: one class byte (5-point, constant coefficients); class byte + the diagonal (27-point)
+    out["step_lap2d"] = filter_step_rates(H, f"laplacian_2d_5pt 4000x{a.rows // 4000}", 1)
+    print(json.dumps(out["step_lap2d"]), flush=True)
+    save()
+    out["step_deuteron"] = filter_step_rates(op, f"deuteron 27-point N={N}", 9)
+    print(json.dumps(out["step_deuteron"]), flush=True)
+    save()
+    out["solve_deuteron"] = solve_series(op, f"deuteron 27-point N={N}", 4, None, (8, 16, 32))
+    save()
+    out["solve_lap2d"] = solve_series(H, f"laplacian_2d_5pt 4000x{a.rows // 4000}", 10, 41, (8, 16, 32), maxiter=a.maxiter)
+    save()
+
+
+def filter_trace(a):
+    """A short run for `rocprofv3 --kernel-trace --stats -- python tools/trl_probe.py --filter-trace`: ten degree-16 filter applications
+    on each arm and matrix, so that the trace's per-kernel averages give k_cheb_step, the plain SpMV and the fused SpMV step."""
+    Hamiltonian.verbose = False
+    N = a.deuteron_n
+    ham = Hamiltonian(N, 25, synthetic.DeuteronPotential(), 197.327**2 / (2 * 469.4592) / (25.0 / N) ** 2)
+    ham.device_potential = True
+    for A in (synthetic.laplacian_2d_5pt(4000, a.rows // 4000), ham.operator("27")):
+        for flags in (0, _capi.FLAG_TRL_FILTER_UNFUSED):
+            h = _capi.Handle(0)
+            h.set_options(flags)
+            n = upload_matrix(h, A)
+            x = np.random.default_rng(4).standard_normal(n)
+            h.trl_begin(2, x)
+            f = ChebFilter(-1.0e6, 1.0e6, -1.1e6, 16)  # (degree 16 of values inside the damped interval: bounded whatever the spectrum)
+            h.trl_set_filter(f.coefficients(), f.c)
+            for _ in range(10):
+                h.trl_filter_apply(x)
+            h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--filter", action="store_true", help="probe the Chebyshev filter instead (see the module docstring)")
+    ap.add_argument("--filter-trace", action="store_true", help="the short run meant for a kernel trace (see filter_trace)")
+    ap.add_argument("--deuteron-n", type=int, default=160)
+    ap.add_argument("--maxiter", type=int, default=400, help="--filter: restart cycles allowed to each solve on the 2-D Laplacian")
     a = ap.parse_args()
+    if a.filter_trace:
+        return filter_trace(a)
+    if a.filter:
+        return filter_probe(a)
     out = {}
     M = a.rows
     H = synthetic.laplacian_2d_5pt(4000, M // 4000)  # the headline's matrix family at M = 1e7
