@@ -516,10 +516,9 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_tsm);
   big_free(h->d_tgate);
   big_free(h->d_tpart);
-  big_free(h->d_tf);
-  big_free(h->d_tcoef);
-  big_free(h->d_tacc);
-  big_free(h->d_tmu);
+  big_free(h->poly.d_rot);
+  big_free(h->poly.d_acc);
+  big_free(h->poly.d_coef);
   if (h->h_pinned) hipHostFree(h->h_pinned);
   xfer_free(h->xfer);
   if (h->cstream) {

@@ -41,6 +41,19 @@ struct RcclApi {
   const char* (*GetErrorString)(ncclResult_t) = nullptr;
 };
 
+// The polynomial p of A that the thick-restart solver multiplies by: with kind != kNone lz_trl_extend forms p(A) V[j] instead of A V[j].
+// One at a time: lz_trl_set_filter and lz_trl_set_series both go through trl_set_poly (lz_trl_api.hip), which clears before it sets.
+struct TrlPoly {
+  enum Kind { kNone, kFilter, kSeries } kind = kNone;
+  int degree = 0, coef_cap = 0;  // coef_cap: the doubles behind d_coef
+  double c = 0.0, inv_e = 0.0;   // the centre of the damped interval (filter) or of the map to [-1, 1] (series); 1 / e of that map
+  double* d_coef = nullptr;      // filter: a[0 .. degree), b[0 .. degree) of z = a_i (A y - c y) - b_i x; series: mu[0 .. degree]
+  double* d_rot = nullptr;       // two work vectors of ld doubles each, rotated with d_tw (allocated when the first polynomial is set)
+  double* d_acc = nullptr;       // the series' running sum, ld doubles (allocated when the first series is set)
+  int64_t ld = 0;                // the row length d_rot and d_acc were allocated for
+  void clear() { kind = kNone, degree = 0; }
+};
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -166,21 +179,7 @@ struct lz_context {
   int* d_tgate = nullptr;      // [0] gate of the second CGS pass
   double* d_tpart = nullptr;   // partials of the passes / SpMV / residual norms
   size_t tpart_cap = 0;
-  // Chebyshev filter of the thick-restart solver (lz_trl_set_filter): with trl_fdeg > 0 lz_trl_extend multiplies by p(A) instead of A
-  double* d_tf = nullptr;      // two more work vectors of trl_ld doubles each (allocated only when a filter is set); tf_ld = their length
-  int64_t tf_ld = 0;
-  double* d_tcoef = nullptr;   // a[0 .. degree), b[0 .. degree) of z = a_i (A y - c y) - b_i x; tcoef_cap doubles
-  int tcoef_cap = 0;
-  int trl_fdeg = 0;            // 0: no filter
-  double trl_fc = 0.0;         // c, the centre of the damped interval
-  // Chebyshev series of the interior mode (lz_trl_set_series): with trl_sdeg > 0 lz_trl_extend multiplies by sum_i mu_i T_i((A - c) / e);
-  // never set together with the filter above, whose two work vectors it shares
-  double* d_tacc = nullptr;    // the running sum, trl_ld doubles (allocated only when a series is set); tacc_ld = its length
-  int64_t tacc_ld = 0;
-  double* d_tmu = nullptr;     // mu[0 .. degree]; tmu_cap doubles
-  int tmu_cap = 0;
-  int trl_sdeg = 0;            // 0: no series
-  double trl_sc = 0.0, trl_sinv_e = 0.0;  // c and 1 / e of the map to [-1, 1]
+  TrlPoly poly;  // none, the Chebyshev filter or the Chebyshev series
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };

@@ -217,13 +217,12 @@ __global__ __launch_bounds__(kTPB) void k_cheb_step(double* __restrict__ wz, con
     z2[p] = z;  // plain store: the next SpMV (or the first Gram-Schmidt pass) reads it at once
   }
 }
+// the grid of both streaming steps (k_cheb_step, k_cheb_series_step): a thread per two rows, 2048 blocks at the most
+static int cheb_grid(int64_t n2) { return (int)std::min<int64_t>(std::max<int64_t>((n2 + kTPB - 1) / kTPB, 1), 2048); }
 void launch_cheb_step(double* wz, const double* y, const double* x, const double* coef, int i, int degree, double c, int64_t rows,
                       int64_t len, hipStream_t s) {
   const int64_t n2 = len >> 1;
-  int64_t g = (n2 + kTPB - 1) / kTPB;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL(k_cheb_step, dim3((int)g), dim3(kTPB), 0, s, wz, y, x, coef, i, degree, c, rows, n2);
+  hipLaunchKernelGGL(k_cheb_step, dim3(cheb_grid(n2)), dim3(kTPB), 0, s, wz, y, x, coef, i, degree, c, rows, n2);
 }
 
 // ------------------------------------------------------------------ Chebyshev series: one term of the recurrence added to the running sum
@@ -260,10 +259,7 @@ __global__ __launch_bounds__(kTPB) void k_cheb_series_step(double* __restrict__ 
 void launch_cheb_series_step(double* wz, const double* y, const double* x, const double* acc_in, double* acc_out, const double* mu, int i,
                              int last, double inv_e, double c, int64_t rows, int64_t len, hipStream_t s) {
   const int64_t n2 = len >> 1;
-  int64_t g = (n2 + kTPB - 1) / kTPB;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL(k_cheb_series_step, dim3((int)g), dim3(kTPB), 0, s, wz, y, x, acc_in, acc_out, mu, i, last, inv_e, c, rows, n2);
+  hipLaunchKernelGGL(k_cheb_series_step, dim3(cheb_grid(n2)), dim3(kTPB), 0, s, wz, y, x, acc_in, acc_out, mu, i, last, inv_e, c, rows, n2);
 }
 
 // ------------------------------------------------------------------ true residuals |A y_i - theta_i y_i|

@@ -62,9 +62,11 @@ int trl_upload_x(lz_handle h, const double* x) {
   return LZ_OK;
 }
 
-// d_tw = A x or, with a filter or a series set, p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never written).  The
-// filter runs the scaled Chebyshev recurrence through three rotating work vectors (d_tw and the two of d_tf) so that the last step
-// lands in d_tw; every product is the plain SpMV / GEMV launch, every recurrence step one k_cheb_step in place on that product.
+// d_tw = A x or, with a polynomial set (h->poly), p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never
+// written).  The recurrence runs through three rotating work vectors (d_tw and the two of poly.d_rot) so that step d lands in d_tw;
+// every product is the plain SpMV / GEMV launch, every recurrence step one streaming kernel in place on that product.
+// Filter: the scaled Chebyshev recurrence, one k_cheb_step per step.  Series: sum_i mu_i T_i, the same rotation for the terms and the
+// running sum in poly.d_acc beside them (k_cheb_series_step); the last term is only added, never stored, and the sum goes to its slot, d_tw.
 void trl_matvec(lz_handle h, const double* x, double* y) {
   if (h->kind == 1)
     launch_spmv_csr(h->csr, x, y, x, h->d_tpart, h->flags, h->stream);
@@ -72,62 +74,75 @@ void trl_matvec(lz_handle h, const double* x, double* y) {
     launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, y, h->d_tpart, h->stream);
 }
 void trl_apply_op(lz_handle h, const double* x) {
-  const int d = h->trl_fdeg > 0 ? h->trl_fdeg : h->trl_sdeg;
-  if (d == 0) {
+  const TrlPoly& P = h->poly;
+  if (P.kind == TrlPoly::kNone) {
     trl_matvec(h, x, h->d_tw);
     return;
   }
-  // fixed-K stencil matrices whose SpMV is the ELL kernel: the step is that kernel's epilogue (24 B per row beside the matrix instead
-  // of 8 + 32), same bits; LZ_FLAG_TRL_FILTER_UNFUSED keeps the two launches
+  const int d = P.degree;
+  const bool series = P.kind == TrlPoly::kSeries;
+  // fixed-K stencil matrices whose SpMV is the ELL kernel: the step is that kernel's epilogue (filter: 24 B of vectors per row beside
+  // the matrix instead of 8 + 32; series: 40 instead of 16 + 48), same bits; LZ_FLAG_TRL_FILTER_UNFUSED keeps the two launches
   const bool fused = h->kind == 1 && h->csr.ell_default && ell_usable(h->csr, h->flags) && !(h->flags & LZ_FLAG_TRL_FILTER_UNFUSED);
-  double* bufs[3] = {h->d_tw, h->d_tf, h->d_tf + h->tf_ld};
-  const double* prev = x;  // x of the recurrence (degree 1: unused, b = 0)
+  double* bufs[3] = {h->d_tw, P.d_rot, P.d_rot + P.ld};
+  const double* prev = x;  // x of the recurrence (filter of degree 1: unused, b = 0)
   const double* cur = x;   // y of the recurrence
-  if (h->trl_sdeg > 0) {
-    // the series sum_i mu_i T_i: the same rotation for the terms, the running sum in d_tacc beside them; the last term is only added,
-    // never stored, and the sum goes to its slot, d_tw (fused: 40 B of vectors per row beside the matrix instead of 16 + 48, same bits)
-    for (int i = 1; i <= d; ++i) {
-      double* z = bufs[(i - d) % 3 == 0 ? 0 : 3 + (i - d) % 3];
-      const bool last = i == d;
-      if (fused) {
-        SpmvCheb ch;
-        ch.xprev = prev;
-        ch.z = last ? nullptr : z;
-        ch.coef = h->d_tmu;
-        ch.i = i;
-        ch.degree = d;
-        ch.c = h->trl_sc;
-        ch.inv_e = h->trl_sinv_e;
-        ch.acc_in = h->d_tacc;
-        ch.acc = last ? h->d_tw : h->d_tacc;
-        launch_spmv_ell(h->csr, cur, z, cur, h->d_tpart, h->stream, nullptr, &ch);
-      } else {
-        trl_matvec(h, cur, z);
-        launch_cheb_series_step(z, cur, prev, h->d_tacc, h->d_tacc, h->d_tmu, i, last, h->trl_sinv_e, h->trl_sc, h->rows, h->rows_pad, h->stream);
-      }
-      prev = cur;
-      cur = z;
-    }
-    return;
-  }
   for (int i = 1; i <= d; ++i) {
     double* z = bufs[(i - d) % 3 == 0 ? 0 : 3 + (i - d) % 3];  // step d -> d_tw
+    const bool last = series && i == d;
     if (fused) {
       SpmvCheb ch;
       ch.xprev = prev;
-      ch.z = z;
-      ch.coef = h->d_tcoef;
-      ch.i = i - 1;
+      ch.z = last ? nullptr : z;
+      ch.coef = P.d_coef;
+      ch.i = series ? i : i - 1;  // mu[i]; a[i - 1], b[i - 1]
       ch.degree = d;
-      ch.c = h->trl_fc;
+      ch.c = P.c;
+      if (series) {
+        ch.inv_e = P.inv_e;
+        ch.acc_in = P.d_acc;
+        ch.acc = last ? h->d_tw : P.d_acc;
+      }
       launch_spmv_ell(h->csr, cur, z, cur, h->d_tpart, h->stream, nullptr, &ch);
     } else {
       trl_matvec(h, cur, z);
-      launch_cheb_step(z, cur, prev, h->d_tcoef, i - 1, d, h->trl_fc, h->rows, h->rows_pad, h->stream);
+      if (series)
+        launch_cheb_series_step(z, cur, prev, P.d_acc, P.d_acc, P.d_coef, i, last, P.inv_e, P.c, h->rows, h->rows_pad, h->stream);
+      else
+        launch_cheb_step(z, cur, prev, P.d_coef, i - 1, d, P.c, h->rows, h->rows_pad, h->stream);
     }
     prev = cur;
     cur = z;
   }
+}
+
+// The one place that sets h->poly (degree 0: clears it): the coefficients are coef0[0 .. n0) followed by coef1[0 .. n1).
+int trl_set_poly(lz_handle h, TrlPoly::Kind kind, int degree, const double* coef0, size_t n0, const double* coef1, size_t n1, double c,
+                 double inv_e) {
+  TrlPoly& P = h->poly;
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  P.clear();  // one polynomial at a time: setting (or clearing) either kind drops what was set
+  if (degree == 0) return LZ_OK;
+  if (!P.d_rot || P.ld != h->trl_ld) {
+    LZ_TRY(dev_free(h, P.d_acc));  // (of the old row length)
+    LZ_TRY(dev_alloc(h, P.d_rot, 2 * (size_t)h->trl_ld));
+    P.ld = h->trl_ld;
+  }
+  if (kind == TrlPoly::kSeries && !P.d_acc) LZ_TRY(dev_alloc(h, P.d_acc, (size_t)P.ld));
+  if ((size_t)P.coef_cap < n0 + n1) {
+    LZ_TRY(dev_alloc(h, P.d_coef, n0 + n1));
+    P.coef_cap = (int)(n0 + n1);
+  }
+  LZ_HIP(h, hipMemsetAsync(P.d_rot, 0, 2 * (size_t)P.ld * sizeof(double), h->stream));
+  if (kind == TrlPoly::kSeries) LZ_HIP(h, hipMemsetAsync(P.d_acc, 0, (size_t)P.ld * sizeof(double), h->stream));
+  LZ_TRY(upload(h, P.d_coef, coef0, n0 * sizeof(double)));
+  if (n1) LZ_TRY(upload(h, P.d_coef + n0, coef1, n1 * sizeof(double)));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  P.kind = kind;
+  P.degree = degree;
+  P.c = c;
+  P.inv_e = inv_e;
+  return LZ_OK;
 }
 
 }  // namespace
@@ -146,8 +161,7 @@ int lz_trl_begin(lz_handle h, int m, const double* v0) {
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   const int64_t ld = skew_stride(h, h->rows_pad);
   if (!h->d_trl || h->trl_m != m || h->trl_ld != ld) {
-    h->trl_fdeg = 0;  // the filter's work vectors belong to the old row length
-    h->trl_sdeg = 0;
+    h->poly.clear();  // its work vectors belong to the old row length
     LZ_TRY(dev_alloc(h, h->d_trl, (size_t)(m + 1) * (size_t)ld));
     LZ_TRY(dev_alloc(h, h->d_tw, (size_t)ld));
     LZ_TRY(dev_alloc(h, h->d_tsm, (size_t)trl_small_layout(m).total));
@@ -266,61 +280,20 @@ int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
 int lz_trl_set_filter(lz_handle h, int degree, const double* a, const double* b, double c) {
   LZ_TRY(trl_state(h, "lz_trl_set_filter"));
   if (degree < 0 || degree > 4096 || (degree > 0 && (!a || !b))) return fail(h, LZ_ERR_ARG, "lz_trl_set_filter: need 0 <= degree <= 4096, a and b");
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->trl_fdeg = 0;
-  h->trl_sdeg = 0;  // one operator at a time: setting (or clearing) the filter clears the series
-  if (degree == 0) return LZ_OK;
-  if (!h->d_tf || h->tf_ld != h->trl_ld) {
-    LZ_TRY(dev_alloc(h, h->d_tf, 2 * (size_t)h->trl_ld));
-    h->tf_ld = h->trl_ld;
-  }
-  if (h->tcoef_cap < 2 * degree) {
-    LZ_TRY(dev_alloc(h, h->d_tcoef, 2 * (size_t)degree));
-    h->tcoef_cap = 2 * degree;
-  }
-  LZ_HIP(h, hipMemsetAsync(h->d_tf, 0, 2 * (size_t)h->trl_ld * sizeof(double), h->stream));
-  LZ_TRY(upload(h, h->d_tcoef, a, (size_t)degree * sizeof(double)));
-  LZ_TRY(upload(h, h->d_tcoef + degree, b, (size_t)degree * sizeof(double)));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->trl_fdeg = degree;
-  h->trl_fc = c;
-  return LZ_OK;
+  return trl_set_poly(h, TrlPoly::kFilter, degree, a, (size_t)degree, b, (size_t)degree, c, 0.0);
 }
 
 int lz_trl_set_series(lz_handle h, int degree, const double* mu, double c, double e) {
   LZ_TRY(trl_state(h, "lz_trl_set_series"));
   if (degree < 0 || degree > 4096 || (degree > 0 && (!mu || !(e > 0.0) || !std::isfinite(c) || !std::isfinite(e))))
     return fail(h, LZ_ERR_ARG, "lz_trl_set_series: need 0 <= degree <= 4096, mu, a finite c and e > 0");
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->trl_sdeg = 0;
-  h->trl_fdeg = 0;  // one operator at a time: setting (or clearing) the series clears the filter
-  if (degree == 0) return LZ_OK;
-  if (!h->d_tf || h->tf_ld != h->trl_ld) {
-    LZ_TRY(dev_alloc(h, h->d_tf, 2 * (size_t)h->trl_ld));
-    h->tf_ld = h->trl_ld;
-  }
-  if (!h->d_tacc || h->tacc_ld != h->trl_ld) {
-    LZ_TRY(dev_alloc(h, h->d_tacc, (size_t)h->trl_ld));
-    h->tacc_ld = h->trl_ld;
-  }
-  if (h->tmu_cap < degree + 1) {
-    LZ_TRY(dev_alloc(h, h->d_tmu, (size_t)degree + 1));
-    h->tmu_cap = degree + 1;
-  }
-  LZ_HIP(h, hipMemsetAsync(h->d_tf, 0, 2 * (size_t)h->trl_ld * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_tacc, 0, (size_t)h->trl_ld * sizeof(double), h->stream));
-  LZ_TRY(upload(h, h->d_tmu, mu, ((size_t)degree + 1) * sizeof(double)));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->trl_sdeg = degree;
-  h->trl_sc = c;
-  h->trl_sinv_e = 1.0 / e;
-  return LZ_OK;
+  return trl_set_poly(h, TrlPoly::kSeries, degree, mu, (size_t)degree + 1, nullptr, 0, c, 1.0 / e);
 }
 
 int lz_trl_filter_apply(lz_handle h, const double* x, double* y) {
   LZ_TRY(trl_state(h, "lz_trl_filter_apply"));
   if (!x || !y) return fail(h, LZ_ERR_ARG, "lz_trl_filter_apply: need x and y");
-  if (h->trl_fdeg == 0 && h->trl_sdeg == 0)
+  if (h->poly.kind == TrlPoly::kNone)
     return fail(h, LZ_ERR_STATE, "lz_trl_filter_apply: no filter set (lz_trl_set_filter or lz_trl_set_series first)");
   double* vm = h->d_trl + (int64_t)h->trl_m * h->trl_ld;  // the residual row carries x and then the result
   LZ_TRY(upload(h, vm, x, (size_t)h->rows * sizeof(double)));

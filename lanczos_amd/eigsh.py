@@ -139,6 +139,26 @@ def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode
     return ncv
 
 
+def _start(n, tol, v0, rng):
+    """``(rng, tol_eff, v0)``: the generator, the effective tolerance and the checked start vector (drawn only when none is given)"""
+    rng = np.random.default_rng(_SEED) if rng is None else rng
+    tol_eff = float(tol) if tol > 0 else _EPS
+    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
+    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
+        raise ValueError("v0 must be a non-zero vector of length n")
+    return rng, tol_eff, v0
+
+
+def _fill(T, proj, beta, j0, j1, couplings=True):
+    """columns ``j0 .. j1 - 1`` of the projected matrix ``T`` (and their rows) from what ``extend`` returned; ``couplings``: the
+    ``beta`` beside the diagonal as well"""
+    for j in range(j0, j1):
+        T[: j + 1, j] = proj[j, : j + 1]
+        T[j, : j + 1] = proj[j, : j + 1]
+        if couplings and j + 1 < len(T):
+            T[j + 1, j] = T[j, j + 1] = beta[j]
+
+
 def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None):
     """The thick-restart outer loop over a backend (``NumpyBackend`` or ``DeviceBackend``).
 
@@ -146,11 +166,7 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
     ``{"matvecs", "cycles", "probes", "breakdowns", "anorm"}`` (anorm: max|theta| over the run, the norm estimate).  Raises ``ArpackNoConvergence`` after ``maxiter`` cycles."""
     m = check_args(n, k, which, ncv)
     maxiter = n * 10 if maxiter is None else int(maxiter)
-    rng = np.random.default_rng(_SEED) if rng is None else rng
-    tol_eff = float(tol) if tol > 0 else _EPS
-    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
-    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
-        raise ValueError("v0 must be a non-zero vector of length n")
+    rng, tol_eff, v0 = _start(n, tol, v0, rng)
     backend.begin(m, v0)
     T = np.zeros((m, m))
     kcur, nw, last = 0, k, None
@@ -161,11 +177,7 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
         while True:  # one extension of the basis to m rows; a breakdown restarts it behind the invariant subspace
             proj, beta = backend.extend(j0, m)
             info["matvecs"] += m - j0
-            for j in range(j0, m):
-                T[: j + 1, j] = proj[j, : j + 1]
-                T[j, : j + 1] = proj[j, : j + 1]
-                if j + 1 < m:
-                    T[j + 1, j] = T[j, j + 1] = beta[j]
+            _fill(T, proj, beta, j0, m)
             scale = max(anorm, np.abs(T).max())
             bad = [j for j in range(j0, m - 1) if not beta[j] > 10 * _EPS * scale]
             if not bad:
@@ -174,9 +186,7 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             info["breakdowns"] += 1
             T[jb + 1:, :] = 0.0
             T[:, jb + 1:] = 0.0
-            for j in range(j0, jb + 1):
-                T[: j + 1, j] = proj[j, : j + 1]
-                T[j, : j + 1] = proj[j, : j + 1]
+            _fill(T, proj, beta, j0, jb + 1, couplings=False)
             backend.probe(jb + 1, rng.standard_normal(n))
             j0 = jb + 1
         info["cycles"] += 1
@@ -203,8 +213,10 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             if conv:
                 backend.restart(m, len(conv), np.ascontiguousarray(S[:, conv]))
                 vecs = backend.get_vectors(len(conv))
-            raise ArpackNoConvergence(f"No convergence ({info['cycles']} iterations, {len(conv)}/{k} eigenvectors converged)",
+            err = ArpackNoConvergence(f"No convergence ({info['cycles']} iterations, {len(conv)}/{k} eigenvectors converged)",
                                       theta[conv], vecs)
+            err.info = info  # the counts of the run that gave up
+            raise err
         if done:
             last = cur
             backend.restart(m, nw, np.ascontiguousarray(S[:, want]))
@@ -286,16 +298,61 @@ class ChebFilter:
 _RANGE_CAP = 1e4  # the filter may spread the k wanted eigenvalues of p(A) over at most this ratio (see filter_plan)
 
 
+def _check_degree(filter_degree):
+    if isinstance(filter_degree, bool) or not isinstance(filter_degree, (int, np.integer)) or filter_degree < 2:
+        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
+    return int(filter_degree)
+
+
 def check_filter_args(which, filter_degree):
     """The filter's own argument errors (``check_args`` keeps SciPy's).  Returns the degree as an int."""
-    if isinstance(filter_degree, bool) or not isinstance(filter_degree, (int, np.integer)):
-        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
-    if filter_degree < 2:
-        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
+    degree = _check_degree(filter_degree)
     if which not in ("SA", "LA"):
         raise ValueError(f"filter_degree needs which='SA' or 'LA' (got {which!r}): the Chebyshev filter serves one end of the spectrum; "
                          "for the eigenvalues nearest a point inside it pass sigma= with which='LM' (sigma=0.0 for 'SM')")
-    return int(filter_degree)
+    return degree
+
+
+def _outer_bounds(theta, S_last, b_last):
+    """``(lo, hi)`` that hold the spectrum, from Ritz values ``theta`` (ascending), the last row of their vectors and the last ``beta``:
+    see ``filter_plan``"""
+    width = theta[-1] - theta[0]
+    hi = theta[-1] + b_last * abs(S_last[-1]) + 1e-3 * width
+    lo = theta[0] - b_last * abs(S_last[0]) - 1e-3 * width
+    return lo, hi
+
+
+def _stage0(backend, m, v0):
+    """Stage 0 of the filtered drivers: ``m`` plain steps from ``v0``.  Returns the Ritz values, the last row of their vectors, the
+    last ``beta`` and the outer bounds ``(lo, hi)`` of the spectrum."""
+    backend.begin(m, v0)
+    backend.set_filter(None)  # (clears a series as well)
+    T = np.zeros((m, m))
+    proj, beta = backend.extend(0, m)
+    _fill(T, proj, beta, 0, m)
+    if not beta[: m - 1].min() > 10 * _EPS * np.abs(T).max():
+        # the Krylov space of v0 is invariant before ncv steps: its Ritz values bound only that subspace, not the spectrum, so no safe
+        # filter can be built from them (the unfiltered loop handles such a start by itself)
+        raise ValueError("filter_degree: the start vector's Krylov space is invariant after fewer than ncv steps (breakdown in the "
+                         "bounds stage); run without filter_degree, or with another v0")
+    theta, S = np.linalg.eigh((T + T.T) / 2)
+    return theta, S[m - 1], beta[m - 1], _outer_bounds(theta, S[m - 1], beta[m - 1])
+
+
+def _ritz_in_A(backend, m, kc, pick=None):
+    """Rayleigh-Ritz with ``A`` itself on ``V[0..kc)``.  ``pick(lam)``: the indices of the ascending eigenvalues ``lam`` to keep
+    (None: all); the rows kept are rotated in place to ``V[0..len)``.  Returns their eigenvalues and residuals."""
+    G = backend.rayleigh(kc)
+    lam, Q = np.linalg.eigh((G + G.T) / 2)
+    if pick is not None:
+        sel = pick(lam)
+        lam, Q = lam[sel], Q[:, sel]
+    if not len(lam):
+        return lam, np.zeros(0)
+    S = np.zeros((m, len(lam)))
+    S[:kc] = Q
+    backend.restart(m, len(lam), S)
+    return lam, backend.residuals(len(lam), lam)
 
 
 def filter_plan(theta, S_last, b_last, k, which, degree):
@@ -309,9 +366,7 @@ def filter_plan(theta, S_last, b_last, k, which, degree):
     value (which errs towards the damped interval), ``p(lam_k) >= ~exp(-d (acosh t_a - acosh t_k))``: the degree used is the largest
     ``d' <= degree``, at least 2, that keeps this above 1e-4, i.e. true residuals near 1e-12 |A|."""
     m = len(theta)
-    width = theta[-1] - theta[0]
-    top = theta[-1] + b_last * abs(S_last[-1]) + 1e-3 * width
-    bottom = theta[0] - b_last * abs(S_last[0]) - 1e-3 * width
+    bottom, top = _outer_bounds(theta, S_last, b_last)
     idx = max(m // 2, k + 2)
     if which == "SA":
         lo, hi, anchor, th_k = theta[idx], top, bottom, theta[k - 1]
@@ -338,49 +393,25 @@ def trl_filtered(backend, n, k, which, degree, ncv=None, maxiter=None, tol=0.0, 
     with ``A``: stage 0, ``degree`` per filtered step, Rayleigh-Ritz), ``"filter"`` and ``trl``'s other counts."""
     degree = check_filter_args(which, degree)
     m = check_args(n, k, which, ncv)
-    rng = np.random.default_rng(_SEED) if rng is None else rng
-    tol_eff = float(tol) if tol > 0 else _EPS
-    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
-    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
-        raise ValueError("v0 must be a non-zero vector of length n")
-    # stage 0: m plain steps
-    backend.begin(m, v0)
-    backend.set_filter(None)
-    T = np.zeros((m, m))
-    proj, beta = backend.extend(0, m)
-    for j in range(m):
-        T[: j + 1, j] = proj[j, : j + 1]
-        T[j, : j + 1] = proj[j, : j + 1]
-        if j + 1 < m:
-            T[j + 1, j] = T[j, j + 1] = beta[j]
-    if not beta[: m - 1].min() > 10 * _EPS * np.abs(T).max():
-        # the Krylov space of v0 is invariant before ncv steps: its Ritz values bound only that subspace, not the spectrum, so no safe
-        # filter can be built from them (the unfiltered loop handles such a start by itself)
-        raise ValueError("filter_degree: the start vector's Krylov space is invariant after fewer than ncv steps (breakdown in the "
-                         "bounds stage); run without filter_degree, or with another v0")
-    theta0, S0 = np.linalg.eigh((T + T.T) / 2)
-    filt = filter_plan(theta0, S0[m - 1], beta[m - 1], k, which, degree)
+    rng, tol_eff, v0 = _start(n, tol, v0, rng)
+    theta0, s_last, b_last, _ = _stage0(backend, m, v0)
+    filt = filter_plan(theta0, s_last, b_last, k, which, degree)
     anorm = max(abs(filt.anchor), abs(filt.hi), abs(filt.lo))
+    res_bound = 1e3 * tol_eff * _RANGE_CAP * anorm
     # the loop on B = p(A): the wanted images are positive and the largest, the anchor lies on their side
     backend.set_filter(filt.coefficients(), filt.c)
-    def ritz_in_A(kc):  # Rayleigh-Ritz with A itself on V[0..kc): ascending eigenvalues, their residuals; the rows are rotated in place
-        G = backend.rayleigh(kc)
-        lam, Q = np.linalg.eigh((G + G.T) / 2)
-        S = np.zeros((m, kc))
-        S[:kc] = Q
-        backend.restart(m, kc, S)
-        return lam, backend.residuals(kc, lam) <= 1e3 * tol_eff * _RANGE_CAP * anorm
-
     try:
         _, run = trl(backend, n, k, "LA", ncv=m, maxiter=maxiter, tol=tol, v0=v0, probe=probe, rng=rng)
     except ArpackNoConvergence as e:  # its pairs are those of B: hand on what they give for A
         kc = len(e.eigenvalues)
         backend.set_filter(None)
-        lam, ok = ritz_in_A(kc) if kc else (np.zeros(0), np.zeros(0, dtype=bool))
+        lam, res = _ritz_in_A(backend, m, kc) if kc else (np.zeros(0), np.zeros(0))
+        ok = res <= res_bound
         vecs = backend.get_vectors(kc)[:, ok] if kc else np.zeros((n, 0))
         raise ArpackNoConvergence(e.args[0], lam[ok], vecs) from None
     backend.set_filter(None)
-    lam, ok = ritz_in_A(k)
+    lam, res = _ritz_in_A(backend, m, k)
+    ok = res <= res_bound
     info = dict(run)
     info["steps"] = m + run["matvecs"]
     info["matvecs"] = m + run["matvecs"] * filt.degree + k
@@ -474,26 +505,10 @@ def check_interior_args(which, sigma, filter_degree):
                                   "eigenvalues nearest sigma are found through a Chebyshev series of A of at most that degree")
     if which != "LM":
         raise NotImplementedError(f"sigma with which={which!r}: only which='LM' (the eigenvalues nearest sigma) is implemented")
-    if isinstance(filter_degree, bool) or not isinstance(filter_degree, (int, np.integer)) or filter_degree < 2:
-        raise ValueError(f"filter_degree must be an integer >= 2, got {filter_degree!r}")
+    degree = _check_degree(filter_degree)
     if isinstance(sigma, (bool, str)) or not np.isscalar(sigma) or not np.isreal(sigma) or not np.isfinite(sigma):
         raise ValueError(f"sigma must be a finite real number, got {sigma!r}")
-    return float(sigma), int(filter_degree)
-
-
-class _CountedBackend:
-    """a backend whose ``extend`` counts its steps (``trl`` does not hand its count on when it gives up)"""
-
-    def __init__(self, backend):
-        self._b = backend
-        self.steps = 0
-
-    def extend(self, k, m):
-        self.steps += m - k
-        return self._b.extend(k, m)
-
-    def __getattr__(self, name):
-        return getattr(self._b, name)
+    return float(sigma), degree
 
 
 def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None, _certify=True):
@@ -519,9 +534,7 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
     Returns ``(theta, info)``; ``info``: ``"steps"`` (Gram-Schmidt steps), ``"matvecs"`` (products with ``A``), both over stage 0 and all
     attempts, ``"filter"`` (``requested``, ``degree``, ``lo``, ``hi``, ``sigma``, ``attempts``) and ``trl``'s counts of the last attempt."""
     check_args(n, k, "LM", None)
-    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or degree < 2:
-        raise ValueError(f"filter_degree must be an integer >= 2, got {degree!r}")
-    degree, sigma = int(degree), float(sigma)
+    degree, sigma = _check_degree(degree), float(sigma)
     extra = max(4, k // 4)
 
     def sizes(extra):  # kb and ncv of an attempt with this many extra pairs
@@ -529,28 +542,8 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
         return kb, check_args(n, kb, "LA", min(n, _MAX_NCV, max(2 * kb + 1, 20)) if ncv is None else ncv)
 
     kb, m = sizes(extra)
-    rng = np.random.default_rng(_SEED) if rng is None else rng
-    tol_eff = float(tol) if tol > 0 else _EPS
-    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
-    if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
-        raise ValueError("v0 must be a non-zero vector of length n")
-    # stage 0: m plain steps
-    backend.begin(m, v0)
-    backend.set_series(None)
-    T = np.zeros((m, m))
-    proj, beta = backend.extend(0, m)
-    for j in range(m):
-        T[: j + 1, j] = proj[j, : j + 1]
-        T[j, : j + 1] = proj[j, : j + 1]
-        if j + 1 < m:
-            T[j + 1, j] = T[j, j + 1] = beta[j]
-    if not beta[: m - 1].min() > 10 * _EPS * np.abs(T).max():
-        raise ValueError("filter_degree: the start vector's Krylov space is invariant after fewer than ncv steps (breakdown in the "
-                         "bounds stage); run without filter_degree, or with another v0")
-    theta0, S0 = np.linalg.eigh((T + T.T) / 2)
-    width = theta0[-1] - theta0[0]
-    hi = theta0[-1] + beta[m - 1] * abs(S0[m - 1, -1]) + 1e-3 * width
-    lo = theta0[0] - beta[m - 1] * abs(S0[m - 1, 0]) - 1e-3 * width
+    rng, tol_eff, v0 = _start(n, tol, v0, rng)
+    _, _, _, (lo, hi) = _stage0(backend, m, v0)
     if not lo <= sigma <= hi:
         raise ValueError(f"sigma={sigma!r} lies outside the spectrum (bounds {lo!r} .. {hi!r}): the eigenvalues nearest to it are an "
                          "end of the spectrum, use which='SA' or which='LA'")
@@ -567,50 +560,48 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
         backend.set_series(filt.coefficients(), filt.c, filt.e)
         att = {"degree": d, "pairs": kb, "steps": 0, "converged": False, "certified": False, "residuals_ok": False}
         attempts.append(att)
-        counted = _CountedBackend(backend)
         try:
-            thB, run = trl(counted, n, kb, "LA", ncv=m, maxiter=maxiter, tol=tol_b, v0=v0, probe=probe, rng=rng)
+            thB, run = trl(backend, n, kb, "LA", ncv=m, maxiter=maxiter, tol=tol_b, v0=v0, probe=probe, rng=rng)
             att["converged"] = True
         except ArpackNoConvergence as err:  # its pairs are those of B: what they certify for A is all this attempt can give
-            thB, run = np.asarray(err.eigenvalues), None
+            thB, run = np.asarray(err.eigenvalues), err.info
         kc = len(thB)
         backend.set_series(None)
-        att["steps"] = counted.steps
-        steps += counted.steps
-        matvecs += counted.steps * d + kc
-        lam, sel, ok = np.zeros(0), np.zeros(0, dtype=int), np.zeros(0, dtype=bool)
+        att["steps"] = run["matvecs"]  # (trl counts its steps there: the loop's operator is one product to it)
+        steps += att["steps"]
+        matvecs += att["steps"] * d + kc
+        theta, ok = np.zeros(0), np.zeros(0, dtype=bool)
         if kc:
-            G = backend.rayleigh(kc)
-            lam, Q = np.linalg.eigh((G + G.T) / 2)
-            near = np.argsort(np.abs(lam - sigma), kind="stable")
-            dist = np.abs(lam - sigma)[near]
             att["p_min"] = p_min = float(np.min(thB))
             margin = 1e3 * tol_b * float(np.abs(thB).max())
 
-            def certified(j):  # is p above p_min on the whole window of the j nearest values found?
-                r = dist[j - 1] - tie
-                return r < 0 or filt.window_min(max(lo, sigma - r), min(hi, sigma + r), 16 * d + 64) > p_min + margin
+            def pick(lam):  # the values nearest sigma that the attempt certifies, as ascending indices
+                near = np.argsort(np.abs(lam - sigma), kind="stable")
+                dist = np.abs(lam - sigma)[near]
 
-            if not _certify:
-                nsel, att["certified"] = min(k, kc), kc >= k
-            elif att["converged"] and certified(k):
-                nsel, att["certified"] = k, True
-            elif att["converged"]:  # the most of the nearest values found that a window certifies
-                nsel = next((j for j in range(k - 1, 0, -1) if certified(j)), 0)
-            else:  # trl gave up: its converged pairs need not be the top of B without a gap, so p_min bounds nothing
-                nsel = 0
-            sel = np.sort(near[:nsel])
-            if nsel:
-                S = np.zeros((m, nsel))
-                S[:kc] = Q[:, sel]
-                backend.restart(m, nsel, S)
-                ok = backend.residuals(nsel, lam[sel]) <= res_bound
+                def certified(j):  # is p above p_min on the whole window of the j nearest values found?
+                    r = dist[j - 1] - tie
+                    return r < 0 or filt.window_min(max(lo, sigma - r), min(hi, sigma + r), 16 * d + 64) > p_min + margin
+
+                if not _certify:
+                    nsel, att["certified"] = min(k, kc), kc >= k
+                elif att["converged"] and certified(k):
+                    nsel, att["certified"] = k, True
+                elif att["converged"]:  # the most of the nearest values found that a window certifies
+                    nsel = next((j for j in range(k - 1, 0, -1) if certified(j)), 0)
+                else:  # trl gave up: its converged pairs need not be the top of B without a gap, so p_min bounds nothing
+                    nsel = 0
+                return np.sort(near[:nsel])
+
+            theta, res = _ritz_in_A(backend, m, kc, pick)
+            if len(theta):
+                ok = res <= res_bound
                 att["residuals_ok"] = bool(ok.all())
         if att["certified"] and att["residuals_ok"]:
             break
         if d == 2:
             err = ArpackNoConvergence(f"No convergence ({int(ok.sum())}/{k} eigenvectors are certified nearest to sigma and pass the residual "
-                                      f"test after {len(attempts)} attempts)", lam[sel][ok], backend.get_vectors(len(sel))[:, ok] if len(sel) else np.zeros((n, 0)))
+                                      f"test after {len(attempts)} attempts)", theta[ok], backend.get_vectors(len(theta))[:, ok] if len(theta) else np.zeros((n, 0)))
             err.info = {"steps": steps, "matvecs": matvecs,
                         "filter": {"requested": degree, "degree": d, "lo": lo, "hi": hi, "sigma": sigma, "attempts": attempts}}
             raise err
@@ -623,7 +614,7 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
     info["matvecs"] = matvecs
     info["anorm"] = anorm
     info["filter"] = {"requested": degree, "degree": d, "lo": lo, "hi": hi, "sigma": sigma, "attempts": attempts}
-    return lam[sel], info
+    return theta, info
 
 
 class DeviceBackend:

@@ -151,6 +151,53 @@ def test_series_and_filter_clear_each_other():
     h.close()
 
 
+def set_operator(h, name, kind, degree):
+    """the series of make_series, or the filter of test_series_and_filter_clear_each_other, at this degree"""
+    if kind == "series":
+        s = make_series(name, degree)
+        h.trl_set_series(s.coefficients(), s.c, s.e)
+    else:
+        ev, _ = spectrum(name)
+        f = ChebFilter(ev[0] + 0.3 * (ev[-1] - ev[0]), ev[-1] + 0.01, ev[0] - 0.01, degree)
+        h.trl_set_filter(f.coefficients(), f.c)
+
+
+# the fused ELL epilogue; the GEMV and the two streaming kernels; 700 rows, no multiple of the padding
+@pytest.mark.parametrize("name", ["lap2d_32x32_n30", "c1_dense512_n20", "ragged_M700_n25"])
+def test_one_operator_state_survives_changes_of_kind_and_degree(name):
+    """The filter and the series share one state in the handle (kind, degree, one coefficient array, the work vectors): after every
+    change of kind or degree - a longer array, a shorter one, a running sum that an earlier series left behind - the operator is
+    bit for bit that of a fresh handle which only ever set this one, and the padding of the result row is zero."""
+    A, _ = _matrix(name)
+    m = 8
+    h = _capi.Handle(0)
+    n = upload_matrix(h, A)
+    x = np.random.default_rng(11).standard_normal(n)
+    h.trl_begin(m, x)
+    fresh = {}
+    for kind, degree in (("series", 3), ("filter", 24), ("series", 40), ("filter", 2), ("series", 3)):
+        set_operator(h, name, kind, degree)
+        y = h.trl_filter_apply(x)
+        raw = h.trl_get_rows(m, 1)[0]
+        if (kind, degree) not in fresh:
+            g = _capi.Handle(0)
+            upload_matrix(g, A)
+            g.trl_begin(m, x)
+            set_operator(g, name, kind, degree)
+            fresh[(kind, degree)] = g.trl_filter_apply(x)
+            g.close()
+        assert np.isfinite(y).all() and np.abs(y).max() > 0
+        assert np.array_equal(y, fresh[(kind, degree)]), (kind, degree)
+        assert np.array_equal(raw[:n], y) and np.all(raw[n:] == 0.0), (kind, degree)
+    h.trl_begin(12, x)  # a basis of another size leaves no operator set
+    with pytest.raises(_capi.LanczosHipError, match="LZ_ERR_STATE"):
+        h.trl_filter_apply(x)
+    h.trl_begin(m, x)  # and the old size does not bring it back
+    with pytest.raises(_capi.LanczosHipError, match="LZ_ERR_STATE"):
+        h.trl_filter_apply(x)
+    h.close()
+
+
 @pytest.mark.parametrize("name,k,sigma", [("graph_M2000_E7000_n40", 10, 5.0), ("lap2d_32x32_n30", 10, 3.0), ("deuteron3d_N12_27pt_n100", 20, 0.0)])
 def test_interior_eigsh_on_the_device(name, k, sigma):
     A, dense = _matrix(name)

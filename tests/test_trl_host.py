@@ -101,6 +101,26 @@ def test_max_iterations_raise_arpack_no_convergence():
     assert len(e.value.eigenvalues) == e.value.eigenvectors.shape[1] < 20
 
 
+def test_a_run_that_gives_up_hands_on_its_counts():
+    """err.info of the ArpackNoConvergence that trl raises: its counts, the steps being those of the extend calls"""
+    from scipy.sparse.linalg import ArpackNoConvergence
+
+    class Counting(NumpyBackend):
+        steps = 0
+
+        def extend(self, k, m):
+            self.steps += m - k
+            return super().extend(k, m)
+
+    A, dense = _matrix("deuteron1d_N1001_n1001")
+    be = Counting(A)
+    with pytest.raises(ArpackNoConvergence) as e:
+        trl(be, dense.shape[0], 20, "SM", maxiter=1)
+    info = e.value.info
+    assert {"matvecs", "cycles", "probes", "breakdowns"} <= set(info)
+    assert info["matvecs"] == be.steps > 0 and info["cycles"] == 1
+
+
 def test_global_rng_is_untouched():
     A, dense = _matrix("lap2d_32x32_n30")
     np.random.seed(7)
