@@ -450,7 +450,22 @@ int lz_trl_filter_apply(lz_handle h, const double* x, double* y);
 /* G_out (k x k row-major, 1 <= k < m) = V[0..k) A V[0..k)^T: per row one product with A itself (a filter is ignored) and one pass over
  * the k rows.  The Rayleigh-Ritz step that turns the eigenvectors of p(A) into eigenpairs of A. */
 int lz_trl_rayleigh(lz_handle h, int k, double* G_out);
-/* raw basis rows j0 .. j0 + count - 1 (0 <= j0, j0 + count <= m + 1) including their padding (lz_padded_rows(rows) doubles each), host
+/* Band (block) Lanczos, Ruhe's form (lanczos_amd.eigsh(block_size=b)): b start vectors, basis row r made from A V[r - b].  The basis has
+ * m + b rows: lz_trl_begin_band allocates and zeroes them (b <= m <= min(128, rows - b), 2 <= b <= 8) and makes rows 0 .. b-1 from the
+ * rows of X (b x rows_local, row-major), each orthogonalised against the ones before it as lz_trl_probe does.  lz_trl_begin is the b = 1
+ * case and stays the only way to a basis for lz_trl_extend; lz_trl_extend_band on such a basis (and lz_trl_extend on a band) is
+ * LZ_ERR_STATE.  On a band basis lz_trl_restart moves all b residual rows (V[kk + r] = V[m + r], r < b), and lz_trl_probe,
+ * lz_trl_set_rows and lz_trl_get_rows reach rows up to m + b - 1.  A filter or series set after lz_trl_begin_band applies as it does
+ * to lz_trl_extend; a basis of another m or b drops it. */
+int lz_trl_begin_band(lz_handle h, int m, int b, const double* X);
+/* steps j = k .. m-1 in batches of up to b, without a host synchronisation.  A batch at j forms w_i = A V[j + i] (or p(A) V[j + i]) for
+ * its steps, orthogonalises all of them against V[0 .. j + b) by two classical Gram-Schmidt passes of two sweeps each - one kernel forms
+ * all (j + b) x b dots, one updates all b vectors, every basis row read once per sweep - and then, one by one, against the rows the batch
+ * itself has made (two passes, the single-vector kernels): beta_{j+i} = |w_i|, V[j + i + b] = w_i / beta_{j+i}.  There is no DGKS gate.
+ * proj_out (m x (m + b) row-major): row j receives the coefficients of A V[j] on V[0 .. j + b) (both passes' sums), rows k .. m-1 only;
+ * beta_out[m]: beta_j, the coefficient on V[j + b].  Either may be NULL.  Sums are formed in a fixed order: same input, same bits. */
+int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta_out);
+/* raw basis rows j0 .. j0 + count - 1 (0 <= j0, j0 + count <= m + 1; band: m + b) including their padding (lz_padded_rows(rows) doubles each), host
  * rows ld >= that apart: tests of the restart kernel */
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
 int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);

@@ -161,6 +161,8 @@ SIGNATURES = {
     "lz_step_bireorth_mem_safe": (C.c_int, [_P, C.c_int]),
     "lz_trl_begin": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_trl_begin_band": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_trl_extend_band": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
     "lz_trl_restart": (C.c_int, [_P, C.c_int, C.c_int, _D]),
     "lz_trl_probe": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_get_vectors": (C.c_int, [_P, C.c_int, _D]),
@@ -772,7 +774,7 @@ class Handle:
 
     # -- thick-restart Lanczos (lanczos_amd.eigsh): a basis of its own, never the fixed-n run's V / Y
     def trl_begin(self, m, v0):
-        self.trl_m = int(m)
+        self.trl_m, self.trl_b = int(m), 1
         self.check(self.lib.lz_trl_begin(self._h, int(m), dptr(f64(v0))))
 
     def trl_extend(self, k, m):
@@ -780,6 +782,20 @@ class Handle:
         proj = np.zeros((m, m))
         beta = np.zeros(m)
         self.check(self.lib.lz_trl_extend(self._h, int(k), int(m), dptr(proj), dptr(beta)))
+        return proj, beta
+
+    def trl_begin_band(self, m, X):
+        """band Lanczos: a basis of m + b rows, rows 0 .. b-1 from the b rows of X (orthonormalised one by one)"""
+        X = f64(X)
+        assert X.ndim == 2 and X.shape[1] == self.rows
+        self.trl_m, self.trl_b = int(m), X.shape[0]
+        self.check(self.lib.lz_trl_begin_band(self._h, int(m), X.shape[0], dptr(X)))
+
+    def trl_extend_band(self, k, m):
+        """steps k .. m-1 -> (proj (m, m + b): row j = the coefficients of A V[j] on V[0 .. j + b) for j >= k, beta (m,))"""
+        proj = np.zeros((m, m + self.trl_b))
+        beta = np.zeros(m)
+        self.check(self.lib.lz_trl_extend_band(self._h, int(k), int(m), dptr(proj), dptr(beta)))
         return proj, beta
 
     def trl_restart(self, m, kk, S):

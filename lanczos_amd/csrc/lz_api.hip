@@ -513,6 +513,7 @@ int lz_destroy(lz_handle h) {
   big_free(h->res_Y);
   big_free(h->d_trl);
   big_free(h->d_tw);
+  big_free(h->d_tW);
   big_free(h->d_tsm);
   big_free(h->d_tgate);
   big_free(h->d_tpart);

@@ -170,11 +170,13 @@ struct lz_context {
   size_t res_V_count = 0;
   double* res_Y = nullptr;
   size_t res_Y_count = 0;
-  // thick-restart Lanczos (lz_trl_api.hip): a basis of its own (trl_m + 1 rows of trl_ld doubles), never the fixed-n run's d_V / d_Y
+  // thick-restart Lanczos (lz_trl_api.hip): a basis of its own (trl_m + trl_b rows of trl_ld doubles), never the fixed-n run's d_V / d_Y
   double* d_trl = nullptr;
   int trl_m = 0;
+  int trl_b = 1;               // residual rows behind the m basis rows: 1 (lz_trl_begin) or the band width (lz_trl_begin_band)
   int64_t trl_ld = 0;
   double* d_tw = nullptr;      // w = A V[j], then the residual (rows_pad)
+  double* d_tW = nullptr;      // band Lanczos: the trl_b work vectors of a batch (trl_ld apart)
   double* d_tsm = nullptr;     // small arrays: see trl_small_layout in lz_trl_api.hip
   int* d_tgate = nullptr;      // [0] gate of the second CGS pass
   double* d_tpart = nullptr;   // partials of the passes / SpMV / residual norms

@@ -322,6 +322,19 @@ int launch_trl_cgs(const double* V, int64_t ldv, int64_t len, int nrows, const d
 int trl_cgs_blocks(int64_t len);
 // one block between the passes of an extension step (mode 0: after pass 1, sets the gate of pass 2; 1: after the gated pass 2; 2: norm only)
 void launch_trl_post(int mode, const double* part, int np, const double* c, int j, double* nrm2, double* proj, int* gate, int force, hipStream_t s);
+// band Lanczos (lz_trl_extend_band): the block Gram-Schmidt of b (2 .. 8) work vectors W[c] (c-th at W + c * ldw) against V[0..r0).
+// dots: part[g * run + i * b + c] = block g's share of V_i . W_c (run = trl_band_run(r0, b), g < trl_band_dots_blocks(len, b));
+// launch_final_rows_t(part, blocks, run, r0 * b, C) then gives C[i * b + c].  len: a multiple of 32.
+inline int trl_band_run(int r0, int b) { return (r0 * b + 15) & ~15; }
+int trl_band_dots_blocks(int64_t len, int b);
+hipError_t launch_trl_band_dots(const double* V, int64_t ldv, int64_t len, int r0, const double* W, int64_t ldw, int b, double* part, hipStream_t s);
+// update: W_c -= sum_{i < r0} C[i * b + c] V_i for every c from one walk over the rows, part[c * G + g] = block g's share of |W_c|^2;
+// returns G (= trl_band_update_blocks(len))
+int trl_band_update_blocks(int64_t len);
+int launch_trl_band_update(const double* V, int64_t ldv, int64_t len, int r0, const double* C, double* W, int64_t ldw, int b, double* part,
+                           hipStream_t s);
+// proj[c * ldf + i] = C1[i * b + c] + C2[i * b + c] (i < r0, c < nb): the two passes' coefficients summed into nb rows of the projected matrix
+void launch_trl_band_proj(const double* C1, const double* C2, int r0, int b, int nb, double* proj, int ldf, hipStream_t s);
 // squares of A y_i - theta_i y_i, block partials at part[i * G + b]; return G
 int launch_trl_resid_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* theta, double* part, hipStream_t s);
 int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s);

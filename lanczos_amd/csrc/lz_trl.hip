@@ -1,5 +1,6 @@
 // Kernels of the thick-restart Lanczos solver (lz_trl_api.hip, lanczos_amd/eigsh.py): the in-place restart V[0..kk) <- S^T V[0..m),
-// the classical Gram-Schmidt update of r, the one-block bookkeeping between the passes, and the fused residual norms.
+// the classical Gram-Schmidt update of r, the band form's block Gram-Schmidt (dots and update of b work vectors per walk over the
+// basis), the one-block bookkeeping between the passes, and the fused residual norms.
 #include "lz_device.h"
 
 namespace lz {
@@ -169,6 +170,231 @@ int launch_trl_cgs(const double* V, int64_t ldv, int64_t len, int nrows, const d
 int trl_cgs_blocks(int64_t len) {
   const int64_t n2 = len >> 1;
   return n2 >= (int64_t)kTPB * 4 * kNumCU ? (int)((n2 + kTPB * 4 - 1) / (kTPB * 4)) : (int)((n2 + kTPB - 1) / kTPB);
+}
+
+// ------------------------------------------------------------------ band Lanczos: C = V[0..r0) W^T, all b columns from one walk over the basis
+// v_mfma_f64_4x4x4_4b_f64 in k_qtw_mfma4's arrangement (lz_reorth.hip: A[blk][i][k] in lane 16k + 4blk + i, B[blk][k][jj] in lane
+// 16k + 4blk + jj, D[blk][i][jj] in lane 16i + 4blk + jj; the four blocks are four adjacent 64-byte chunks of the same four basis
+// rows).  There the B operand broadcasts one vector over the four columns jj; here column jj IS work vector 4g + jj, so one MFMA
+// per four basis rows forms the dots with four work vectors (NG = 2: two MFMAs for up to eight) from one load of the rows.
+// A block stages a slice of L positions of all b work vectors in LDS, walks the r0 rows of that slice from the newest down (the
+// update pass that follows starts at row 0), and adds the tile results to its wave's r0 x b run in LDS; the grid is persistent
+// (slice = blockIdx.x, + gridDim.x, ...), so a block leaves ONE run however long the rows are.  The four waves' runs are added in
+// wave order, the blocks' runs by k_final_rows_t: a fixed order, no atomics.  len is a multiple of 32, L of 128.
+template <int NG>
+__global__ __launch_bounds__(kTPB) void k_trl_band_dots(const double* __restrict__ V, int64_t ldv, int64_t len, int r0,
+                                                       const double* __restrict__ W, int64_t ldw, int b, int L, int run,
+                                                       double* __restrict__ part) {
+  extern __shared__ double2 sw[];  // [b][L / 2] double2 of W, then [4][run] doubles
+  constexpr int T = 2, U = 4;
+  double* keep_all = reinterpret_cast<double*>(sw) + (int64_t)b * L;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double* keep = keep_all + w * run;
+  for (int i = threadIdx.x; i < 4 * run; i += kTPB) keep_all[i] = 0.0;
+  const int li = lane & 3, blk = (lane >> 2) & 3, lk = lane >> 4;
+  const int sub = L >> 2;  // positions per wave (a multiple of 32)
+  const int m_lo = w * sub;
+  const int eoff = 8 * blk + 2 * lk;
+  const int L2 = L >> 1;
+  const int64_t nslices = (len + L - 1) / L;
+  const int i_top = ((r0 - 1) / (4 * T)) * (4 * T);
+  for (int64_t slice = blockIdx.x; slice < nslices; slice += gridDim.x) {
+    const int64_t base = slice * L;
+    const int cnt = (int)(len - base < L ? len - base : L);
+    __syncthreads();  // the previous slice's image is no longer read (first trip: the runs are zero)
+    for (int c = 0; c < b; ++c) {
+      const double2* src = reinterpret_cast<const double2*>(W + (int64_t)c * ldw + base);
+      for (int t = threadIdx.x; t < (cnt >> 1); t += kTPB) sw[c * L2 + t] = src[t];
+    }
+    __syncthreads();
+    int m_hi = m_lo + sub;
+    if (m_hi > cnt) m_hi = cnt;
+    const int nsteps = m_hi > m_lo ? (m_hi - m_lo) >> 5 : 0;  // 32 positions (256 B of a row) per step
+    if (nsteps == 0) continue;                                // (wave-uniform; the barriers above are reached by every wave)
+    const double2* swl[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int col = 4 * g + li;
+      swl[g] = sw + (col < b ? col : 0) * L2 + ((m_lo + eoff) >> 1);
+    }
+    for (int i0 = i_top; i0 >= 0; i0 -= 4 * T) {
+      const double2* a[T];
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        int i = i0 + 4 * t + li;
+        if (i >= r0) i = r0 - 1;  // clamped duplicate, discarded below
+        a[t] = reinterpret_cast<const double2*>(V + (int64_t)i * ldv + base + m_lo + eoff);
+      }
+      double acc[T][NG];
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[t][g] = 0.0;
+      for (int s0 = 0; s0 < nsteps; s0 += U) {
+        double2 av[T][U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int t = 0; t < T; ++t) av[t][u] = (s0 + u < nsteps) ? ld_stream<1>(a[t] + 16 * (s0 + u)) : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int g = 0; g < NG; ++g) {
+            const double2 bv = (s0 + u < nsteps && 4 * g + li < b) ? swl[g][16 * (s0 + u)] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+              acc[t][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[t][u].x, bv.x, acc[t][g], 0, 0, 0);
+              acc[t][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[t][u].y, bv.y, acc[t][g], 0, 0, 0);
+            }
+          }
+      }
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          double v = acc[t][g];       // D[blk][i][jj] in lane 16 i + 4 blk + jj
+          v += __shfl_xor(v, 4, 64);  // add the four blocks (adjacent 64-byte chunks)
+          v += __shfl_xor(v, 8, 64);
+          const int row = i0 + 4 * t + lk, col = 4 * g + li;
+          if (blk == 0 && row < r0 && col < b) keep[row * b + col] += v;  // this wave's own run: no other wave touches it
+        }
+    }
+  }
+  __syncthreads();
+  double* mine = part + (int64_t)blockIdx.x * run;
+  for (int i = threadIdx.x; i < run; i += kTPB) mine[i] = ((keep_all[i] + keep_all[run + i]) + keep_all[2 * run + i]) + keep_all[3 * run + i];
+}
+
+// slice length of k_trl_band_dots: about 40 KiB of work vectors per block (four blocks per CU), at least 512 positions
+static int band_slice(int b) { return 512 * std::max(1, 10 / b); }
+int trl_band_dots_blocks(int64_t len, int b) {
+  const int L = band_slice(b);
+  return (int)std::min<int64_t>((len + L - 1) / L, 4 * kNumCU);
+}
+hipError_t launch_trl_band_dots(const double* V, int64_t ldv, int64_t len, int r0, const double* W, int64_t ldw, int b, double* part,
+                                hipStream_t s) {
+  const int L = band_slice(b);
+  const int run = trl_band_run(r0, b);
+  const int G = trl_band_dots_blocks(len, b);
+  const size_t lds = ((size_t)b * L + 4 * (size_t)run) * sizeof(double);
+  if (b <= 4) {
+    if (lds > 65536) {
+      const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_trl_band_dots<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(k_trl_band_dots<1>, dim3(G), dim3(kTPB), lds, s, V, ldv, len, r0, W, ldw, b, L, run, part);
+  } else {
+    if (lds > 65536) {
+      const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_trl_band_dots<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(k_trl_band_dots<2>, dim3(G), dim3(kTPB), lds, s, V, ldv, len, r0, W, ldw, b, L, run, part);
+  }
+  return hipSuccess;
+}
+
+// ------------------------------------------------------------------ band Lanczos: W[c] -= sum_{i < r0} C[i][c] V_i for all b columns in one walk
+// k_trl_cgs with B accumulators per position: a lane owns P double2 positions of every work vector and walks the rows RU at a time,
+// every row loaded once for all B columns; the sums are formed in row order (products and sums rounded separately) and subtracted
+// once.  part[c * gridDim.x + block] = the block's share of |w_c|^2.
+template <int B, int P, int RU>
+__global__ __launch_bounds__(kTPB) void k_trl_band_update(const double* __restrict__ V, int64_t ldv, int64_t n2, int r0,
+                                                         const double* __restrict__ C, double* __restrict__ W, int64_t ldw,
+                                                         double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
+  const int64_t ld2 = ldv >> 1, lw2 = ldw >> 1;
+  const double2* V2 = reinterpret_cast<const double2*>(V);
+  double2* W2 = reinterpret_cast<double2*>(W);
+  int64_t pos[P];
+  bool ok[P];
+  double tx[B][P], ty[B][P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    pos[p] = base + (int64_t)p * kTPB;
+    ok[p] = pos[p] < n2;
+    if (!ok[p]) pos[p] = n2 - 1;
+#pragma unroll
+    for (int c = 0; c < B; ++c) tx[c][p] = ty[c][p] = 0.0;
+  }
+  for (int k = 0; k < r0; k += RU) {
+    double2 q[RU][P];
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < r0)
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(V2 + (int64_t)(k + u) * ld2 + pos[p]);
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < r0) {
+#pragma unroll
+        for (int c = 0; c < B; ++c) {
+          const double ck = C[(k + u) * B + c];
+#pragma unroll
+          for (int p = 0; p < P; ++p) {
+            tx[c][p] = tx[c][p] + ck * q[u][p].x;
+            ty[c][p] = ty[c][p] + ck * q[u][p].y;
+          }
+        }
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < B; ++c) {
+    double ss = 0.0;
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+      if (ok[p]) {
+        double2 x = W2[(int64_t)c * lw2 + pos[p]];
+        x.x = x.x - tx[c][p];
+        x.y = x.y - ty[c][p];
+        W2[(int64_t)c * lw2 + pos[p]] = x;
+        ss = fma(x.x, x.x, ss);
+        ss = fma(x.y, x.y, ss);
+      }
+    ss = block_sum(ss, sm);
+    if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = ss;
+  }
+}
+
+int trl_band_update_blocks(int64_t len) {
+  const int64_t n2 = len >> 1;
+  return n2 >= (int64_t)kTPB * 2 * kNumCU ? (int)((n2 + kTPB * 2 - 1) / (kTPB * 2)) : (int)((n2 + kTPB - 1) / kTPB);
+}
+template <int B>
+static int launch_trl_band_update_t(const double* V, int64_t ldv, int64_t len, int r0, const double* C, double* W, int64_t ldw, double* part,
+                                    hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  const int grid = trl_band_update_blocks(len);
+  if (n2 >= (int64_t)kTPB * 2 * kNumCU)  // long rows: 2 positions x 4 rows in flight per lane
+    hipLaunchKernelGGL((k_trl_band_update<B, 2, 4>), dim3(grid), dim3(kTPB), 0, s, V, ldv, n2, r0, C, W, ldw, part);
+  else  // short rows: one position per lane, 8 rows in flight
+    hipLaunchKernelGGL((k_trl_band_update<B, 1, 8>), dim3(grid), dim3(kTPB), 0, s, V, ldv, n2, r0, C, W, ldw, part);
+  return grid;
+}
+int launch_trl_band_update(const double* V, int64_t ldv, int64_t len, int r0, const double* C, double* W, int64_t ldw, int b, double* part,
+                           hipStream_t s) {
+  switch (b) {
+    case 2: return launch_trl_band_update_t<2>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 3: return launch_trl_band_update_t<3>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 4: return launch_trl_band_update_t<4>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 5: return launch_trl_band_update_t<5>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 6: return launch_trl_band_update_t<6>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 7: return launch_trl_band_update_t<7>(V, ldv, len, r0, C, W, ldw, part, s);
+    case 8: return launch_trl_band_update_t<8>(V, ldv, len, r0, C, W, ldw, part, s);
+    default: return 0;
+  }
+}
+
+// proj[c * ldf + i] = C1[i * b + c] + C2[i * b + c] for i < r0, c < nb: rows j .. j + nb - 1 of the projected coefficients, columns 0 .. r0 - 1
+__global__ __launch_bounds__(kTPB) void k_trl_band_proj(const double* __restrict__ C1, const double* __restrict__ C2, int r0, int b, int nb,
+                                                       double* __restrict__ proj, int ldf) {
+  for (int f = threadIdx.x; f < r0 * nb; f += kTPB) {
+    const int c = f / r0, i = f % r0;
+    proj[(int64_t)c * ldf + i] = C1[i * b + c] + C2[i * b + c];
+  }
+}
+void launch_trl_band_proj(const double* C1, const double* C2, int r0, int b, int nb, double* proj, int ldf, hipStream_t s) {
+  hipLaunchKernelGGL(k_trl_band_proj, dim3(1), dim3(kTPB), 0, s, C1, C2, r0, b, nb, proj, ldf);
 }
 
 // ------------------------------------------------------------------ between the passes (one block)

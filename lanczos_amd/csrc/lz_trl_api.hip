@@ -1,5 +1,5 @@
 // C ABI of the thick-restart Lanczos solver (include/lanczos_hip.h, "thick-restart Lanczos"): the device half of lanczos_amd.eigsh.
-// The basis is a buffer of its own (d_trl: trl_m + 1 rows of trl_ld doubles); the fixed-n run's V / Y on the same handle are untouched.
+// The basis is a buffer of its own (d_trl: trl_m + trl_b rows of trl_ld doubles); the fixed-n run's V / Y on the same handle are untouched.
 #include "lz_context.h"
 
 using namespace lz;
@@ -7,27 +7,37 @@ using namespace lz::api;
 
 namespace {
 
-// d_tsm: c of pass 1 and of pass 2 (cl doubles each), nrm2 + a scratch beta slot, the projected rows (m x m), beta (m), the restart's
-// S (m x m), theta and the residual norms (m each)
+// d_tsm: c of pass 1 and of pass 2 (cl doubles each), nrm2 + a scratch beta slot, the projected rows (m x m; band: m x (m + b)), beta (m),
+// the restart's S (m x m), theta and the residual norms (m each); band only: the block coefficients of both passes ((m + b) x b each)
+// and the b squared norms of a batch
 struct TrlSmall {
-  int64_t c1, c2, nrm2, proj, beta, S, theta, res, total;
+  int64_t c1, c2, nrm2, proj, beta, S, theta, res, C1, C2, nrmb, total;
+  int ldf;  // row length of proj
 };
-TrlSmall trl_small_layout(int m) {
+TrlSmall trl_small_layout(int m, int b = 1) {
   TrlSmall L;
-  const int64_t cl = qtw_ldp(m + 2) + 16;
+  const int64_t cl = qtw_ldp(m + b + 1) + 16;
+  L.ldf = b > 1 ? m + b : m;
   L.c1 = 0;
   L.c2 = cl;
   L.nrm2 = 2 * cl;
   L.proj = L.nrm2 + 8;
-  L.beta = L.proj + (int64_t)m * m;
+  L.beta = L.proj + (int64_t)m * L.ldf;
   L.S = L.beta + m + 8;
   L.theta = L.S + (int64_t)m * m;
   L.res = L.theta + m;
-  L.total = L.res + m + 8;
+  L.C1 = L.res + m + 8;
+  const int64_t cb = b > 1 ? trl_band_run(m + b, b) + 16 : 0;
+  L.C2 = L.C1 + cb;
+  L.nrmb = L.C2 + cb;
+  L.total = L.nrmb + (b > 1 ? 16 : 0);
   return L;
 }
+TrlSmall trl_small_layout(lz_handle h) { return trl_small_layout(h->trl_m, h->trl_b); }
 
-QtwPlan trl_plan(lz_handle h) { return plan_qtw(h->rows_pad, h->flags & ~(LZ_FLAG_QTW_MFMA | LZ_FLAG_ONE_REDUCE), h->tune, h->trl_m + 2); }
+QtwPlan trl_plan(lz_handle h) {
+  return plan_qtw(h->rows_pad, h->flags & ~(LZ_FLAG_QTW_MFMA | LZ_FLAG_ONE_REDUCE), h->tune, h->trl_m + h->trl_b + 1);
+}
 
 int trl_state(lz_handle h, const char* who) {
   if (!h) return LZ_ERR_ARG;
@@ -39,7 +49,7 @@ int trl_state(lz_handle h, const char* who) {
 
 // V[k] = x (in d_tw) made orthogonal to V[0..k) by two CGS passes, then normalised
 int trl_orth_store(lz_handle h, int k) {
-  const TrlSmall L = trl_small_layout(h->trl_m);
+  const TrlSmall L = trl_small_layout(h);
   double* V = h->d_trl;
   const QtwPlan plan = trl_plan(h);
   int np = 0;
@@ -62,21 +72,22 @@ int trl_upload_x(lz_handle h, const double* x) {
   return LZ_OK;
 }
 
-// d_tw = A x or, with a polynomial set (h->poly), p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never
-// written).  The recurrence runs through three rotating work vectors (d_tw and the two of poly.d_rot) so that step d lands in d_tw;
+// out = A x or, with a polynomial set (h->poly), p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never
+// written; out: d_tw, or a work vector of a band batch).  The recurrence runs through three rotating work vectors (out and the two of
+// poly.d_rot) so that step d lands in out;
 // every product is the plain SpMV / GEMV launch, every recurrence step one streaming kernel in place on that product.
 // Filter: the scaled Chebyshev recurrence, one k_cheb_step per step.  Series: sum_i mu_i T_i, the same rotation for the terms and the
-// running sum in poly.d_acc beside them (k_cheb_series_step); the last term is only added, never stored, and the sum goes to its slot, d_tw.
+// running sum in poly.d_acc beside them (k_cheb_series_step); the last term is only added, never stored, and the sum goes to its slot, out.
 void trl_matvec(lz_handle h, const double* x, double* y) {
   if (h->kind == 1)
     launch_spmv_csr(h->csr, x, y, x, h->d_tpart, h->flags, h->stream);
   else
     launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, y, h->d_tpart, h->stream);
 }
-void trl_apply_op(lz_handle h, const double* x) {
+void trl_apply_op(lz_handle h, const double* x, double* out) {
   const TrlPoly& P = h->poly;
   if (P.kind == TrlPoly::kNone) {
-    trl_matvec(h, x, h->d_tw);
+    trl_matvec(h, x, out);
     return;
   }
   const int d = P.degree;
@@ -84,11 +95,11 @@ void trl_apply_op(lz_handle h, const double* x) {
   // fixed-K stencil matrices whose SpMV is the ELL kernel: the step is that kernel's epilogue (filter: 24 B of vectors per row beside
   // the matrix instead of 8 + 32; series: 40 instead of 16 + 48), same bits; LZ_FLAG_TRL_FILTER_UNFUSED keeps the two launches
   const bool fused = h->kind == 1 && h->csr.ell_default && ell_usable(h->csr, h->flags) && !(h->flags & LZ_FLAG_TRL_FILTER_UNFUSED);
-  double* bufs[3] = {h->d_tw, P.d_rot, P.d_rot + P.ld};
+  double* bufs[3] = {out, P.d_rot, P.d_rot + P.ld};
   const double* prev = x;  // x of the recurrence (filter of degree 1: unused, b = 0)
   const double* cur = x;   // y of the recurrence
   for (int i = 1; i <= d; ++i) {
-    double* z = bufs[(i - d) % 3 == 0 ? 0 : 3 + (i - d) % 3];  // step d -> d_tw
+    double* z = bufs[(i - d) % 3 == 0 ? 0 : 3 + (i - d) % 3];  // step d -> out
     const bool last = series && i == d;
     if (fused) {
       SpmvCheb ch;
@@ -101,7 +112,7 @@ void trl_apply_op(lz_handle h, const double* x) {
       if (series) {
         ch.inv_e = P.inv_e;
         ch.acc_in = P.d_acc;
-        ch.acc = last ? h->d_tw : P.d_acc;
+        ch.acc = last ? out : P.d_acc;
       }
       launch_spmv_ell(h->csr, cur, z, cur, h->d_tpart, h->stream, nullptr, &ch);
     } else {
@@ -145,53 +156,85 @@ int trl_set_poly(lz_handle h, TrlPoly::Kind kind, int degree, const double* coef
   return LZ_OK;
 }
 
+// The basis of m + b rows (b = 1: lz_trl_begin; b >= 2: the band form), its work vectors and small arrays: allocated when m, b or the
+// row length changed, zeroed always.
+int trl_alloc(lz_handle h, int m, int b, const char* who) {
+  const std::string w(who);
+  if (h->kind == 0) return fail(h, LZ_ERR_STATE, w + ": no matrix set");
+  if (h->world > 1 || h->comm_kind != 0)
+    return fail(h, LZ_ERR_STATE, w + ": the thick-restart solver runs on one rank (this handle has a communicator)");
+  if (h->flags & (LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE))
+    return fail(h, LZ_ERR_STATE, w + ": not with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE");
+  if (b == 1 && (m < 2 || m > 128 || m > h->rows)) return fail(h, LZ_ERR_ARG, w + ": need 2 <= m <= min(128, rows)");
+  if (b > 1 && (m < b || m > 128 || m + b > h->rows)) return fail(h, LZ_ERR_ARG, w + ": need b <= m <= min(128, rows - b)");
+  LZ_HIP(h, hipSetDevice(h->dev));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  const int64_t ld = skew_stride(h, h->rows_pad);
+  const size_t nrows = (size_t)(m + b);
+  if (!h->d_trl || h->trl_m != m || h->trl_b != b || h->trl_ld != ld) {
+    h->poly.clear();  // its work vectors belong to the old row length
+    LZ_TRY(dev_alloc(h, h->d_trl, nrows * (size_t)ld));
+    LZ_TRY(dev_alloc(h, h->d_tw, (size_t)ld));
+    if (b > 1)
+      LZ_TRY(dev_alloc(h, h->d_tW, (size_t)b * (size_t)ld));
+    else
+      LZ_TRY(dev_free(h, h->d_tW));
+    LZ_TRY(dev_alloc(h, h->d_tsm, (size_t)trl_small_layout(m, b).total));
+    LZ_TRY(dev_alloc(h, h->d_tgate, 4));
+    h->trl_m = m;
+    h->trl_b = b;
+    h->trl_ld = ld;
+  }
+  const QtwPlan plan = trl_plan(h);
+  size_t need = (size_t)(m + b + 1 + 32) * (size_t)plan.P;
+  need = std::max<size_t>(need, (size_t)trl_cgs_blocks(h->rows_pad));
+  need = std::max<size_t>(need, (size_t)h->rows / 4 + 64);  // dense GEMV / scalar SpMV partials
+  need = std::max<size_t>(need, (size_t)h->csr.n_rowblk + 64);
+  if (h->csr.pb) need = std::max<size_t>(need, (size_t)pb_num_partials(h->csr.pb) + 64);
+  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64);  // residual norms
+  if (b > 1) {  // the block Gram-Schmidt's coefficient runs and squared-norm partials
+    need = std::max<size_t>(need, (size_t)trl_band_dots_blocks(h->rows_pad, b) * (size_t)trl_band_run(m + b, b));
+    need = std::max<size_t>(need, (size_t)b * (size_t)trl_band_update_blocks(h->rows_pad));
+  }
+  need += 8192;
+  if (need > h->tpart_cap) {
+    LZ_TRY(dev_alloc(h, h->d_tpart, need));
+    h->tpart_cap = need;
+  }
+  LZ_HIP(h, hipMemsetAsync(h->d_trl, 0, nrows * (size_t)ld * sizeof(double), h->stream));
+  if (b > 1) LZ_HIP(h, hipMemsetAsync(h->d_tW, 0, (size_t)b * (size_t)ld * sizeof(double), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->d_tsm, 0, (size_t)trl_small_layout(m, b).total * sizeof(double), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->d_tgate, 0, 4 * sizeof(int), h->stream));
+  return LZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int lz_trl_begin(lz_handle h, int m, const double* v0) {
   if (!h || !v0) return LZ_ERR_ARG;
-  if (h->kind == 0) return fail(h, LZ_ERR_STATE, "lz_trl_begin: no matrix set");
-  if (h->world > 1 || h->comm_kind != 0)
-    return fail(h, LZ_ERR_STATE, "lz_trl_begin: the thick-restart solver runs on one rank (this handle has a communicator)");
-  if (h->flags & (LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE))
-    return fail(h, LZ_ERR_STATE, "lz_trl_begin: not with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE");
-  if (m < 2 || m > 128 || m > h->rows) return fail(h, LZ_ERR_ARG, "lz_trl_begin: need 2 <= m <= min(128, rows)");
-  LZ_HIP(h, hipSetDevice(h->dev));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  const int64_t ld = skew_stride(h, h->rows_pad);
-  if (!h->d_trl || h->trl_m != m || h->trl_ld != ld) {
-    h->poly.clear();  // its work vectors belong to the old row length
-    LZ_TRY(dev_alloc(h, h->d_trl, (size_t)(m + 1) * (size_t)ld));
-    LZ_TRY(dev_alloc(h, h->d_tw, (size_t)ld));
-    LZ_TRY(dev_alloc(h, h->d_tsm, (size_t)trl_small_layout(m).total));
-    LZ_TRY(dev_alloc(h, h->d_tgate, 4));
-    h->trl_m = m;
-    h->trl_ld = ld;
-  }
-  const QtwPlan plan = trl_plan(h);
-  size_t need = (size_t)(m + 2 + 32) * (size_t)plan.P;
-  need = std::max<size_t>(need, (size_t)trl_cgs_blocks(h->rows_pad));
-  need = std::max<size_t>(need, (size_t)h->rows / 4 + 64);  // dense GEMV / scalar SpMV partials
-  need = std::max<size_t>(need, (size_t)h->csr.n_rowblk + 64);
-  if (h->csr.pb) need = std::max<size_t>(need, (size_t)pb_num_partials(h->csr.pb) + 64);
-  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64);  // residual norms
-  need += 8192;
-  if (need > h->tpart_cap) {
-    LZ_TRY(dev_alloc(h, h->d_tpart, need));
-    h->tpart_cap = need;
-  }
-  LZ_HIP(h, hipMemsetAsync(h->d_trl, 0, (size_t)(m + 1) * (size_t)ld * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_tsm, 0, (size_t)trl_small_layout(m).total * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_tgate, 0, 4 * sizeof(int), h->stream));
+  LZ_TRY(trl_alloc(h, m, 1, "lz_trl_begin"));
   LZ_TRY(trl_upload_x(h, v0));
   return trl_orth_store(h, 0);
 }
 
+int lz_trl_begin_band(lz_handle h, int m, int b, const double* X) {
+  if (!h || !X) return LZ_ERR_ARG;
+  if (b < 2 || b > 8) return fail(h, LZ_ERR_ARG, "lz_trl_begin_band: need 2 <= b <= 8");
+  LZ_TRY(trl_alloc(h, m, b, "lz_trl_begin_band"));
+  for (int i = 0; i < b; ++i) {
+    LZ_TRY(trl_upload_x(h, X + (int64_t)i * h->rows));
+    LZ_TRY(trl_orth_store(h, i));
+  }
+  return LZ_OK;
+}
+
 int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out) {
   LZ_TRY(trl_state(h, "lz_trl_extend"));
+  if (h->trl_b != 1) return fail(h, LZ_ERR_STATE, "lz_trl_extend: the basis was begun as a band (lz_trl_extend_band)");
   if (m != h->trl_m || k < 0 || k >= m) return fail(h, LZ_ERR_ARG, "lz_trl_extend: need m == the m of lz_trl_begin and 0 <= k < m");
-  const TrlSmall L = trl_small_layout(m);
+  const TrlSmall L = trl_small_layout(h);
   double* V = h->d_trl;
   double* sm = h->d_tsm;
   const int64_t ld = h->trl_ld;
@@ -200,7 +243,7 @@ int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out)
   QtwFuse gated;
   gated.gate = h->d_tgate;
   for (int j = k; j < m; ++j) {
-    trl_apply_op(h, V + (int64_t)j * ld);  // w = A V[j], or p(A) V[j] with a filter set
+    trl_apply_op(h, V + (int64_t)j * ld, h->d_tw);  // w = A V[j], or p(A) V[j] with a filter set
     // pass 1: c = V[0..j] . w (row j + 1 is the self slot: c[j + 1] = w.w), w -= sum c_i V_i
     LZ_HIP(h, launch_qtw(V, ld, h->rows_pad, j + 2, j + 1, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
     launch_final_rows(h->d_tpart, j + 2, plan.P, sm + L.c1, h->stream, plan.family == 2);
@@ -221,12 +264,74 @@ int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out)
   return LZ_OK;
 }
 
+int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta_out) {
+  LZ_TRY(trl_state(h, "lz_trl_extend_band"));
+  if (h->trl_b < 2) return fail(h, LZ_ERR_STATE, "lz_trl_extend_band: the basis was begun without a band (lz_trl_begin_band first)");
+  if (m != h->trl_m || k < 0 || k >= m) return fail(h, LZ_ERR_ARG, "lz_trl_extend_band: need m == the m of lz_trl_begin_band and 0 <= k < m");
+  const int b = h->trl_b;
+  const TrlSmall L = trl_small_layout(h);
+  double* V = h->d_trl;
+  double* W = h->d_tW;
+  double* sm = h->d_tsm;
+  const int64_t ld = h->trl_ld;
+  const QtwPlan plan = trl_plan(h);
+  // the sweeps stream rows_pad, the products write rows: a breakdown in an earlier call (0 / 0 behind a vanished residual) may have left
+  // NaN in a work vector's padding, which no product would clear
+  if (h->rows_pad > h->rows)
+    for (int i = 0; i < b; ++i)
+      LZ_HIP(h, hipMemsetAsync(W + (int64_t)i * ld + h->rows, 0, (size_t)(h->rows_pad - h->rows) * sizeof(double), h->stream));
+  for (int j = k; j < m; j += b) {
+    const int nb = std::min(b, m - j);  // steps j .. j + nb - 1: they need rows below r0 only, which all exist
+    const int r0 = j + b;
+    for (int i = 0; i < nb; ++i) trl_apply_op(h, V + (int64_t)(j + i) * ld, W + (int64_t)i * ld);  // w_i = A V[j + i], or p(A) V[j + i]
+    // block CGS against V[0..r0), two passes: every row is read once per sweep for all b work vectors (a short last batch sweeps the stale
+    // ones too: their coefficients are never read)
+    const int G = trl_band_dots_blocks(h->rows_pad, b);
+    const int run = trl_band_run(r0, b);
+    int nu = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+      double* C = sm + (pass == 0 ? L.C1 : L.C2);
+      LZ_HIP(h, launch_trl_band_dots(V, ld, h->rows_pad, r0, W, ld, b, h->d_tpart, h->stream));
+      launch_final_rows_t(h->d_tpart, G, run, r0 * b, C, h->stream);
+      nu = launch_trl_band_update(V, ld, h->rows_pad, r0, C, W, ld, b, h->d_tpart, h->stream);
+    }
+    launch_final_rows(h->d_tpart, b, nu, sm + L.nrmb, h->stream);  // |w_i|^2 after the second pass
+    launch_trl_band_proj(sm + L.C1, sm + L.C2, r0, b, nb, sm + L.proj + (int64_t)j * L.ldf, L.ldf, h->stream);
+    // in-batch tail: w_i against the rows this batch has made so far (the single-vector kernels, based at row r0), then V[r0 + i] = w_i / |w_i|
+    double* Vn = V + (int64_t)r0 * ld;
+    for (int i = 0; i < nb; ++i) {
+      double* w = W + (int64_t)i * ld;
+      const double* nrm2 = sm + L.nrmb;  // i == 0: nothing new to orthogonalise against, the sweep's own norm
+      if (i > 0) {
+        double* proj = sm + L.proj + (int64_t)(j + i) * L.ldf + r0;
+        for (int pass = 0; pass < 2; ++pass) {
+          double* c = sm + (pass == 0 ? L.c1 : L.c2);
+          LZ_HIP(h, launch_qtw(Vn, ld, h->rows_pad, i + 1, i, w, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
+          launch_final_rows(h->d_tpart, i + 1, plan.P, c, h->stream, plan.family == 2);
+          const int np = launch_trl_cgs(Vn, ld, h->rows_pad, i, c, w, h->d_tpart, nullptr, h->stream);
+          launch_trl_post(pass, h->d_tpart, np, c, i - 1, sm + L.nrm2, proj, h->d_tgate, 1, h->stream);  // (force: the gate is set, both passes run)
+        }
+        nrm2 = sm + L.nrm2;
+      }
+      launch_scale_store(Vn + (int64_t)i * ld, w, nrm2, sm + L.beta + j + i, h->rows_pad, h->stream);
+    }
+    LZ_TRY(check_launch(h, "trl extend band"));
+  }
+  if (proj_out) LZ_HIP(h, hipMemcpyAsync(proj_out, sm + L.proj, (size_t)m * L.ldf * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (beta_out) LZ_HIP(h, hipMemcpyAsync(beta_out, sm + L.beta, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
+}
+
 int lz_trl_restart(lz_handle h, int m, int kk, const double* S) {
   LZ_TRY(trl_state(h, "lz_trl_restart"));
   if (!S || m != h->trl_m || kk < 1 || kk >= m) return fail(h, LZ_ERR_ARG, "lz_trl_restart: need m == the m of lz_trl_begin, 1 <= kk < m, S");
-  const TrlSmall L = trl_small_layout(m);
+  const TrlSmall L = trl_small_layout(h);
   LZ_TRY(upload(h, h->d_tsm + L.S, S, (size_t)m * kk * sizeof(double)));
   LZ_HIP(h, launch_trl_restart(h->d_trl, h->trl_ld, h->rows, m, kk, h->d_tsm + L.S, h->stream));
+  for (int r = 1; r < h->trl_b; ++r)  // band: the other residual rows follow V[m] (ascending: a destination is never a source still to be copied)
+    LZ_HIP(h, hipMemcpyAsync(h->d_trl + (int64_t)(kk + r) * h->trl_ld, h->d_trl + (int64_t)(m + r) * h->trl_ld, (size_t)h->rows * sizeof(double),
+                             hipMemcpyDeviceToDevice, h->stream));
   LZ_TRY(check_launch(h, "trl restart"));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   return LZ_OK;
@@ -234,7 +339,7 @@ int lz_trl_restart(lz_handle h, int m, int kk, const double* S) {
 
 int lz_trl_probe(lz_handle h, int k, const double* x) {
   LZ_TRY(trl_state(h, "lz_trl_probe"));
-  if (!x || k < 0 || k > h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_probe: need 0 <= k <= m and x");
+  if (!x || k < 0 || k > h->trl_m + h->trl_b - 1) return fail(h, LZ_ERR_ARG, "lz_trl_probe: need 0 <= k <= m (band: m + b - 1) and x");
   LZ_TRY(trl_upload_x(h, x));
   return trl_orth_store(h, k);
 }
@@ -256,7 +361,7 @@ int lz_trl_get_vectors(lz_handle h, int k, double* Y_out) {
 int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
   LZ_TRY(trl_state(h, "lz_trl_residuals"));
   if (!theta || !out || k < 1 || k > h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_residuals: need 1 <= k <= m, theta and out");
-  const TrlSmall L = trl_small_layout(h->trl_m);
+  const TrlSmall L = trl_small_layout(h);
   double* dth = h->d_tsm + L.theta;
   LZ_TRY(upload(h, dth, theta, (size_t)k * sizeof(double)));
   int G = 0;
@@ -297,7 +402,7 @@ int lz_trl_filter_apply(lz_handle h, const double* x, double* y) {
     return fail(h, LZ_ERR_STATE, "lz_trl_filter_apply: no filter set (lz_trl_set_filter or lz_trl_set_series first)");
   double* vm = h->d_trl + (int64_t)h->trl_m * h->trl_ld;  // the residual row carries x and then the result
   LZ_TRY(upload(h, vm, x, (size_t)h->rows * sizeof(double)));
-  trl_apply_op(h, vm);
+  trl_apply_op(h, vm, h->d_tw);
   LZ_TRY(check_launch(h, "trl filter apply"));
   LZ_HIP(h, hipMemcpyAsync(vm, h->d_tw, (size_t)h->rows_pad * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   LZ_HIP(h, hipMemcpyAsync(y, h->d_tw, (size_t)h->rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -308,7 +413,7 @@ int lz_trl_filter_apply(lz_handle h, const double* x, double* y) {
 int lz_trl_rayleigh(lz_handle h, int k, double* G_out) {
   LZ_TRY(trl_state(h, "lz_trl_rayleigh"));
   if (!G_out || k < 1 || k >= h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_rayleigh: need 1 <= k < m and G_out");
-  const TrlSmall L = trl_small_layout(h->trl_m);
+  const TrlSmall L = trl_small_layout(h);
   double* V = h->d_trl;
   double* G = h->d_tsm + L.S;  // k x k in the restart's S area
   const QtwPlan plan = trl_plan(h);
@@ -326,8 +431,8 @@ int lz_trl_rayleigh(lz_handle h, int k, double* G_out) {
 
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld) {
   LZ_TRY(trl_state(h, "lz_trl_set_rows"));
-  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + 1 || ld < h->rows_pad)
-    return fail(h, LZ_ERR_ARG, "lz_trl_set_rows: need rows j0 .. j0 + count - 1 <= m and ld >= the padded row length");
+  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + h->trl_b || ld < h->rows_pad)
+    return fail(h, LZ_ERR_ARG, "lz_trl_set_rows: need rows j0 .. j0 + count - 1 <= m (band: m + b - 1) and ld >= the padded row length");
   LZ_TRY(upload2d(h, h->d_trl + (int64_t)j0 * h->trl_ld, (size_t)h->trl_ld * sizeof(double), rows, (size_t)ld * sizeof(double),
                   (size_t)h->rows_pad * sizeof(double), (size_t)count));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
@@ -336,8 +441,8 @@ int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t 
 
 int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld) {
   LZ_TRY(trl_state(h, "lz_trl_get_rows"));
-  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + 1 || ld < h->rows_pad)
-    return fail(h, LZ_ERR_ARG, "lz_trl_get_rows: need rows j0 .. j0 + count - 1 <= m and ld >= the padded row length");
+  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + h->trl_b || ld < h->rows_pad)
+    return fail(h, LZ_ERR_ARG, "lz_trl_get_rows: need rows j0 .. j0 + count - 1 <= m (band: m + b - 1) and ld >= the padded row length");
   LZ_HIP(h, hipMemcpy2DAsync(rows, (size_t)ld * sizeof(double), h->d_trl + (int64_t)j0 * h->trl_ld, (size_t)h->trl_ld * sizeof(double),
                              (size_t)h->rows_pad * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));

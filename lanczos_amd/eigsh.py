@@ -1,6 +1,6 @@
 """``eigsh``: converged eigenpairs of a symmetric matrix by thick-restart Lanczos on the GPU.
 
-The Krylov basis (at most ``ncv + 1`` rows) and every pass over it live on the device (``lz_trl_*`` in
+The Krylov basis (at most ``ncv + 1`` rows; ``ncv + b`` in the band form) and every pass over it live on the device (``lz_trl_*`` in
 include/lanczos_hip.h); the host keeps only the ``ncv x ncv`` projected matrix ``T`` and runs the outer loop below.
 
 Thick restart (Wu & Simon, 2000) is what ``scipy.sparse.linalg.eigsh`` does for a symmetric matrix in another form (ARPACK's
@@ -15,6 +15,10 @@ order 1), so the scale here is ``max|theta|``, the norm estimate of the run.
 Probe.  A single-vector Krylov method can miss a copy of a degenerate eigenvalue.  When all wanted pairs have converged, the loop
 locks them, adds one random direction orthogonal to the basis and asks for one more converged pair than before; it stops only
 when the lowest ``k`` wanted values are unchanged between two such rounds.
+
+Band.  ``block_size=b`` runs the loop in Ruhe's band form (``trl_band``): ``b`` start vectors, basis row ``r`` made from ``A V[r - b]``, so
+copies of an eigenvalue up to multiplicity ``b`` appear without a probe and the device orthogonalises ``b`` vectors per walk over the
+basis; the bookkeeping stays that of single rows.
 
 Breakdown.  When a ``beta`` falls below ``10 eps max|theta|`` the Krylov space is invariant: the loop goes on from a fresh random
 vector orthogonal to the basis with a zero coupling instead of dividing by ``beta``.
@@ -45,10 +49,11 @@ def _order(theta, which):
 class NumpyBackend:
     """The calls of the device backend (``lz_trl_*``) in NumPy: what the host tests drive the outer loop with."""
 
-    def __init__(self, A, force_second_pass=False):
+    def __init__(self, A, force_second_pass=False, block_size=None):
         self.A = A
         self.n = A.shape[0]
         self.force = force_second_pass
+        self.block_size = block_size
         self.filter = None
         self.series = None
 
@@ -100,9 +105,33 @@ class NumpyBackend:
             self.V[j + 1] = w / beta[j]
         return proj, beta
 
+    def begin_band(self, m, X):
+        """the band form of ``begin``: ``m + b`` rows, rows ``0..b`` the rows of ``X`` orthonormalised one by one (``probe``)"""
+        X = np.asarray(X, dtype=np.float64)
+        self.V = np.zeros((m + len(X), self.n))
+        for i in range(len(X)):
+            self.probe(i, X[i])
+
+    def extend_band(self, k, m):
+        """the band form of ``extend``: step ``j`` makes row ``j + b`` from ``Op V[j]``, orthogonalised against every row below it by two
+        CGS passes (no gate).  Returns ``proj`` (``m x (m + b)``: row ``j`` holds the coefficients on rows ``0..j+b``) and ``beta`` (``m``)."""
+        b = len(self.V) - m
+        proj = np.zeros((m, m + b))
+        beta = np.zeros(m)
+        for j in range(k, m):
+            w = self._op(self.V[j])
+            w, c = self._cgs(w, j + b - 1)
+            w, c2 = self._cgs(w, j + b - 1)
+            proj[j, : j + b] = c + c2
+            beta[j] = np.linalg.norm(w)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                self.V[j + b] = w / beta[j]
+        return proj, beta
+
     def restart(self, m, kk, S):
+        nb = len(self.V) - m  # 1, or the band width: the residual rows move down behind the kept ones
         self.V[:kk] = S.T @ self.V[:m]
-        self.V[kk] = self.V[m]
+        self.V[kk: kk + nb] = self.V[m: m + nb].copy()
 
     def probe(self, k, x):
         for _ in range(2):
@@ -116,8 +145,8 @@ class NumpyBackend:
         return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
 
 
-def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
-    """SciPy's argument errors, plus this solver's own limits.  Returns ncv."""
+def _check_problem(n, k, which, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
+    """SciPy's argument errors for everything but ``ncv``"""
     if M is not None or sigma is not None or Minv is not None or OPinv is not None:
         raise NotImplementedError("eigsh on the device solves the standard problem only: M, sigma, Minv and OPinv must be None")
     if mode != "normal":
@@ -130,6 +159,11 @@ def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode
         raise ValueError("k must be greater than 0.")
     if k >= n:
         raise TypeError(f"k >= N for an N x N matrix (k={k}, N={n}): reduce k")
+
+
+def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
+    """SciPy's argument errors, plus this solver's own limits.  Returns ncv."""
+    _check_problem(n, k, which, M, sigma, Minv, OPinv, mode)
     if ncv is None:
         ncv = min(n, max(2 * k + 1, 20))
     ncv = min(int(ncv), n)  # (as SciPy does)
@@ -237,6 +271,149 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             else:
                 T[:kk, kk] = T[kk, :kk] = b_last * S[m - 1, keep]
             kcur = kk
+
+
+_MAX_BLOCK = 8  # the widest band the device kernels are built for (lz_trl.hip)
+
+
+def check_block_size(block_size):
+    """``block_size`` as an int; ``ValueError`` unless it is an integer ``2 .. 8``"""
+    if isinstance(block_size, bool) or not isinstance(block_size, (int, np.integer)) or not 2 <= block_size <= _MAX_BLOCK:
+        raise ValueError(f"block_size must be None or an integer 2 <= block_size <= {_MAX_BLOCK}, got {block_size!r}")
+    return int(block_size)
+
+
+def check_band_args(n, k, which, ncv, block_size, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
+    """``check_args`` for the band loop: the same errors for everything but ``ncv``, which must leave ``b`` residual rows behind the
+    basis and ``2 b + 1`` free rows in front of them.  Returns ``(ncv, b)``."""
+    b = check_block_size(block_size)
+    if sigma is not None:
+        raise NotImplementedError("block_size with sigma: the interior mode's certificate is defined for the single-vector loop only")
+    _check_problem(n, k, which, M, sigma, Minv, OPinv, mode)
+    top = min(n - b, _MAX_NCV)
+    if ncv is None:
+        ncv = min(top, max(2 * k + 1, 20, k + 2 * b + 1))
+    ncv = int(ncv)
+    if not k + 2 * b + 1 <= ncv <= top:
+        raise ValueError(f"ncv must be k+2b+1<=ncv<=min(n-b, {_MAX_NCV}) with block_size b={b}, ncv={ncv}: the band restart keeps b residual "
+                         "rows behind the basis and needs b + 1 free rows in front of them, and the probe one more pair")
+    return ncv, b
+
+
+def _start_block(n, b, v0, rng):
+    """the ``b`` start vectors of the band loop: ``v0`` if given, the rest uniform(-1, 1) from the private generator"""
+    X = rng.uniform(-1.0, 1.0, (b, n))
+    if v0 is not None:
+        X[0] = v0
+    return X
+
+
+def trl_band(backend, n, k, which="LM", block_size=2, ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None):
+    """The thick-restart outer loop in Ruhe's band form: ``b = block_size`` start vectors, basis row ``r`` made from ``Op V[r - b]``.
+
+    The basis has ``m + b`` rows (``m = ncv``).  ``F`` (``m x (m + b)``) holds in row ``j`` the coefficients of ``Op V[j]`` on the
+    basis: what ``extend_band`` measured (``F[j, j + b] = beta[j]``) or, for a kept Ritz vector, its value and its couplings to the
+    ``b`` residual rows.  ``T[i, j] = F[j, i]`` (``i <= j``) is the projected matrix, ``Rl[r, jj] = F[m - b + jj, m + r]`` the ``b x b``
+    upper triangle that couples the last ``b`` rows to the residual rows: the residual of Ritz pair ``i`` is exactly
+    ``|Rl S[m-b..m, i]|``.  A copy of an eigenvalue of multiplicity up to ``b`` needs no probe.  A breakdown is still one tiny
+    ``beta`` (``<= 10 eps scale (j + b)``, see below) and one replaced row (deflation is exact: only the deficient direction is replaced, so no part of a residual is
+    hidden from the estimate, which replacing a whole block would do).
+
+    Returns ``(theta, info)`` as ``trl`` does, ``info["block_size"] = b``."""
+    m, b = check_band_args(n, k, which, ncv, block_size)
+    maxiter = n * 10 if maxiter is None else int(maxiter)
+    rng = np.random.default_rng(_SEED) if rng is None else rng
+    tol_eff = float(tol) if tol > 0 else _EPS
+    if v0 is not None:
+        v0 = np.asarray(v0, dtype=np.float64).reshape(-1)
+        if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
+            raise ValueError("v0 must be a non-zero vector of length n")
+    backend.begin_band(m, _start_block(n, b, v0, rng))
+    F = np.zeros((m, m + b))
+    kcur, nw, last = 0, k, None
+    anorm = 0.0
+    info = {"matvecs": 0, "cycles": 0, "probes": 0, "breakdowns": 0, "block_size": b}
+    steps = np.arange(m)
+    while True:
+        j0 = kcur
+        while True:  # one extension of the basis to m + b rows; a breakdown replaces one row and goes on behind it
+            proj, beta = backend.extend_band(j0, m)
+            info["matvecs"] += m - j0
+            F[j0:] = proj[j0:]
+            F[steps[j0:], steps[j0:] + b] = beta[j0:]
+            # the first breakdown: a row behind it is made from a normalised rounding error, so neither it nor any later step of this
+            # extension may enter the scale (the device went on without a synchronisation: those steps hold anything, NaN included)
+            # The bound is 10 eps scale times the j + b rows the step subtracted: a sum of r rounded terms errs by up to r eps of their
+            # size, and that error is what is left of w when the Krylov space has run out.  (10 eps scale alone, the single-vector
+            # loop's bound, lies below the device's rounding from about ten rows on: on diag(1, 2, 3) x 10 with b = 4 steps 16 .. 18
+            # left 7e-16, 2e-15 and 1.3e-14 against 6.7e-15, and the row made of the last one cost all orthogonality.)
+            scale = max(anorm, np.abs(F[:j0]).max()) if j0 else anorm
+            jb = None
+            for j in range(j0, m):
+                scale = max(scale, np.abs(F[j, : j + b]).max())
+                if not beta[j] > 10 * _EPS * scale * (j + b):
+                    jb = j
+                    break
+            if jb is None or jb == m - 1:
+                break
+            info["breakdowns"] += 1
+            F[jb + 1:] = 0.0
+            F[jb, jb + b] = 0.0
+            backend.probe(jb + b, rng.standard_normal(n))
+            j0 = jb + 1
+        info["cycles"] += 1
+        dead = jb is not None  # the last residual vanished: row m + b - 1 is noise, replaced after the restart
+        if dead:
+            F[m - 1, m + b - 1] = 0.0
+        T = np.triu(F[:, :m].T)
+        T = T + np.triu(T, 1).T
+        theta, S = np.linalg.eigh(T)
+        anorm = max(np.abs(theta).max(), anorm)
+        Rl = F[m - b:, m:].T
+        C = Rl @ S[m - b:]  # column i: the coefficients of pair i's residual on the b residual rows
+        res = np.linalg.norm(C, axis=0)
+        order = _order(theta, which)
+        want = order[:nw]
+        ok = res <= tol_eff * anorm
+        done = ok[want].all()
+        if done:
+            top = order[:k]
+            cur = np.sort(theta[top])
+            if not probe or (last is not None and np.abs(cur - last).max() <= 1e3 * tol_eff * anorm):
+                sel = top[np.argsort(theta[top], kind="stable")]
+                backend.restart(m, k, np.ascontiguousarray(S[:, sel]))
+                info["anorm"] = anorm
+                return theta[sel], info
+        if info["cycles"] >= maxiter:
+            conv = sorted((i for i in order[:k] if ok[i]), key=lambda i: theta[i])
+            vecs = np.zeros((n, 0))
+            if conv:
+                backend.restart(m, len(conv), np.ascontiguousarray(S[:, conv]))
+                vecs = backend.get_vectors(len(conv))
+            err = ArpackNoConvergence(f"No convergence ({info['cycles']} iterations, {len(conv)}/{k} eigenvectors converged)",
+                                      theta[conv], vecs)
+            err.info = info
+            raise err
+        if done:  # probe round: lock the wanted pairs, swap the last residual row for a random direction, ask for one pair more
+            last = cur
+            kk, keep = nw, want
+        else:
+            nconv = int(ok[want].sum())
+            kk = min(m - b - 1, nw + max(nconv, (m - nw) // 2))
+            keep = order[:kk]
+        backend.restart(m, kk, np.ascontiguousarray(S[:, keep]))
+        F = np.zeros((m, m + b))
+        F[np.arange(kk), np.arange(kk)] = theta[keep]
+        F[:kk, kk: kk + b] = C[:, keep].T
+        if done:
+            backend.probe(kk + b - 1, rng.standard_normal(n))
+            F[:, kk + b - 1] = 0.0
+            info["probes"] += 1
+            nw = min(nw + 1, m - 2 * b - 1)
+        elif dead:
+            backend.probe(kk + b - 1, rng.standard_normal(n))
+            F[:, kk + b - 1] = 0.0
+        kcur = kk
 
 
 class ChebFilter:
@@ -378,7 +555,7 @@ def filter_plan(theta, S_last, b_last, k, which, degree):
     return ChebFilter(lo, hi, anchor, max(2, min(degree, used)))
 
 
-def trl_filtered(backend, n, k, which, degree, ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None):
+def trl_filtered(backend, n, k, which, degree, ncv=None, maxiter=None, tol=0.0, v0=None, probe=True, rng=None, block_size=None):
     """Thick-restart Lanczos on ``B = p(A)``, ``p`` a Chebyshev filter that damps the unwanted part of the spectrum (Zhou & Saad's
     filtered Lanczos): ``B`` has ``A``'s eigenvectors and its wanted eigenvalues are far better separated, so the loop takes far fewer
     Gram-Schmidt steps at ``degree`` products with ``A`` each.
@@ -389,19 +566,26 @@ def trl_filtered(backend, n, k, which, degree, ncv=None, maxiter=None, tol=0.0, 
     Acceptance is in ``A``-space: a pair whose true residual exceeds ``1e3 tol_eff 1e4 |A|`` (the range cap's error model with the
     loop's factor 1e3) is not returned; ``ArpackNoConvergence`` then carries the pairs that pass.
 
+    ``block_size=b``: stage 0 runs single-vector as without it, then ``trl_band`` runs on ``B`` (``ncv`` follows the band's rule).
+
     Returns ``(theta, info)`` as ``trl`` does; ``info`` has ``"steps"`` (Gram-Schmidt steps, stage 0 included), ``"matvecs"`` (products
     with ``A``: stage 0, ``degree`` per filtered step, Rayleigh-Ritz), ``"filter"`` and ``trl``'s other counts."""
     degree = check_filter_args(which, degree)
-    m = check_args(n, k, which, ncv)
+    m = check_args(n, k, which, ncv) if block_size is None else check_band_args(n, k, which, ncv, block_size)[0]
     rng, tol_eff, v0 = _start(n, tol, v0, rng)
     theta0, s_last, b_last, _ = _stage0(backend, m, v0)
     filt = filter_plan(theta0, s_last, b_last, k, which, degree)
     anorm = max(abs(filt.anchor), abs(filt.hi), abs(filt.lo))
     res_bound = 1e3 * tol_eff * _RANGE_CAP * anorm
     # the loop on B = p(A): the wanted images are positive and the largest, the anchor lies on their side
+    if block_size is not None:  # (a basis of another size drops the device's filter: size it before the filter is set)
+        backend.begin_band(m, _start_block(n, block_size, v0, np.random.default_rng(_SEED)))
     backend.set_filter(filt.coefficients(), filt.c)
     try:
-        _, run = trl(backend, n, k, "LA", ncv=m, maxiter=maxiter, tol=tol, v0=v0, probe=probe, rng=rng)
+        if block_size is None:
+            _, run = trl(backend, n, k, "LA", ncv=m, maxiter=maxiter, tol=tol, v0=v0, probe=probe, rng=rng)
+        else:
+            _, run = trl_band(backend, n, k, "LA", block_size, ncv=m, maxiter=maxiter, tol=tol, v0=v0, probe=probe, rng=rng)
     except ArpackNoConvergence as e:  # its pairs are those of B: hand on what they give for A
         kc = len(e.eigenvalues)
         backend.set_filter(None)
@@ -620,9 +804,10 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
 class DeviceBackend:
     """The ``lz_trl_*`` calls on one ``_capi.Handle`` that already holds the matrix."""
 
-    def __init__(self, handle, n, force_second_pass=False):
+    def __init__(self, handle, n, force_second_pass=False, block_size=None):
         self.h = handle
         self.n = n
+        self.block_size = block_size
         if force_second_pass:
             from ._capi import FLAG_TRL_PASS2_ALWAYS
 
@@ -633,6 +818,12 @@ class DeviceBackend:
 
     def extend(self, k, m):
         return self.h.trl_extend(k, m)
+
+    def begin_band(self, m, X):
+        self.h.trl_begin_band(m, X)
+
+    def extend_band(self, k, m):
+        return self.h.trl_extend_band(k, m)
 
     def restart(self, m, kk, S):
         self.h.trl_restart(m, kk, S)
@@ -677,7 +868,7 @@ def upload_matrix(h, A):
 
 
 def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=None, tol=0, return_eigenvectors=True, Minv=None,
-          OPinv=None, mode="normal", device_id=0, handle=None, info=None, filter_degree=None):
+          OPinv=None, mode="normal", device_id=0, handle=None, info=None, filter_degree=None, block_size=None):
     """Find ``k`` eigenvalues and eigenvectors of the real symmetric matrix ``A`` - ``scipy.sparse.linalg.eigsh``'s signature and
     defaults, solved by thick-restart Lanczos on the GPU.
 
@@ -695,17 +886,29 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
     ``sigma`` with ``which="LM"`` and ``filter_degree``: the ``k`` eigenvalues nearest ``sigma`` (SciPy's meaning, without a
     factorisation; ``sigma=0.0`` is the interior form of ``"SM"``), ascending, by Lanczos on a Chebyshev series of ``A`` that peaks at
     ``sigma`` (``trl_interior``); the result is certified complete or ``ArpackNoConvergence`` is raised.  ``ncv`` then counts against
-    ``k + max(4, k // 4)`` pairs."""
+    ``k + max(4, k // 4)`` pairs.
+    ``block_size`` (an integer ``2 .. 8``; default None: the single-vector loop): band Lanczos with that many start vectors
+    (``trl_band``) - every copy of an eigenvalue of multiplicity up to ``block_size`` is found without the probe's help, and the device
+    orthogonalises ``block_size`` new vectors in one walk over the basis.  ``ncv`` (default ``min(n - b, 128, max(2k + 1, 20, k + 2b + 1))``)
+    must then satisfy ``k + 2b + 1 <= ncv <= min(n - b, 128)``.  Combines with ``which`` and with ``filter_degree``; with ``sigma`` it
+    raises ``NotImplementedError``."""
     from . import _capi
 
     n = int(A.shape[0])
     if len(A.shape) != 2 or A.shape[1] != n:
         raise ValueError(f"expected square matrix (shape={A.shape})")
+    if block_size is not None:
+        check_block_size(block_size)
+        if sigma is not None:
+            raise NotImplementedError("block_size with sigma: the interior mode's certificate is defined for the single-vector loop only")
     interior = check_interior_args(which, sigma, filter_degree) if M is None and Minv is None and OPinv is None else None
     if interior is not None:
         check_args(n, k, which, None, M, None, Minv, OPinv, mode)  # (ncv is measured against the k + extra pairs of trl_interior)
     else:
-        check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+        if block_size is None:
+            check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+        else:
+            check_band_args(n, k, which, ncv, block_size, M, sigma, Minv, OPinv, mode)
         if filter_degree is not None:
             check_filter_args(which, filter_degree)
     h = handle if handle is not None else _capi.Handle(device_id)
@@ -713,10 +916,14 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
         upload_matrix(h, A)
         if interior is not None:
             theta, run = trl_interior(DeviceBackend(h, n), n, k, interior[0], interior[1], ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
-        elif filter_degree is None:
+        elif filter_degree is None and block_size is None:
             theta, run = trl(DeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+        elif filter_degree is None:
+            theta, run = trl_band(DeviceBackend(h, n, block_size=block_size), n, k, which, block_size, ncv=ncv, maxiter=maxiter, tol=tol,
+                                  v0=v0)
         else:
-            theta, run = trl_filtered(DeviceBackend(h, n), n, k, which, filter_degree, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+            theta, run = trl_filtered(DeviceBackend(h, n, block_size=block_size), n, k, which, filter_degree, ncv=ncv, maxiter=maxiter,
+                                      tol=tol, v0=v0, block_size=block_size)
         if info is not None:
             info.update(run)
             info["residuals"] = h.trl_residuals(k, theta)

@@ -9,6 +9,10 @@ gate next to the fixed-n loop's step, and one eigsh run on the device-assembled 
                                                 the series step fused into the SpMV against SpMV + k_cheb_series_step, and the
                                                 eigenvalues nearest zero filtered against the unfiltered which="SM"
                                                 (the record is profiles/r09/trl_series_probe.json)
+    python tools/trl_probe.py --band [--out FILE]     band Lanczos (eigsh(block_size=b)): one batch of lz_trl_extend_band against b
+                                                single-vector steps of lz_trl_extend at the same basis size, and block_size
+                                                None / 2 / 4 solves with and without the filter
+                                                (the record is profiles/r10/trl_band_probe.json)
 
 Times are host wall clock around calls that end in a stream synchronisation, median of several repetitions: a call's fixed cost
 (~20 us: upload of S, launch, synchronisation) is included."""
@@ -22,7 +26,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from lanczos_amd import Hamiltonian, _capi, synthetic  # noqa: E402
-from lanczos_amd.eigsh import ChebFilter, DeviceBackend, SeriesFilter, trl, trl_filtered, trl_interior, upload_matrix  # noqa: E402
+from lanczos_amd.eigsh import ChebFilter, DeviceBackend, SeriesFilter, trl, trl_band, trl_filtered, trl_interior, upload_matrix  # noqa: E402
 
 HBM_PEAK = 8.0e12  # MI355X HBM3E, bytes/s
 
@@ -247,6 +251,106 @@ def series_probe(a):
         save()
 
 
+def band_batch_rates(H, r0=36, reps=9):
+    """One batch of b band steps (rows r0 .. r0 + b - 1 made from b products, four block sweeps over r0 rows and the in-batch tail) against
+    b steps of the single-vector lz_trl_extend whose Gram-Schmidt sees r0 - b/2 + 1 .. r0 + b/2 rows, on two handles that hold the same
+    matrix, arms interleaved.  Byte model: a sweep over r rows for c vectors moves (r + c) rows_pad 8 bytes, an update writes c more;
+    the band batch is four sweeps (r0 rows, b vectors), the single-vector step four sweeps (j + 1 rows, one vector), second pass included
+    (the gate "trips on nearly every step")."""
+    out = []
+    hs, hb = _capi.Handle(0), _capi.Handle(0)
+    hs.set_options(_capi.FLAG_TRL_PASS2_ALWAYS)
+    for h in (hs, hb):
+        M = upload_matrix(h, H)
+    pad = hs.padded_rows(M)
+    rng = np.random.default_rng(5)
+    for b in (2, 4, 8):
+        ms = r0 + b // 2
+        hs.trl_begin(ms, rng.standard_normal(M))
+        hs.trl_extend(0, ms)
+        hb.trl_begin_band(r0, rng.standard_normal((b, M)))
+        hb.trl_extend_band(0, r0)
+        tb, ts = [], []
+        for rep in range(reps + 2):  # two warm-up rounds
+            t = time.perf_counter()
+            hb.trl_extend_band(r0 - b, r0)
+            t1 = time.perf_counter()
+            hs.trl_extend(ms - b, ms)
+            t2 = time.perf_counter()
+            if rep >= 2:
+                tb.append(t1 - t)
+                ts.append(t2 - t1)
+        tb, ts = float(np.median(tb)), float(np.median(ts))
+        bytes_band = (4 * (r0 + b) + 2 * b) * pad * 8.0
+        bytes_single = sum(4 * (j + 2) + 2 for j in range(ms - b, ms)) * pad * 8.0
+        out.append({"b": b, "rows": M, "r0": r0, "single_rows": f"{ms - b + 1}..{ms}", "reps": reps,
+                    "band_us_per_row": tb / b * 1e6, "single_us_per_row": ts / b * 1e6, "single_over_band": ts / tb,
+                    "band_model_bytes": bytes_band, "single_model_bytes": bytes_single, "model_bytes_ratio": bytes_single / bytes_band,
+                    "band_frac_hbm_peak": bytes_band / tb / HBM_PEAK, "single_frac_hbm_peak": bytes_single / ts / HBM_PEAK})
+        print(json.dumps(out[-1]), flush=True)
+    hs.close()
+    hb.close()
+    return out
+
+
+def solve_band(A, label, k, ncv=None, maxiter=None):
+    """eigsh(k, 'SA') at block_size None / 2 / 4, without and with filter_degree = 16, on one handle in this order; a run that does not
+    converge within maxiter cycles is recorded as such"""
+    from scipy.sparse.linalg import ArpackNoConvergence
+
+    h = _capi.Handle(0)
+    n = upload_matrix(h, A)
+    v0 = np.random.default_rng(3).standard_normal(n)
+    runs = []
+    for d in (None, 16):
+        for b in (None, 2, 4):
+            be = DeviceBackend(h, n, block_size=b)
+            t = time.perf_counter()
+            try:
+                if d is not None:
+                    theta, info = trl_filtered(be, n, k, "SA", d, ncv=ncv, v0=v0, maxiter=maxiter, block_size=b)
+                elif b is None:
+                    theta, info = trl(be, n, k, "SA", ncv=ncv, v0=v0, maxiter=maxiter)
+                else:
+                    theta, info = trl_band(be, n, k, "SA", b, ncv=ncv, v0=v0, maxiter=maxiter)
+            except ArpackNoConvergence as e:
+                runs.append({"block_size": b, "filter_degree": d, "converged": False, "wall_s": time.perf_counter() - t, "note": str(e)})
+                print(json.dumps(runs[-1]), flush=True)
+                continue
+            wall = time.perf_counter() - t
+            res = h.trl_residuals(k, theta)
+            runs.append({"block_size": b, "filter_degree": d, "converged": True, "steps": info.get("steps", info["matvecs"]),
+                         "A_products": info["matvecs"], "cycles": info["cycles"], "probes": info["probes"], "breakdowns": info["breakdowns"],
+                         "wall_s": wall, "theta": theta.tolist(), "max_residual_over_anorm": float(res.max() / info["anorm"])})
+            print(json.dumps(runs[-1]), flush=True)
+    h.close()
+    return {"matrix": label, "rows": n, "k": k, "which": "SA", "ncv": ncv or "default", "maxiter": maxiter, "runs": runs}
+
+
+def band_probe(a):
+    out = {}
+
+    def save():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+    Hamiltonian.verbose = False
+    if a.no_batch and a.out and os.path.exists(a.out):  # keep the batch record of an earlier run
+        with open(a.out) as f:
+            out.update(json.load(f))
+    if not a.no_batch:
+        H = synthetic.laplacian_2d_5pt(4000, a.rows // 4000)
+        out["batch_lap2d"] = band_batch_rates(H)
+        save()
+    N = a.deuteron_n
+    op = deuteron(N)
+    for ncv in (None, 40):  # the default, and room for the band (see trl_band)
+        out[f"solve_deuteron_ncv{ncv or 'default'}"] = solve_band(op, f"deuteron 27-point N={N}", 4, ncv=ncv, maxiter=a.band_maxiter)
+        save()
+
+
 def filter_trace(a):
     """A short run for `rocprofv3 --kernel-trace --stats -- python tools/trl_probe.py --filter-trace`: ten degree-16 filter applications
     on each arm and matrix, so that the trace's per-kernel averages give k_cheb_step, the plain SpMV and the fused SpMV step."""
@@ -274,6 +378,9 @@ def main():
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--filter", action="store_true", help="probe the Chebyshev filter instead (see the module docstring)")
     ap.add_argument("--series", action="store_true", help="probe the Chebyshev series of the interior mode instead (see the module docstring)")
+    ap.add_argument("--band", action="store_true", help="probe band Lanczos (eigsh(block_size=...)) instead (see the module docstring)")
+    ap.add_argument("--no-batch", action="store_true", help="--band: the solves only (the batch record in --out is kept)")
+    ap.add_argument("--band-maxiter", type=int, default=3000, help="--band: restart cycles allowed to each solve")
     ap.add_argument("--solve-n", type=int, default=48, help="--series: a second, smaller deuteron grid for the solves")
     ap.add_argument("--solve-maxiter", type=int, default=4000, help="--series: restart cycles allowed to each solve on the smaller grid")
     ap.add_argument("--filter-trace", action="store_true", help="the short run meant for a kernel trace (see filter_trace)")
@@ -287,6 +394,8 @@ def main():
         return filter_probe(a)
     if a.series:
         return series_probe(a)
+    if a.band:
+        return band_probe(a)
     out = {}
     M = a.rows
     H = synthetic.laplacian_2d_5pt(4000, M // 4000)  # the headline's matrix family at M = 1e7
