@@ -134,7 +134,9 @@ int lz_set_options(lz_handle h, int flags);
  *   14  irregular SpMV plan (0 auto: the column-blocked two-phase kernels for matrices without column locality, 1 never, 2 always)
  *   15  loop structure (0 auto: three launches per step for small problems, five up to 4e6 rows per rank, above that on one rank
  *       the one-sweep loop - one walk over the basis per step, lz_last_engine 9 -, else six; 1 six always; 6 the one-sweep loop
- *       at any size (one rank, fused-norm full re-orthogonalisation, default kernels, n <= 1536))
+ *       at any size (one rank, fused-norm full re-orthogonalisation, default kernels, n <= 1536) - its fused form (no three-term
+ *       pass, lz_last_one_sweep_fused) where the matrix has a scale-on-read SpMV, as the automatic choice does; 7 the one-sweep
+ *       loop at any size with the separate three-term kernel always (A/B, tests))
  *   16  rows per chunk of the CHUNKED Ritz mode (0 auto: chunked only when Y does not fit beside the basis; > 0 forces it: tests)
  *   11  two-sided Gram-Schmidt links (0 / 1: streaming kernel + fold kernel per link)
  *   17  fixed-K (stencil) SpMV layout: 0 auto (CSR-order kernel with products staged through LDS; the ELL-ordered second copy -
@@ -370,8 +372,13 @@ int lz_last_engine(lz_handle h, int* engine);
 /* One-sweep loop (lz_last_engine 9): the steps of the last lz_run whose predicted coefficients missed the measured ones by more
  * than the gate (1e-14 in units of the new vector) and that therefore ran the correcting sweep; 0 after any other loop. */
 int lz_last_gate_trips(lz_handle h, int* trips);
-/* Host evaluation of the one-sweep loop's per-step arithmetic (the device kernels' expressions and order), for checks
- * without a GPU.  G (symmetric) and H are n x n with column i at [i * n].  predict: chat[0..j] of step j + 1 from alpha_j, the
+/* One-sweep loop: 1 when the last lz_run took the fused form - one rank, 5 or 7 entries per row in the ELL-ordered copy, n <= 1520:
+ * the sweep forms w_j = (A v_{j-1} - alpha v_{j-1}) - beta v_{j-2} itself and works in the units of w, the SpMV divides by beta_j on
+ * read and stores V[j]; no three-term kernel runs inside the loop.  0 for the unfused form (27-point rows, two-phase or dense
+ * SpMV, lz_set_tuning(h, 15, 7)) and after any other loop.  Both forms report lz_last_engine 9. */
+int lz_last_one_sweep_fused(lz_handle h, int* fused);
+/* Host evaluation of the one-sweep loop's per-step arithmetic (the device kernels' expressions, summed in index order; the
+ * kernels add the same terms lane-strided through a fixed shuffle tree), for checks without a GPU.  G (symmetric) and H are n x n with column i at [i * n].  predict: chat[0..j] of step j + 1 from alpha_j, the
  * norm beta_j that formed v_j and nrm2 = ||w_{j+1}||^2.  post: col[0..j) = G[:j, j] of the v_j formed with chat from the
  * measured dots d[i] = V_i . u_j, nrm2 = ||w_j||^2. */
 int lz_one_sweep_host_predict(int n, int j, const double* H, const double* G, double alpha_j, double beta_j, double nrm2, double* chat);

@@ -48,7 +48,7 @@ TUNE_BI_LINKS = 11          # two-sided Gram-Schmidt links
 TUNE_NO_SKEW = 12           # 1 = no row-stride skew
 TUNE_POISON_BASIS = 13      # 1 = NaN-poison a fresh basis allocation (test knob)
 TUNE_SPMV_PLAN = 14         # irregular SpMV plan (0 auto, 1 never two-phase, 2 always)
-TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size)
+TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size, 7 the same, never fused)
 TUNE_RITZ_CHUNK_ROWS = 16   # rows per chunk of the chunked Ritz mode (> 0 forces it)
 TUNE_FIXED_LAYOUT = 17      # fixed-K SpMV layout (0 auto: row-class coded ELL where the rows fall into classes, else CSR order and ELL only in the partial loop;
                             # 1 never ELL; 2 / 3 uncoded ELL always, one / two rows per lane; 4 offsets-only coding)
@@ -139,6 +139,7 @@ SIGNATURES = {
     "lz_comm_counts": (C.c_int, [_P, _I64, _I64]),
     "lz_last_engine": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_last_gate_trips": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_one_sweep_fused": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_one_sweep_host_predict": (C.c_int, [C.c_int, C.c_int, _D, _D, C.c_double, C.c_double, C.c_double, _D]),
     "lz_one_sweep_host_post": (C.c_int, [C.c_int, C.c_int, _D, _D, _D, C.c_double, _D]),
     "lz_last_host_syncs": (C.c_int, [_P, _I64]),
@@ -665,6 +666,12 @@ class Handle:
         """one-sweep loop: steps of the last run whose predicted coefficients missed by more than the gate (they ran a correcting sweep)"""
         k = C.c_int()
         self.check(self.lib.lz_last_gate_trips(self._h, C.byref(k)))
+        return k.value
+
+    def last_one_sweep_fused(self):
+        """one-sweep loop: 1 when the last run took the fused form (no three-term pass; the SpMV divides by beta on read), else 0"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_one_sweep_fused(self._h, C.byref(k)))
         return k.value
 
     def last_host_syncs(self):

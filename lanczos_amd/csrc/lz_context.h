@@ -158,6 +158,7 @@ struct lz_context {
   int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run
   int os_n = 0;
   int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
+  int last_os_fused = 0;       // one-sweep loop: 1 = the last lz_run took the fused form (no three-term pass)
   double* d_om = nullptr;      // device-resident partial re-orthogonalisation: omega-recurrence state (omega_state_doubles)
   int* d_omi = nullptr;        //   ... gate of the coming step, sweep count, per-step sweep log (omega_state_ints)
   int om_n = 0;
@@ -269,7 +270,7 @@ double spmv_bytes(lz_handle h, bool ell = false);  // ell: the launch takes the 
 double spmv_flops(lz_handle h);
 int step_spmv(lz_handle h, int j, double* alpha_dst = nullptr, bool reduce = true, int* np_out = nullptr);
 int step_reorth(lz_handle h, int j, int nrows, bool scale, int beta_idx, bool in_run_loop = false);
-int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm = true);
+int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm = true, int* np_out = nullptr);
 size_t fused_coff(lz_handle h);
 size_t onered_part_off(lz_handle h);
 int breakdown_status(lz_handle h, int n, const double* alpha_out, const double* beta_out);

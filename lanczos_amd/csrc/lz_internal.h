@@ -207,6 +207,7 @@ void launch_scale_store(double* vj, const double* r, const double* nrm2, double*
 // arithmetic below is shared by the kernels and the host check (lz_one_sweep_host, tools/one_sweep_prototype.py).
 constexpr double kOneSweepTau = 1e-14;  // gate: max |e| above this runs one correcting sweep (profiles/one_sweep_prototype.md)
 constexpr int kOneSweepMaxN = 1536;     // the sweep parks 4 x qtw_ldp(n) per-wave dots in LDS (48 KiB)
+constexpr int kOneSweepFusedMaxN = kOneSweepMaxN - 16;  // the fused form parks one slot more per wave (qtw_ldp(n + 1))
 // c_hat_i of step j + 1 (i <= j): ((A V_i) . v_j - alpha_j G[i, j] - beta_j G[i, j-1]) / sqrt(nrm2)
 __host__ __device__ inline double os_predict_one(int i, int j, int n, const double* H, const double* G, double a, double bj, double bn) {
   double s;
@@ -228,18 +229,24 @@ __host__ __device__ inline double os_post_one(int i, int j, int n, const double*
 }
 // sweep (mode 0): V[j] = 2 u - (sum_{i<j} coef_i V_i + cs u), u = r / sqrt(nrm2) (beta stored to beta_slot); part[b * ldp + i] =
 // block b's share of V_i . u (i < j) and, at i = j, of V[j] . V[j] (ldp = qtw_ldp(j + 1)).  Mode 1 (correction, runs only when
-// gate[0] != 0): V[j] -= sum_{i<j} coef_i V_i, no dots.  Returns the number of blocks (the partial runs).
+// gate[0] != 0): dst -= sum_{i<j} coef_i V_i, no dots.  Mode 2 (the fused form, j >= 1; r = y = A v_{j-1}): the sweep forms
+// w = (y - alpha_prev V[j-1]) - beta_prev V[j-2] itself (k_three_term's expression; no beta term at j = 1) and works in the units of w:
+// dst = u~ = 2 w - (sum_{i<j} coef_i V_i + w), coef the un-normalised predictions; part[b * ldp + i] = V_i . w (i < j), u~ . u~ (i = j),
+// ||w||^2 (i = j + 1), ldp = qtw_ldp(j + 2).  dst == nullptr: V[j].  Returns the number of blocks (the partial runs).
 int os_sweep_blocks(int64_t len);
 int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const double* coef, const double* r, const double* nrm2,
-                    double* beta_slot, double* part, const int* gate, hipStream_t s);
+                    double* beta_slot, double* part, const int* gate, hipStream_t s, double* dst = nullptr, const double* alpha_prev = nullptr,
+                    const double* beta_prev = nullptr);
 // post (one block): d = [V_i . u_j (i < j), v_j . v_j] (the second-stage sums); writes G[:, j] / G[j, :], H[:, j-1]'s update
 // part, and when max |e| > tau the correction g (= G[:j, j]) with the corrected column; ist[0] = gate, ist[1] += trips,
-// elog[j] = max |e|
-void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, const double* nrm2, double tau,
-                    double* g, int* ist, double* elog, hipStream_t s);
-// predict (one block, after step j's three-term recurrence): chat[0..j] of step j + 1, and H[:, j]'s alpha / beta entries
-void launch_os_predict(const double* G, double* H, int n, int j, const double* alpha_j, const double* beta_j, const double* nrm2,
-                       double* chat, hipStream_t s);
+// elog[j] = max |e|.  fused: d = [V_i . w (i < j), u~ . u~, ||w||^2] and chat in the units of w; post normalises both by
+// b = sqrt(||w||^2), takes cs = 1, leaves ||w||^2 in nrm2[0] and the correction's coefficients for u~ (b g_i) in g[n ..].
+void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, double* nrm2, double tau, double* g, int* ist,
+                    double* elog, bool fused, hipStream_t s);
+// one block: sum_out[0] = sum(part[0 .. np)) in k_final_sum's grouping - ||w_{j+1}||^2 behind the three-term kernel, or (fused) alpha_j
+// behind the SpMV - and then, when `predict`, chat[0..j] of step j + 1 (fused: not divided by sqrt(nrm2)) and H[:, j]'s alpha / beta entries
+void launch_os_sum_predict(const double* part, int np, double* sum_out, const double* G, double* H, int n, int j, const double* alpha_j,
+                           const double* beta_j, double* chat, bool fused, bool predict, hipStream_t s);
 // ---- device-resident partial re-orthogonalisation (Simon's omega-recurrence in a one-block kernel) ----
 // State: st[0] = ||A|| estimate, st[1] = force_next, st[2 .. 2 + n + 2) = hb (hb[k] = the norm that formed V[k]), then three
 // rows of n + 1 doubles (omega_{j,:} lives in row j % 3); ist[0] = the gate of the coming step (1: sweep), ist[1] = number of

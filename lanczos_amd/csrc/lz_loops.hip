@@ -135,7 +135,7 @@ int step_reorth(lz_handle h, int j, int nrows, bool scale, int beta_idx, bool in
 }
 
 // r = r - alpha V[j] - beta V[jm1]; d_nrm2[0] = sum over ranks of ||r||^2
-int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm) {
+int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm, int* np_out) {
   const double M = (double)h->rows;
   int np = 0;
   {
@@ -144,6 +144,7 @@ int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const do
                            d_beta, h->rows_pad, h->d_part, h->stream);
     LZ_TRY(check_launch(h, "three_term"));
   }
+  if (np_out) *np_out = np;  // (the caller's own kernel adds the partials)
   if (!need_norm) return LZ_OK;  // fused-norm mode: ||r||^2 travels with the next Q^T r all-reduce
   {
     Scope sc(h, LZ_K_FINAL, 0, 0);
@@ -416,57 +417,140 @@ int run_small_engine(lz_handle h, int n, const double* v0_local, bool steps, boo
 // (sweep 8 j M + 16 M, three-term 24 M) plus the SpMV.  The coefficients equal the two-pass loop's to rounding (not bit
 // for bit: the dots that decide them are summed in another order, and ||w||^2 comes from the three-term kernel).
 // One rank, fused-norm mode, full re-orthogonalisation, default kernels; lz_run_resume continues on the two-pass loop.
-int run_loop_one_sweep(lz_handle h, int n) {
-  const double M = (double)h->rows;
+// Where the matrix has a scale-on-read SpMV the fused form below runs instead (lz_set_tuning(h, 15, 7): this one always).
+struct OneSweepState {
+  double *G, *H, *chat, *g, *elog;
+  int nb;
+};
+static int one_sweep_setup(lz_handle h, int n, OneSweepState& st) {
   const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8;
   if (h->os_n < n) {
     LZ_TRY(dev_alloc(h, h->d_os, os_doubles));
     LZ_TRY(dev_alloc(h, h->d_osi, 4));
     h->os_n = n;
   }
-  const int nb = os_sweep_blocks(h->rows_pad);
-  LZ_TRY(ensure_part(h, (size_t)nb * qtw_ldp(n) + 64));
-  double* G = h->d_os;
-  double* H = G + (size_t)n * n;
-  double* chat = H + (size_t)n * n;
-  double* g = chat + n + 1;
-  double* elog = g + 2 * n + 2;
+  st.nb = os_sweep_blocks(h->rows_pad);
+  LZ_TRY(ensure_part(h, (size_t)st.nb * qtw_ldp(n + 1) + 64));
+  st.G = h->d_os;
+  st.H = st.G + (size_t)n * n;
+  st.chat = st.H + (size_t)n * n;
+  st.g = st.chat + n + 1;
+  st.elog = st.g + 2 * n + 2;
   LZ_HIP(h, hipMemsetAsync(h->d_os, 0, os_doubles * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));  // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate)
+  return LZ_OK;
+}
+// sweep (mode 0: units of u = w / beta, reads r and ||w||^2; mode 2: the fused form, see run_loop_one_sweep_fused), second-stage sums,
+// post, gated correction of step j
+static int one_sweep_step(lz_handle h, int n, int j, const OneSweepState& st, bool fused) {
+  const double M = (double)h->rows;
+  const int bidx = (j + n - 2) % (n - 1);  // beta[j-1] with Python's negative index at j = 0
+  double* dst = fused ? h->d_r2 : h->d_V + (int64_t)j * h->ldv;
+  {
+    Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 4.0 * (j + 1) * M);
+    if (fused)  // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-2} v_{j-2}: the beta that formed v_{j-1} sits at step j - 1's slot
+      launch_os_sweep(2, h->d_V, h->ldv, h->rows_pad, j, st.chat, h->d_r, nullptr, nullptr, h->d_part, nullptr, h->stream, dst, h->d_alpha + (j - 1),
+                      h->d_beta + (j - 1 + n - 2) % (n - 1));
+    else
+      launch_os_sweep(0, h->d_V, h->ldv, h->rows_pad, j, st.chat, h->d_r, h->d_nrm2, h->d_beta + bidx, h->d_part, nullptr, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep"));
+  }
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    const int nout = fused ? j + 2 : j + 1;
+    launch_final_rows_t(h->d_part, st.nb, qtw_ldp(nout), nout, h->d_c, h->stream);
+    LZ_TRY(check_launch(h, "final_rows(one-sweep)"));
+    launch_os_post(h->d_c, st.chat, st.G, st.H, n, j, h->d_nrm2, kOneSweepTau, st.g, h->d_osi, st.elog, fused, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep post"));
+  }
+  {
+    Scope sc(h, LZ_K_QTW, 0, 0);  // (bytes are not counted: the correction runs in almost no step)
+    launch_os_sweep(1, h->d_V, h->ldv, h->rows_pad, j, fused ? st.g + n : st.g, nullptr, nullptr, nullptr, nullptr, h->d_osi, h->stream, dst);
+    LZ_TRY(check_launch(h, "one-sweep correction"));
+  }
+  return LZ_OK;
+}
+
+int run_loop_one_sweep(lz_handle h, int n) {
+  OneSweepState st;
+  LZ_TRY(one_sweep_setup(h, n, st));
+  h->last_os_fused = 0;
   // warm-up (Lanczos.py:108-110): r = A v0; alpha0 = r.v0; r = r - alpha0 v0, ||r||^2
   LZ_TRY(step_spmv(h, 0));
   LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
   for (int j = 0; j < n; ++j) {
     const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
     h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);  // beta[j-1] with Python's negative index at j = 0
-    {
-      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 4.0 * (j + 1) * M);
-      launch_os_sweep(0, h->d_V, h->ldv, h->rows_pad, j, chat, h->d_r, h->d_nrm2, h->d_beta + bidx, h->d_part, nullptr, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep"));
-    }
-    {
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_final_rows_t(h->d_part, nb, qtw_ldp(j + 1), j + 1, h->d_c, h->stream);
-      LZ_TRY(check_launch(h, "final_rows(one-sweep)"));
-      launch_os_post(h->d_c, chat, G, H, n, j, h->d_nrm2, kOneSweepTau, g, h->d_osi, elog, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep post"));
-    }
-    {
-      Scope sc(h, LZ_K_QTW, 0, 0);  // (bytes are not counted: the correction runs in almost no step)
-      launch_os_sweep(1, h->d_V, h->ldv, h->rows_pad, j, g, nullptr, nullptr, nullptr, nullptr, h->d_osi, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep correction"));
-    }
+    const int bidx = (j + n - 2) % (n - 1);
+    LZ_TRY(one_sweep_step(h, n, j, st, false));
     LZ_TRY(step_spmv(h, j));
     // at j = 0 the reference subtracts beta * V[-1], the still-zero last row: a no-op
-    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, true));
-    if (j + 1 < n) {
+    int np = 0;
+    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, false, &np));
+    {  // ||w_{j+1}||^2 from the three-term kernel's partials and the next step's predictions, one launch
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_predict(G, H, n, j, h->d_alpha + j, h->d_beta + bidx, h->d_nrm2, chat, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep predict"));
+      launch_os_sum_predict(h->d_part, np, h->d_nrm2, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, false,
+                            j + 1 < n, h->stream);
+      LZ_TRY(check_launch(h, "final_sum(nrm2) + one-sweep predict"));
     }
   }
   return LZ_OK;
+}
+
+// The one-sweep loop without the three-term pass (one rank, a matrix with a scale-on-read SpMV form: 5 or 7 entries per row, ELL
+// ordered).  w_j = (A v_{j-1} - alpha_{j-1} v_{j-1}) - beta_{j-2} v_{j-2} reads two rows the sweep of step j walks anyway, so the sweep
+// forms w itself from y = A v_{j-1} (k_os_sweep, mode 2) and measures ||w||^2 from the registers that hold it.  beta_j is then not
+// known before the walk, so the step works in the units of w: the predictions c' are not divided by beta, the sweep leaves
+// u~ = 2 w - (sum c'_i V_i + w) in the second residual buffer (self term exactly 1; the unfused form's ||w||^2 / beta^2 is 1 to an
+// ulp), post divides the measured and the predicted dots by b = sqrt(||w||^2), and the SpMV forms v_j = u~ / b wherever it reads x,
+// stores V[j], beta_j and y = A v_j (the partial loop's SC form, always scaling).  Its alpha partials are summed by the one-block
+// kernel that predicts step j + 1.  Six launches per step instead of nine, 8 j M + 41 M bytes instead of 8 j M + 65 M with a
+// row-class coded 5-point matrix.  Step 0 and the warm-up are the unfused form's; after the last step the three-term kernel runs
+// once, so d_r, ||r||^2 and V hold what lz_get_residual / lz_run_resume expect.  Coefficients and basis equal the unfused form's to
+// rounding (tests/test_gpu_one_sweep_fused.py).
+bool one_sweep_fused_applies(lz_handle h, int n) {
+  const bool one_rank = h->world == 1 && h->comm_kind == 0;
+  return one_rank && h->kind == 1 && ell_usable(h->csr, h->flags) && (h->csr.fixed_k == 5 || h->csr.fixed_k == 7) && n <= kOneSweepFusedMaxN &&
+         h->tune[15] != 7;
+}
+int run_loop_one_sweep_fused(lz_handle h, int n) {
+  const double M = (double)h->rows;
+  OneSweepState st;
+  LZ_TRY(one_sweep_setup(h, n, st));
+  h->last_os_fused = 1;
+  LZ_TRY(step_spmv(h, 0));
+  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
+  for (int j = 0; j < n; ++j) {
+    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
+    h->prof_iter = (j % pstride) == pstride / 2;
+    const int bidx = (j + n - 2) % (n - 1);
+    double* vj = h->d_V + (int64_t)j * h->ldv;
+    LZ_TRY(one_sweep_step(h, n, j, st, j > 0));
+    int npa = 0;
+    if (j == 0) {  // step 0 is the unfused form's: V[0] is in place, a plain SpMV
+      Scope sc(h, LZ_K_SPMV, spmv_bytes(h), spmv_flops(h));
+      npa = launch_spmv_csr(h->csr, vj, h->d_r, vj, h->d_part, h->flags, h->stream);
+      LZ_TRY(check_launch(h, "spmv"));
+    } else {
+      SpmvScale ss;
+      ss.r = h->d_r2;
+      ss.nrm2 = h->d_nrm2;
+      ss.vj = vj;
+      ss.beta_slot = h->d_beta + bidx;
+      ss.gate = h->d_osi + 2;  // always 0: scale on read
+      // (bytes as the partial loop counts its fused SpMV: with a row-class coded matrix u~ once, y, V[j] and the class byte)
+      Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
+      npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream, &ss);
+      LZ_TRY(check_launch(h, "spmv(ell, scale fused)"));
+    }
+    {  // alpha_j from the SpMV's partials and the next step's predictions, one launch
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_os_sum_predict(h->d_part, npa, h->d_alpha + j, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, true, j + 1 < n, h->stream);
+      LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+    }
+  }
+  // r = (A v_{n-1} - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2}, ||r||^2: the residual entering step n
+  return step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 1 + n - 2) % (n - 1), true);
 }
 
 // ---- which loop structure runs the Krylov iteration --------------------------------------------------------------------
@@ -506,7 +590,7 @@ Loop choose_loop(lz_handle h, int n) {
 #endif
   // one-sweep loop: one rank, full fused-norm re-orthogonalisation, default kernels, no overlap; tune[15] == 6 forces it at any size
   const bool one_sweep_ok = one_rank && full_fused && default_kernels && !(f & LZ_FLAG_OVERLAP_HALO) && n >= 2 && n <= kOneSweepMaxN;
-  if (h->tune[15] == 6 && one_sweep_ok) return LOOP_ONE_SWEEP;
+  if ((h->tune[15] == 6 || h->tune[15] == 7) && one_sweep_ok) return LOOP_ONE_SWEEP;  // (7: never the fused form, A/B)
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
   if (one_rank && h->qplan.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)h->qplan.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;
@@ -1025,7 +1109,7 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
     case LOOP_ONE_REDUCE: LZ_TRY(run_loop_onereduce(h, n)); break;
     case LOOP_PARTIAL_DEVICE: LZ_TRY(run_loop_partial_device(h, n)); break;
     case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
-    case LOOP_ONE_SWEEP: LZ_TRY(run_loop_one_sweep(h, n)); break;
+    case LOOP_ONE_SWEEP: LZ_TRY(one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n)); break;
     default: LZ_TRY(run_loop_six(h, n, &sweeps)); break;
   }
   h->last_sweeps = sweeps;

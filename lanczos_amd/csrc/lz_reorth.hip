@@ -14,6 +14,7 @@
 // the same scalar inputs; only the inner products differ (summation order).
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "lz_device.h"
 
@@ -1349,68 +1350,137 @@ template <int P, int RU, int MODE>
 __global__ __launch_bounds__(kTPB) void k_os_sweep(double* __restrict__ V, int64_t ldv, int64_t n2, int j, const double* __restrict__ coef,
                                                   const double* __restrict__ r, const double* __restrict__ nrm2,
                                                   double* __restrict__ beta_slot, int ldp, double* __restrict__ part,
-                                                  const int* __restrict__ gate) {
+                                                  const int* __restrict__ gate, double* __restrict__ dst,
+                                                  const double* __restrict__ alpha_prev, const double* __restrict__ beta_prev) {
   if (MODE == 1 && gate[0] == 0) return;  // no correction due on this step
   extern __shared__ double keep[];        // [kTPB / 64][ldp]: this block's per-wave dots
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
   const int64_t ld2 = ldv >> 1;
   const double2* V2 = reinterpret_cast<const double2*>(V);
-  double2* out = reinterpret_cast<double2*>(V) + (int64_t)j * ld2;
-  int64_t pos[P];
+  double2* out = reinterpret_cast<double2*>(dst);  // V[j], or the residual buffer (fused form and its correction)
+  // (the fused form keeps 32-bit positions - n2 < 2^30, the SpMV's row index is an int - which is what lets its prologue fit the walk's registers)
+  using pos_t = std::conditional_t<MODE == 2, int, int64_t>;
+  pos_t pos[P];
   bool ok[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-    pos[p] = base + (int64_t)p * kTPB;
-    ok[p] = pos[p] < n2;
-    if (!ok[p]) pos[p] = n2 - 1;  // valid address, result discarded
+    pos[p] = (pos_t)(base + (int64_t)p * kTPB);
+    ok[p] = base + (int64_t)p * kTPB < n2;
+    if (!ok[p]) pos[p] = (pos_t)(n2 - 1);  // valid address, result discarded
   }
   double2 w[P];
-  double b = 1.0, cs = 0.0;
+  double b = 1.0, cs = MODE == 2 ? 1.0 : 0.0;  // fused form: units of w, self term 1
   if (MODE == 0) {
     const double s2 = nrm2[0];
     b = sqrt(s2);
     cs = s2 / (b * b);  // the self term c_j = ||w||^2 / beta^2 (k_update_slice's raw_c arithmetic)
     if (blockIdx.x == 0 && threadIdx.x == 0) beta_slot[0] = b;
   }
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    if (MODE == 0) {
-      w[p] = reinterpret_cast<const double2*>(r)[pos[p]];
-      w[p].x = w[p].x / b;
-      w[p].y = w[p].y / b;
-    } else {
-      w[p] = out[pos[p]];
-    }
-    if (!ok[p]) w[p] = make_double2(0.0, 0.0);  // so the clamped duplicates add nothing to the dots
-  }
   double tx[P], ty[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) tx[p] = ty[p] = 0.0;
-  for (int k = 0; k < j; k += RU) {
+  if (MODE == 2) {
+    // fused form (j >= 1): w = (y - alpha V[j-1]) - beta V[j-2] in k_three_term's expression, formed position by position so that
+    // the two newest rows are consumed here - their dots against w, ||w||^2 and their share of the sum - and only w and the
+    // running sums stay live for the walk over rows 0 .. j-3
+    const double a = alpha_prev[0];
+    const bool two = j >= 2;  // j == 1: no beta term (the reference's V[-1] is the zero row)
+    const double bp = two ? beta_prev[0] : 0.0;
+    const double c1 = coef[j - 1], c2 = two ? coef[j - 2] : 0.0;
+    const double2* y2 = reinterpret_cast<const double2*>(r);
+    const double2* v1 = V2 + (int64_t)(j - 1) * ld2;
+    const double2* v2 = V2 + (int64_t)(two ? j - 2 : 0) * ld2;
+    double d1 = 0.0, d2 = 0.0, ww = 0.0;
+    constexpr int PB = P < 8 ? P : 8;  // positions per batch: 3 PB loads in flight, so that the prologue needs no more registers than the walk
+    auto batches = [&](auto two_c) {  // (one straight-line body per case: the batches stay in order)
+      constexpr bool TWO = decltype(two_c)::value;
+#pragma unroll
+      for (int p0 = 0; p0 < P; p0 += PB) {
+        double2 x[PB], v[PB], m[PB];
+#pragma unroll
+        for (int q = 0; q < PB; ++q) {
+          x[q] = y2[pos[p0 + q]];
+          v[q] = ld_stream<1>(v1 + pos[p0 + q]);
+          m[q] = TWO ? ld_stream<1>(v2 + pos[p0 + q]) : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int q = 0; q < PB; ++q) {
+          const int p = p0 + q;
+          x[q].x = x[q].x - v[q].x * a;
+          x[q].y = x[q].y - v[q].y * a;
+          if (TWO) {
+            x[q].x = x[q].x - m[q].x * bp;
+            x[q].y = x[q].y - m[q].y * bp;
+          }
+          if (!ok[p]) x[q] = make_double2(0.0, 0.0);  // so the clamped duplicates add nothing to the dots
+          w[p] = x[q];
+          ww = fma(x[q].x, x[q].x, ww);
+          ww = fma(x[q].y, x[q].y, ww);
+          d1 = fma(v[q].x, x[q].x, d1);
+          d1 = fma(v[q].y, x[q].y, d1);
+          tx[p] = tx[p] + c1 * v[q].x;
+          ty[p] = ty[p] + c1 * v[q].y;
+          if (TWO) {
+            d2 = fma(m[q].x, x[q].x, d2);
+            d2 = fma(m[q].y, x[q].y, d2);
+            tx[p] = tx[p] + c2 * m[q].x;
+            ty[p] = ty[p] + c2 * m[q].y;
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (keeps the next batch's loads behind this batch's arithmetic)
+      }
+    };
+    if (two)  // block-uniform
+      batches(std::true_type());
+    else
+      batches(std::false_type());
+    ww = wave_sum(ww);
+    d1 = wave_sum(d1);
+    d2 = wave_sum(d2);
+    if (lane == 0) {
+      keep[wv * ldp + j + 1] = ww;
+      keep[wv * ldp + j - 1] = d1;
+      if (two) keep[wv * ldp + j - 2] = d2;
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      if (MODE == 0) {
+        w[p] = reinterpret_cast<const double2*>(r)[pos[p]];
+        w[p].x = w[p].x / b;
+        w[p].y = w[p].y / b;
+      } else {
+        w[p] = out[pos[p]];
+      }
+      if (!ok[p]) w[p] = make_double2(0.0, 0.0);  // so the clamped duplicates add nothing to the dots
+    }
+  }
+  const int jw = MODE == 2 ? (j >= 2 ? j - 2 : 0) : j;  // rows the walk covers
+  for (int k = 0; k < jw; k += RU) {
     double2 q[RU][P];
 #pragma unroll
     for (int u = 0; u < RU; ++u)
-      if (k + u < j) {  // block-uniform
+      if (k + u < jw) {  // block-uniform
         const double2* row = V2 + (int64_t)(k + u) * ld2;
 #pragma unroll
         for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(row + pos[p]);
       }
 #pragma unroll
     for (int u = 0; u < RU; ++u)
-      if (k + u < j) {
+      if (k + u < jw) {
         const double ck = coef[k + u];
         double d = 0.0;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
           tx[p] = tx[p] + ck * q[u][p].x;
           ty[p] = ty[p] + ck * q[u][p].y;
-          if (MODE == 0) {
+          if (MODE != 1) {
             d = fma(q[u][p].x, w[p].x, d);
             d = fma(q[u][p].y, w[p].y, d);
           }
         }
-        if (MODE == 0) {
+        if (MODE != 1) {
           d = wave_sum(d);
           if (lane == 0) keep[wv * ldp + k + u] = d;
         }
@@ -1420,7 +1490,7 @@ __global__ __launch_bounds__(kTPB) void k_os_sweep(double* __restrict__ V, int64
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     double2 o;
-    if (MODE == 0) {
+    if (MODE != 1) {
       tx[p] = tx[p] + cs * w[p].x;  // row j (u itself) is the last term of the sum, as in k_update_slice
       ty[p] = ty[p] + cs * w[p].y;
       o = make_double2(2.0 * w[p].x - tx[p], 2.0 * w[p].y - ty[p]);
@@ -1438,7 +1508,8 @@ __global__ __launch_bounds__(kTPB) void k_os_sweep(double* __restrict__ V, int64
   if (lane == 0) keep[wv * ldp + j] = vv;
   __syncthreads();
   double* mine = part + (int64_t)blockIdx.x * ldp;
-  for (int i = threadIdx.x; i <= j; i += kTPB)
+  const int nout = MODE == 2 ? j + 2 : j + 1;  // fused form: one more slot, ||w||^2
+  for (int i = threadIdx.x; i < nout; i += kTPB)
     __builtin_nontemporal_store(((keep[i] + keep[ldp + i]) + keep[2 * ldp + i]) + keep[3 * ldp + i], mine + i);
 }
 
@@ -1471,18 +1542,23 @@ int os_sweep_blocks(int64_t len) {
 }
 
 int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const double* coef, const double* r, const double* nrm2,
-                    double* beta_slot, double* part, const int* gate, hipStream_t s) {
+                    double* beta_slot, double* part, const int* gate, hipStream_t s, double* dst, const double* alpha_prev,
+                    const double* beta_prev) {
   const int64_t n2 = len >> 1;
   const int P = os_sweep_p(n2);
   const int grid = (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
-  const int ldp = qtw_ldp(j + 1);
-  const size_t lds = mode == 0 ? (size_t)(kTPB / 64) * ldp * sizeof(double) : 0;
-#define LZ_OS_GO(PP, RR)                                                                                                          \
-  do {                                                                                                                            \
-    if (mode == 0)                                                                                                                \
-      hipLaunchKernelGGL((k_os_sweep<PP, RR, 0>), dim3(grid), dim3(kTPB), lds, s, V, ldv, n2, j, coef, r, nrm2, beta_slot, ldp, part, gate); \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((k_os_sweep<PP, RR, 1>), dim3(grid), dim3(kTPB), lds, s, V, ldv, n2, j, coef, r, nrm2, beta_slot, ldp, part, gate); \
+  const int ldp = qtw_ldp(mode == 2 ? j + 2 : j + 1);
+  const size_t lds = mode != 1 ? (size_t)(kTPB / 64) * ldp * sizeof(double) : 0;
+  if (!dst) dst = V + (int64_t)j * ldv;
+#define LZ_OS_ARGS V, ldv, n2, j, coef, r, nrm2, beta_slot, ldp, part, gate, dst, alpha_prev, beta_prev
+#define LZ_OS_GO(PP, RR)                                                                                       \
+  do {                                                                                                         \
+    if (mode == 0)                                                                                             \
+      hipLaunchKernelGGL((k_os_sweep<PP, RR, 0>), dim3(grid), dim3(kTPB), lds, s, LZ_OS_ARGS);                 \
+    else if (mode == 2)                                                                                        \
+      hipLaunchKernelGGL((k_os_sweep<PP, RR, 2>), dim3(grid), dim3(kTPB), lds, s, LZ_OS_ARGS);                 \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_os_sweep<PP, RR, 1>), dim3(grid), dim3(kTPB), lds, s, LZ_OS_ARGS);                 \
   } while (0)
   switch (P) {
     case 16: LZ_OS_GO(16, 1); break;
@@ -1492,32 +1568,86 @@ int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const 
     default: LZ_OS_GO(1, 16); break;
   }
 #undef LZ_OS_GO
+#undef LZ_OS_ARGS
   return grid;
 }
 
-// k_os_post: one block.  max |e| is a max (order-free); every other sum runs in index order (os_post_one).
+// The one-block kernels' O(j^2) sums, spread over the lanes of a wave: wave `wv` of `nw` takes coefficients wv * CB + q (q < CB), then
+// nw * CB further on; lane t adds the terms l = t, t + 64, ... of each in that order, a fixed shuffle tree adds the lanes (reruns are
+// bit-identical).  Both operands of a coefficient are contiguous in l (G is symmetric and stored both ways, a column of H is
+// contiguous): coalesced loads, the CB coefficients' loads of a trip independent of each other.  f(i, sum) runs in lane 0.
+constexpr int kOsCB = 4;
+template <class RowA, class VecB, class Len, class F>
+__device__ __forceinline__ void os_wave_dots(int count, RowA rowa, VecB vecb, Len len, F f) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (int i0 = wv * kOsCB; i0 < count; i0 += nw * kOsCB) {
+    double acc[kOsCB];
+    const double* ra[kOsCB];
+    int m = 0;
+#pragma unroll
+    for (int q = 0; q < kOsCB; ++q) {
+      const int i = i0 + q < count ? i0 + q : count - 1;  // (a clamped duplicate: computed, not stored)
+      acc[q] = 0.0;
+      ra[q] = rowa(i);
+      m = max(m, len(i));
+    }
+#pragma unroll 4
+    for (int l = lane; l < m; l += 64) {
+      const double b = vecb(l);
+#pragma unroll
+      for (int q = 0; q < kOsCB; ++q) {
+        const int i = i0 + q < count ? i0 + q : count - 1;
+        acc[q] = fma(l < len(i) ? ra[q][l] : 0.0, b, acc[q]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kOsCB; ++q) {
+      const double t = wave_sum(acc[q]);
+      if (lane == 0 && i0 + q < count) f(i0 + q, t);
+    }
+  }
+}
+
+// k_os_post: one block.  max |e| is a max (order-free); every other sum is a fixed tree (os_wave_dots).  FUSED: the sweep worked in the
+// units of w - d holds [V_i . w (i < j), u~ . u~, ||w||^2], chat the un-normalised predictions; both are divided by b = sqrt(||w||^2)
+// here, the self term is cs = 1, nrm2[0] = ||w||^2 is left for the SpMV that scales u~, and the correction's coefficients for u~
+// (b g_i) go to g[n ..].
+template <bool FUSED>
 __global__ __launch_bounds__(kFinalThreads) void k_os_post(const double* __restrict__ d, const double* __restrict__ chat, double* __restrict__ G,
-                                                          double* __restrict__ H, int n, int j, const double* __restrict__ nrm2, double tau,
+                                                          double* __restrict__ H, int n, int j, double* __restrict__ nrm2, double tau,
                                                           double* __restrict__ g, int* __restrict__ ist, double* __restrict__ elog) {
-  extern __shared__ double col[];  // [j + 1]
+  extern __shared__ double smem[];  // col [j + 1], the applied coefficients [j], the measured dots [j]
+  double* col = smem;
+  double* sc = col + (j + 1);
+  double* sd = sc + (j + 1);
   __shared__ double smax[kFinalThreads / 64];
   __shared__ int s_trip;
-  const double s2 = nrm2[0];
-  const double b = sqrt(s2), cs = s2 / (b * b);
+  const double s2 = FUSED ? d[j + 1] : nrm2[0];
+  const double b = sqrt(s2), cs = FUSED ? 1.0 : s2 / (b * b);
   double em = 0.0;
-  for (int i = threadIdx.x; i < j; i += kFinalThreads) {
-    em = fmax(em, fabs(d[i] - chat[i]));
-    col[i] = os_post_one(i, j, n, G, d, chat, cs);
+  for (int i = threadIdx.x; i < j; i += blockDim.x) {
+    const double di = FUSED ? d[i] / b : d[i], ci = FUSED ? chat[i] / b : chat[i];
+    const double e = fabs(di - ci);
+    em = e == e ? fmax(em, e) : __builtin_inf();  // (a NaN leftover must trip the gate: fmax would drop it)
+    sd[i] = di;
+    sc[i] = ci;
   }
-  if (threadIdx.x == 0) col[j] = d[j];
+  if (threadIdx.x == 0) {
+    col[j] = FUSED ? d[j] / s2 : d[j];
+    if (FUSED) nrm2[0] = s2;
+  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) em = fmax(em, __shfl_down(em, off, 64));
   if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = em;
   __syncthreads();
+  // G[i, j] (i < j) of v_j = (2 - cs) u_j - sum_{l<j} c_l V_l: (2 - cs) d_i - sum_l c_l G[i, l]
+  os_wave_dots(
+      j, [&](int i) { return G + (int64_t)i * n; }, [&](int l) { return sc[l]; }, [&](int) { return j; },
+      [&](int i, double t) { col[i] = (2.0 - cs) * sd[i] - t; });
   if (threadIdx.x == 0) {
     double m = 0.0;
-    for (int k = 0; k < kFinalThreads / 64; ++k) m = fmax(m, smax[k]);
-    const int trip = (j > 0 && !(m <= tau)) ? 1 : 0;  // (a NaN leftover trips the gate too)
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) m = fmax(m, smax[k]);
+    const int trip = (j > 0 && !(m <= tau)) ? 1 : 0;
     s_trip = trip;
     elog[j] = m;
     ist[0] = trip;
@@ -1527,57 +1657,88 @@ __global__ __launch_bounds__(kFinalThreads) void k_os_post(const double* __restr
   const int trip = s_trip;
   if (trip) {
     // correction v_j -= sum_i g_i V_i with g = G[:j, j]: new G[i, j] = G[i, j] - sum_l G[i, l] g_l, new v.v from the old column
-    for (int i = threadIdx.x; i < j; i += kFinalThreads) g[i] = col[i];
+    for (int i = threadIdx.x; i < j; i += blockDim.x) g[i] = col[i];
     __syncthreads();
-    for (int i = threadIdx.x; i < j; i += kFinalThreads) {
-      double s = g[i];
-      for (int l = 0; l < j; ++l) s -= G[(int64_t)l * n + i] * g[l];
-      double t = -2.0 * g[i];
-      for (int l = 0; l < j; ++l) t += G[(int64_t)l * n + i] * g[l];
-      col[i] = s;
-      g[n + i] = g[i] * t;  // this row's share of the change of v.v (g has 2n doubles)
-    }
+    os_wave_dots(
+        j, [&](int i) { return G + (int64_t)i * n; }, [&](int l) { return g[l]; }, [&](int) { return j; },
+        [&](int i, double t) {
+          col[i] = g[i] - t;
+          sd[i] = g[i] * (t - 2.0 * g[i]);  // this row's share of the change of v.v
+        });
     __syncthreads();
     if (threadIdx.x == 0) {
       double vv = col[j];
-      for (int i = 0; i < j; ++i) vv += g[n + i];
+      for (int i = 0; i < j; ++i) vv += sd[i];
       col[j] = vv;
     }
+    if (FUSED)
+      for (int i = threadIdx.x; i < j; i += blockDim.x) g[n + i] = b * g[i];  // the correction acts on u~ = b v_j
     __syncthreads();
   }
-  for (int i = threadIdx.x; i <= j; i += kFinalThreads) {
+  for (int i = threadIdx.x; i <= j; i += blockDim.x) {
     G[(int64_t)j * n + i] = col[i];
     G[(int64_t)i * n + j] = col[i];
   }
   if (j > 0) {  // w_j = b / (2 - cs) (v_j + sum_{l<j} c_l V_l), c the applied coefficients: column j - 1 of H
     const double f = b / (2.0 - cs);
     double* hc = H + (int64_t)(j - 1) * n;
-    for (int l = threadIdx.x; l < j; l += kFinalThreads) {
-      const double c = trip ? chat[l] + g[l] : chat[l];
+    for (int l = threadIdx.x; l < j; l += blockDim.x) {
+      const double c = trip ? sc[l] + g[l] : sc[l];
       hc[l] = hc[l] + f * c;
     }
     if (threadIdx.x == 0) hc[j] = f;
   }
 }
 
-void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, const double* nrm2, double tau,
-                    double* g, int* ist, double* elog, hipStream_t s) {
-  hipLaunchKernelGGL(k_os_post, dim3(1), dim3(kFinalThreads), (size_t)(j + 1) * sizeof(double), s, d, chat, G, H, n, j, nrm2, tau, g, ist, elog);
+void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, double* nrm2, double tau, double* g, int* ist,
+                    double* elog, bool fused, hipStream_t s) {
+  const size_t lds = (size_t)3 * (j + 1) * sizeof(double);
+  if (fused)
+    hipLaunchKernelGGL(k_os_post<true>, dim3(1), dim3(kFinalThreads), lds, s, d, chat, G, H, n, j, nrm2, tau, g, ist, elog);
+  else
+    hipLaunchKernelGGL(k_os_post<false>, dim3(1), dim3(kFinalThreads), lds, s, d, chat, G, H, n, j, nrm2, tau, g, ist, elog);
 }
 
-__global__ __launch_bounds__(kFinalThreads) void k_os_predict(const double* __restrict__ G, double* __restrict__ H, int n, int j,
-                                                             const double* __restrict__ alpha_j, const double* __restrict__ beta_j,
-                                                             const double* __restrict__ nrm2, double* __restrict__ chat) {
-  const double a = alpha_j[0], bj = j > 0 ? beta_j[0] : 0.0, bn = sqrt(nrm2[0]);
-  for (int i = threadIdx.x; i <= j; i += kFinalThreads) chat[i] = os_predict_one(i, j, n, H, G, a, bj, bn);
+// One block behind the SpMV (fused form: sum_out = alpha_j from the SpMV's partials) or behind the three-term kernel (sum_out =
+// ||w_{j+1}||^2 from its partials), k_final_sum's grouping; then, when `predict`, the next step's predictions
+//   c_hat_i = ((A V_i) . v_j - alpha_j G[i, j] - beta_j G[i, j-1]) / bn,  (A V_i) . v_j = sum_{l <= i+1} H[l, i] G[l, j]  (i < j),  alpha_j  (i = j)
+// with bn = sqrt(||w_{j+1}||^2), or 1 in the fused form (whose sweep works in the units of w), and column j of H.
+template <bool FUSED>
+__global__ __launch_bounds__(kFinalThreads) void k_os_sum_predict(const double* __restrict__ part, int np, double* __restrict__ sum_out,
+                                                                 const double* __restrict__ G, double* __restrict__ H, int n, int j,
+                                                                 const double* __restrict__ alpha_j, const double* __restrict__ beta_j,
+                                                                 double* __restrict__ chat, int predict) {
+  __shared__ double sm[kFinalThreads / 64];
+  __shared__ double s_sum;
+  const double t = final_sum_1024(part, np, sm);
+  if (threadIdx.x == 0) {
+    sum_out[0] = t;
+    s_sum = t;
+  }
+  if (!predict) return;
+  __syncthreads();
+  const double a = FUSED ? s_sum : alpha_j[0], bj = j > 0 ? beta_j[0] : 0.0, bn = FUSED ? 1.0 : sqrt(s_sum);
+  const double* gj = G + (int64_t)j * n;
+  const double* gm = G + (int64_t)(j > 0 ? j - 1 : 0) * n;
+  auto finish = [&](int i, double s) {
+    s = s - a * gj[i];
+    if (j > 0) s = s - bj * gm[i];
+    chat[i] = s / bn;
+  };
+  os_wave_dots(
+      j, [&](int i) { return H + (int64_t)i * n; }, [&](int l) { return gj[l]; }, [&](int i) { return i + 2; }, finish);
+  if (threadIdx.x == 0) finish(j, a);  // V_j . A v_j: the SpMV's own dot
   // column j of H: alpha_j on the diagonal, beta_j above it; k_os_post of step j + 1 adds the w_{j+1} terms
   double* hc = H + (int64_t)j * n;
-  for (int l = threadIdx.x; l < n; l += kFinalThreads) hc[l] = l == j ? a : (l == j - 1 ? bj : 0.0);
+  for (int l = threadIdx.x; l < n; l += blockDim.x) hc[l] = l == j ? a : (l == j - 1 ? bj : 0.0);
 }
 
-void launch_os_predict(const double* G, double* H, int n, int j, const double* alpha_j, const double* beta_j, const double* nrm2,
-                       double* chat, hipStream_t s) {
-  hipLaunchKernelGGL(k_os_predict, dim3(1), dim3(kFinalThreads), 0, s, G, H, n, j, alpha_j, beta_j, nrm2, chat);
+void launch_os_sum_predict(const double* part, int np, double* sum_out, const double* G, double* H, int n, int j, const double* alpha_j,
+                           const double* beta_j, double* chat, bool fused, bool predict, hipStream_t s) {
+  if (fused)
+    hipLaunchKernelGGL(k_os_sum_predict<true>, dim3(1), dim3(kFinalThreads), 0, s, part, np, sum_out, G, H, n, j, alpha_j, beta_j, chat, predict ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_os_sum_predict<false>, dim3(1), dim3(kFinalThreads), 0, s, part, np, sum_out, G, H, n, j, alpha_j, beta_j, chat, predict ? 1 : 0);
 }
 
 }  // namespace lz

@@ -192,6 +192,78 @@ def one_sweep_lanczos(H, n, seed=99, v0=None, tau=1e-14, fast=True):
     return alpha, bet[1:], V, stats
 
 
+def one_sweep_fused_lanczos(H, n, seed=99, v0=None, tau=1e-14):
+    """The fused form of the loop (run_loop_one_sweep_fused): from step 1 on there is no three-term pass - the sweep forms
+    w_j = (A v_{j-1} - alpha v_{j-1}) - beta v_{j-2} itself and works in the units of w: the predictions are not divided by beta, the
+    self term is exactly 1, u~ = 2 w - (sum c'_i V_i + w), and V_i . w, u~ . u~ and ||w||^2 are measured in the same walk.  Post
+    divides the measured and the predicted dots by b = sqrt(||w||^2) (deferred normalisation); v_j = u~ / b is formed by the SpMV."""
+    H = scipy.sparse.csr_matrix(H)
+    M = H.shape[0]
+    V = np.zeros((n, M))
+    V[0] = start_vector(M, seed, v0)
+    alpha = np.zeros(n)
+    bet = np.zeros(n)
+    G = np.zeros((n, n))
+    Hm = np.zeros((n, n))
+    y = H @ V[0]
+    alpha[0] = np.dot(y, V[0])
+    r = y - alpha[0] * V[0]
+    emax = np.zeros(n)
+    trips = []
+    chat = np.zeros(0)
+    for j in range(n):
+        if j == 0:  # step 0 is the unfused form's: units of u = r / b, cs = ||r||^2 / b^2
+            nrm2 = np.dot(r, r)
+            b = np.sqrt(nrm2)
+            cs = nrm2 / (b * b)
+            u = r / b
+            v = 2 * u - cs * u
+            col = np.array([np.dot(v, v)])
+            capp = chat
+        else:
+            w = y - alpha[j - 1] * V[j - 1]
+            if j >= 2:
+                w = w - bet[j - 1] * V[j - 2]
+            t = chat @ V[:j]
+            ut = 2 * w - (t + w)
+            d = V[:j] @ w
+            nrm2 = np.dot(w, w)
+            b = np.sqrt(nrm2)
+            dn, cn = d / b, chat / b
+            emax[j] = np.abs(dn - cn).max()
+            col = np.concatenate([dn - G[:j, :j] @ cn, [np.dot(ut, ut) / nrm2]])
+            capp = cn.copy()
+            if emax[j] > tau:
+                trips.append(j)
+                g = col[:j].copy()
+                ut = ut - (b * g) @ V[:j]
+                Gjj = G[:j, :j]
+                col = np.concatenate([col[:j] - Gjj @ g, [col[j] - 2.0 * g @ col[:j] + g @ Gjj @ g]])
+                capp = capp + g
+            v = ut / b  # (the SpMV's division on read)
+            Hm[j, j - 1] += b
+            Hm[:j, j - 1] += b * capp
+        bet[j] = b
+        V[j] = v
+        G[: j + 1, j] = col
+        G[j, : j + 1] = col
+        y = H @ v
+        alpha[j] = np.dot(v, y)
+        Hm[j, j] += alpha[j]
+        if j:
+            Hm[j - 1, j] += b
+        if j + 1 < n:  # un-normalised predictions V_i . w_{j+1}
+            p = np.empty(j + 1)
+            p[:j] = (Hm[: j + 1, :j] * G[: j + 1, j][:, None]).sum(axis=0) if j else p[:j]
+            p[j] = alpha[j]
+            p = p - alpha[j] * G[: j + 1, j]
+            if j:
+                p = p - b * G[: j + 1, j - 1]
+            chat = p
+    stats = {"emax": emax, "trips": trips, "G": G}
+    return alpha, bet[1:], V, stats
+
+
 def report_case(name, H, n, seed=99, v0=None):
     t0 = time.perf_counter()
     H = scipy.sparse.csr_matrix(H)
