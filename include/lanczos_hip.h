@@ -136,7 +136,10 @@ int lz_set_options(lz_handle h, int flags);
  *       the one-sweep loop - one walk over the basis per step, lz_last_engine 9 -, else six; 1 six always; 6 the one-sweep loop
  *       at any size (one rank, fused-norm full re-orthogonalisation, default kernels, n <= 1536) - its fused form (no three-term
  *       pass, lz_last_one_sweep_fused) where the matrix has a scale-on-read SpMV, as the automatic choice does; 7 the one-sweep
- *       loop at any size with the separate three-term kernel always (A/B, tests))
+ *       loop at any size with the separate three-term kernel always (A/B, tests).  Where the fused form applies, n >= 4 and
+ *       n <= 1023, the automatic choice takes its PAIR form - one walk over the basis per two steps, lz_last_one_sweep_pairs;
+ *       6 and 7 never do; 8 the one-sweep loop at any size with pairs; 9 the same with 16 instead of 8 positions per lane in
+ *       the pair walk on long vectors (A/B))
  *   16  rows per chunk of the CHUNKED Ritz mode (0 auto: chunked only when Y does not fit beside the basis; > 0 forces it: tests)
  *   11  two-sided Gram-Schmidt links (0 / 1: streaming kernel + fold kernel per link)
  *   17  fixed-K (stencil) SpMV layout: 0 auto (CSR-order kernel with products staged through LDS; the ELL-ordered second copy -
@@ -377,6 +380,15 @@ int lz_last_gate_trips(lz_handle h, int* trips);
  * read and stores V[j]; no three-term kernel runs inside the loop.  0 for the unfused form (27-point rows, two-phase or dense
  * SpMV, lz_set_tuning(h, 15, 7)) and after any other loop.  Both forms report lz_last_engine 9. */
 int lz_last_one_sweep_fused(lz_handle h, int* fused);
+/* One-sweep loop, pair form: the number of pair walks behind the result the last lz_run returned - from step 2 on, one walk over
+ * the basis finishes v_j and forms the un-normalised v_{j+1} (the SpMV of step j runs on the uncorrected w_j / beta_j, and what the
+ * correction owes to w_{j+1} is applied as a combination of basis rows): (n - 2) / 2 pairs, an odd last step runs the single form.
+ * 0 after the single forms, after any other loop, and after a run that abandoned its pairs.  lz_last_one_sweep_fused stays 1. */
+int lz_last_one_sweep_pairs(lz_handle h, int* pairs);
+/* 1 when the last lz_run tried the pair form and a pair's prediction missed by more than the gate (1e-14): a pair has no correcting
+ * sweep, so the whole run was repeated on the single fused form (what was returned is that run's result, bit for bit).  The handle
+ * remembers it until a matrix is set again: later runs take the single form at once and report 0 here. */
+int lz_last_pair_abandoned(lz_handle h, int* abandoned);
 /* Host evaluation of the one-sweep loop's per-step arithmetic (the device kernels' expressions, summed in index order; the
  * kernels add the same terms lane-strided through a fixed shuffle tree), for checks without a GPU.  G (symmetric) and H are n x n with column i at [i * n].  predict: chat[0..j] of step j + 1 from alpha_j, the
  * norm beta_j that formed v_j and nrm2 = ||w_{j+1}||^2.  post: col[0..j) = G[:j, j] of the v_j formed with chat from the

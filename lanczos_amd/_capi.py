@@ -48,7 +48,8 @@ TUNE_BI_LINKS = 11          # two-sided Gram-Schmidt links
 TUNE_NO_SKEW = 12           # 1 = no row-stride skew
 TUNE_POISON_BASIS = 13      # 1 = NaN-poison a fresh basis allocation (test knob)
 TUNE_SPMV_PLAN = 14         # irregular SpMV plan (0 auto, 1 never two-phase, 2 always)
-TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size, 7 the same, never fused)
+TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size (never pairs), 7 the same, never fused,
+                            # 8 the one-sweep loop at any size with pair walks, 9 the same with 16 positions per lane in the pair walk)
 TUNE_RITZ_CHUNK_ROWS = 16   # rows per chunk of the chunked Ritz mode (> 0 forces it)
 TUNE_FIXED_LAYOUT = 17      # fixed-K SpMV layout (0 auto: row-class coded ELL where the rows fall into classes, else CSR order and ELL only in the partial loop;
                             # 1 never ELL; 2 / 3 uncoded ELL always, one / two rows per lane; 4 offsets-only coding)
@@ -140,6 +141,8 @@ SIGNATURES = {
     "lz_last_engine": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_last_gate_trips": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_last_one_sweep_fused": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_one_sweep_pairs": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_pair_abandoned": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_one_sweep_host_predict": (C.c_int, [C.c_int, C.c_int, _D, _D, C.c_double, C.c_double, C.c_double, _D]),
     "lz_one_sweep_host_post": (C.c_int, [C.c_int, C.c_int, _D, _D, _D, C.c_double, _D]),
     "lz_last_host_syncs": (C.c_int, [_P, _I64]),
@@ -672,6 +675,18 @@ class Handle:
         """one-sweep loop: 1 when the last run took the fused form (no three-term pass; the SpMV divides by beta on read), else 0"""
         k = C.c_int()
         self.check(self.lib.lz_last_one_sweep_fused(self._h, C.byref(k)))
+        return k.value
+
+    def last_one_sweep_pairs(self):
+        """one-sweep loop: pair walks (one walk over the basis per two steps) behind the last run's result; 0 after a run that abandoned them"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_one_sweep_pairs(self._h, C.byref(k)))
+        return k.value
+
+    def last_pair_abandoned(self):
+        """one-sweep loop: 1 when the last run tried the pair form, a prediction missed the gate and the run was repeated on the single form"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_pair_abandoned(self._h, C.byref(k)))
         return k.value
 
     def last_host_syncs(self):

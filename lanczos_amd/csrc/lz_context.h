@@ -159,6 +159,9 @@ struct lz_context {
   int os_n = 0;
   int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
   int last_os_fused = 0;       // one-sweep loop: 1 = the last lz_run took the fused form (no three-term pass)
+  int last_os_pairs = 0;       // one-sweep loop: pair walks (one walk per two steps) behind the last lz_run's result; 0 after a repeat
+  int last_pair_abandoned = 0; // 1 = the last lz_run tried the pair form, a leftover exceeded kOneSweepTau and the run was repeated on the single form
+  bool pair_tripped = false;   // remembered until the matrix is set again: the pair form is not tried a second time
   double* d_om = nullptr;      // device-resident partial re-orthogonalisation: omega-recurrence state (omega_state_doubles)
   int* d_omi = nullptr;        //   ... gate of the coming step, sweep count, per-step sweep log (omega_state_ints)
   int om_n = 0;

@@ -247,6 +247,22 @@ void launch_os_post(const double* d, const double* chat, double* G, double* H, i
 // behind the SpMV - and then, when `predict`, chat[0..j] of step j + 1 (fused: not divided by sqrt(nrm2)) and H[:, j]'s alpha / beta entries
 void launch_os_sum_predict(const double* part, int np, double* sum_out, const double* G, double* H, int n, int j, const double* alpha_j,
                            const double* beta_j, double* chat, bool fused, bool predict, hipStream_t s);
+// Pair form (run_loop_one_sweep_pair): one walk per two steps, j >= 2 the first step of the pair; the arithmetic is one_sweep_pair_lanczos's
+// (tools/one_sweep_prototype.py).  The walk parks 4 x 2 x os_pair_ldp(j) per-wave dots in LDS: n + 1 <= kOneSweepPairMaxLdp keeps that
+// within 64 KiB.  predict: alpha_out[0] = a0 = sum(part[0 .. np)) (the speculative SpMV's dot), H[:, j-1] gets step j's applied
+// coefficients, kap[0..j] / p[0..j] as the prototype names them.  sweep: V[j] = v_j, y (in: y° = A w / b; out: u~_{j+1}, in place),
+// part[b * 2 ldp + ..] = [V_i . w (i < j), u~ . u~ | V_i . z (i < j), v_j . z, ||u~_{j+1}||^2]; wide16: 16 positions per lane instead
+// of 8 on long vectors (A/B).  post: d = the runs' sums (launch_final_rows_t over 2 ldp columns); G[:, j], G[:, j+1], H[:, j], elog[j],
+// elog[j+1], nrm2[0] = ||u~_{j+1}||^2, and ist[3] = 1 when a leftover exceeds tau (sticky).
+constexpr int kOneSweepPairMaxLdp = 1024;
+int os_pair_ldp(int j);
+int os_pair_sweep_blocks(int64_t len, bool wide16);
+void launch_os_pair_predict(const double* part, int np, double* alpha_out, const double* nrm2, const double* chat, const double* G, double* H,
+                            int n, int j, double* kap, double* p, hipStream_t s);
+int launch_os_pair_sweep(double* V, int64_t ldv, int64_t len, int j, const double* chat, const double* kap, const double* w, double* y,
+                         const double* nrm2, const double* alpha0, double* part, bool wide16, hipStream_t s);
+void launch_os_pair_post(const double* d, int ldp, const double* chat, const double* kap, const double* p, double* G, double* H, int n, int j,
+                         double* nrm2, const double* alpha_j, double tau, int* ist, double* elog, hipStream_t s);
 // ---- device-resident partial re-orthogonalisation (Simon's omega-recurrence in a one-block kernel) ----
 // State: st[0] = ||A|| estimate, st[1] = force_next, st[2 .. 2 + n + 2) = hb (hb[k] = the norm that formed V[k]), then three
 // rows of n + 1 doubles (omega_{j,:} lives in row j % 3); ist[0] = the gate of the coming step (1: sweep), ist[1] = number of

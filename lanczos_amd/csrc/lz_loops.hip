@@ -422,7 +422,7 @@ struct OneSweepState {
   double *G, *H, *chat, *g, *elog;
   int nb;
 };
-static int one_sweep_setup(lz_handle h, int n, OneSweepState& st) {
+static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_blocks = 0) {
   const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8;
   if (h->os_n < n) {
     LZ_TRY(dev_alloc(h, h->d_os, os_doubles));
@@ -430,14 +430,15 @@ static int one_sweep_setup(lz_handle h, int n, OneSweepState& st) {
     h->os_n = n;
   }
   st.nb = os_sweep_blocks(h->rows_pad);
-  LZ_TRY(ensure_part(h, (size_t)st.nb * qtw_ldp(n + 1) + 64));
+  // (the pair walk leaves two runs per block, and its block count may differ from the single walk's)
+  LZ_TRY(ensure_part(h, (size_t)std::max(st.nb, 2 * pair_blocks) * qtw_ldp(n + 1) + 64));
   st.G = h->d_os;
   st.H = st.G + (size_t)n * n;
   st.chat = st.H + (size_t)n * n;
   st.g = st.chat + n + 1;
   st.elog = st.g + 2 * n + 2;
   LZ_HIP(h, hipMemsetAsync(h->d_os, 0, os_doubles * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));  // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate)
+  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));  // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate), [3] a pair's leftover exceeded tau
   return LZ_OK;
 }
 // sweep (mode 0: units of u = w / beta, reads r and ||w||^2; mode 2: the fused form, see run_loop_one_sweep_fused), second-stage sums,
@@ -513,43 +514,124 @@ bool one_sweep_fused_applies(lz_handle h, int n) {
   return one_rank && h->kind == 1 && ell_usable(h->csr, h->flags) && (h->csr.fixed_k == 5 || h->csr.fixed_k == 7) && n <= kOneSweepFusedMaxN &&
          h->tune[15] != 7;
 }
-int run_loop_one_sweep_fused(lz_handle h, int n) {
+// The scale-on-read SpMV of the fused and the pair form: V[j] = src / sqrt(nrm2[0]) wherever it reads x, beta -> its slot, dst = A V[j];
+// returns the alpha partials in d_part (src and dst are the two residual buffers, never the same one)
+static int one_sweep_scaling_spmv(lz_handle h, int n, int j, const double* src, double* dst, int* npa) {
   const double M = (double)h->rows;
+  double* vj = h->d_V + (int64_t)j * h->ldv;
+  SpmvScale ss;
+  ss.r = src;
+  ss.nrm2 = h->d_nrm2;
+  ss.vj = vj;
+  ss.beta_slot = h->d_beta + (j + n - 2) % (n - 1);
+  ss.gate = h->d_osi + 2;  // always 0: scale on read
+  // (bytes as the partial loop counts its fused SpMV: with a row-class coded matrix u~ once, y, V[j] and the class byte)
+  Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
+  *npa = launch_spmv_ell(h->csr, vj, dst, vj, h->d_part, h->stream, &ss);
+  return check_launch(h, "spmv(ell, scale fused)");
+}
+// one step of the fused form: sweep / post / gated correction, SpMV, alpha sum + the next step's predictions
+static int one_sweep_fused_iter(lz_handle h, int n, int j, const OneSweepState& st) {
+  const int bidx = (j + n - 2) % (n - 1);
+  double* vj = h->d_V + (int64_t)j * h->ldv;
+  LZ_TRY(one_sweep_step(h, n, j, st, j > 0));
+  int npa = 0;
+  if (j == 0) {  // step 0 is the unfused form's: V[0] is in place, a plain SpMV
+    Scope sc(h, LZ_K_SPMV, spmv_bytes(h), spmv_flops(h));
+    npa = launch_spmv_csr(h->csr, vj, h->d_r, vj, h->d_part, h->flags, h->stream);
+    LZ_TRY(check_launch(h, "spmv"));
+  } else {
+    LZ_TRY(one_sweep_scaling_spmv(h, n, j, h->d_r2, h->d_r, &npa));
+  }
+  {  // alpha_j from the SpMV's partials and the next step's predictions, one launch
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_os_sum_predict(h->d_part, npa, h->d_alpha + j, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, true, j + 1 < n, h->stream);
+    LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+  }
+  return LZ_OK;
+}
+int run_loop_one_sweep_fused(lz_handle h, int n) {
   OneSweepState st;
   LZ_TRY(one_sweep_setup(h, n, st));
   h->last_os_fused = 1;
+  h->last_os_pairs = 0;
   LZ_TRY(step_spmv(h, 0));
   LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
   for (int j = 0; j < n; ++j) {
     const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
     h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
-    double* vj = h->d_V + (int64_t)j * h->ldv;
-    LZ_TRY(one_sweep_step(h, n, j, st, j > 0));
-    int npa = 0;
-    if (j == 0) {  // step 0 is the unfused form's: V[0] is in place, a plain SpMV
-      Scope sc(h, LZ_K_SPMV, spmv_bytes(h), spmv_flops(h));
-      npa = launch_spmv_csr(h->csr, vj, h->d_r, vj, h->d_part, h->flags, h->stream);
-      LZ_TRY(check_launch(h, "spmv"));
-    } else {
-      SpmvScale ss;
-      ss.r = h->d_r2;
-      ss.nrm2 = h->d_nrm2;
-      ss.vj = vj;
-      ss.beta_slot = h->d_beta + bidx;
-      ss.gate = h->d_osi + 2;  // always 0: scale on read
-      // (bytes as the partial loop counts its fused SpMV: with a row-class coded matrix u~ once, y, V[j] and the class byte)
-      Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
-      npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream, &ss);
-      LZ_TRY(check_launch(h, "spmv(ell, scale fused)"));
-    }
-    {  // alpha_j from the SpMV's partials and the next step's predictions, one launch
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_sum_predict(h->d_part, npa, h->d_alpha + j, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, true, j + 1 < n, h->stream);
-      LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
-    }
+    LZ_TRY(one_sweep_fused_iter(h, n, j, st));
   }
   // r = (A v_{n-1} - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2}, ||r||^2: the residual entering step n
+  return step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 1 + n - 2) % (n - 1), true);
+}
+
+// The pair form of the fused loop: ONE walk over the basis per TWO steps.  A walk applies coefficients of size O(eps) and measures dots
+// already predicted to O(eps), so the correction step j owes to w_{j+1} is itself a combination of basis rows, exact to O(eps^2):
+// A (sum cn_i V_i) = sum_i cn_i sum_l H[l, i] V_l.  The SpMV therefore runs on the UNCORRECTED w_j / b (speculative; its dot is alpha_j,
+// O(eps) from v_j . A v_j), and one walk finishes v_j and forms u~_{j+1}, with two coefficient vectors and two dot vectors from the same
+// loads (k_os_pair_predict / k_os_pair_sweep / k_os_pair_post, lz_reorth.hip; tools/one_sweep_prototype.py, one_sweep_pair_lanczos).
+// beta_{j+1} = ||u~_{j+1}||, O(eps^2) from ||w_{j+1}||.  Nine launches and 8 j M + 40 M bytes of walk per pair instead of twice
+// 8 j M + 16 M.  Steps 0, 1 and an odd last step are the single fused form's.  A pair has no correcting sweep: a leftover above
+// kOneSweepTau sets a sticky device flag, and lz_run repeats the run on the single form (and remembers it until the matrix is set again).
+bool one_sweep_pair_applies(lz_handle h, int n) {
+  const int knob = h->tune[15];
+  return one_sweep_fused_applies(h, n) && knob != 6 && n >= 4 && qtw_ldp(n + 1) <= kOneSweepPairMaxLdp && !h->pair_tripped;
+}
+int run_loop_one_sweep_pair(lz_handle h, int n) {
+  const double M = (double)h->rows;
+  const bool wide16 = h->tune[15] == 9;  // (A/B: 16 positions per lane on long vectors)
+  OneSweepState st;
+  const int nbp = os_pair_sweep_blocks(h->rows_pad, wide16);
+  LZ_TRY(one_sweep_setup(h, n, st, nbp));
+  h->last_os_fused = 1;
+  h->last_os_pairs = 0;
+  double* kap = st.g;  // (the correcting sweep's coefficient buffers are free while a pair runs)
+  double* pp = st.g + n + 1;
+  LZ_TRY(step_spmv(h, 0));
+  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
+  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
+  auto sampled = [&](int j) { return (j % pstride) == pstride / 2; };
+  for (int j = 0; j < n;) {
+    if (j < 2 || j + 1 >= n) {
+      h->prof_iter = sampled(j);
+      LZ_TRY(one_sweep_fused_iter(h, n, j, st));
+      j += 1;
+      continue;
+    }
+    h->prof_iter = sampled(j) || sampled(j + 1);
+    // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-1} v_{j-2} -> d_r, ||w_j||^2 -> d_nrm2
+    LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
+    int npa = 0;
+    LZ_TRY(one_sweep_scaling_spmv(h, n, j, h->d_r, h->d_r2, &npa));  // y° = A (w_j / b); the V[j] it stores is provisional
+    const int ldp = os_pair_ldp(j);
+    {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_os_pair_predict(h->d_part, npa, h->d_alpha + j, h->d_nrm2, st.chat, st.G, st.H, n, j, kap, pp, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep pair predict"));
+    }
+    {
+      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 40.0 * M, 8.0 * (j + 1) * M);
+      launch_os_pair_sweep(h->d_V, h->ldv, h->rows_pad, j, st.chat, kap, h->d_r, h->d_r2, h->d_nrm2, h->d_alpha + j, h->d_part, wide16, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep pair walk"));
+    }
+    {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_final_rows_t(h->d_part, nbp, 2 * ldp, ldp + j + 2, h->d_c, h->stream);
+      LZ_TRY(check_launch(h, "final_rows(one-sweep pair)"));
+      launch_os_pair_post(h->d_c, ldp, st.chat, kap, pp, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, kOneSweepTau, h->d_osi, st.elog, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep pair post"));
+    }
+    LZ_TRY(one_sweep_scaling_spmv(h, n, j + 1, h->d_r2, h->d_r, &npa));  // V[j+1] = u~_{j+1} / beta_{j+1}, y = A V[j+1]
+    {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 1), st.G, st.H, n, j + 1, h->d_alpha + (j + 1), h->d_beta + j, st.chat, true,
+                            j + 2 < n, h->stream);
+      LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+    }
+    h->last_os_pairs += 1;
+    j += 2;
+  }
   return step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 1 + n - 2) % (n - 1), true);
 }
 
@@ -590,7 +672,8 @@ Loop choose_loop(lz_handle h, int n) {
 #endif
   // one-sweep loop: one rank, full fused-norm re-orthogonalisation, default kernels, no overlap; tune[15] == 6 forces it at any size
   const bool one_sweep_ok = one_rank && full_fused && default_kernels && !(f & LZ_FLAG_OVERLAP_HALO) && n >= 2 && n <= kOneSweepMaxN;
-  if ((h->tune[15] == 6 || h->tune[15] == 7) && one_sweep_ok) return LOOP_ONE_SWEEP;  // (7: never the fused form, A/B)
+  // (7: never the fused form; 6: never the pair form; 8 / 9: the pair form where it applies, 8 / 16 positions per lane in its walk - A/B)
+  if (h->tune[15] >= 6 && h->tune[15] <= 9 && one_sweep_ok) return LOOP_ONE_SWEEP;
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
   if (one_rank && h->qplan.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)h->qplan.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;
@@ -1090,7 +1173,10 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   const Loop loop = choose_loop(h, n);
   const bool one_reduce = loop == LOOP_ONE_REDUCE || loop == LOOP_PARTIAL_ONE_REDUCE;
   int sweeps = n;
+  bool tried_pairs = false;
   h->last_engine = (int)loop;
+  h->last_os_pairs = 0;
+  h->last_pair_abandoned = 0;
   switch (loop) {
 #ifdef LZ_KBENCH
     case LOOP_SMALL_ENGINE:
@@ -1109,7 +1195,10 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
     case LOOP_ONE_REDUCE: LZ_TRY(run_loop_onereduce(h, n)); break;
     case LOOP_PARTIAL_DEVICE: LZ_TRY(run_loop_partial_device(h, n)); break;
     case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
-    case LOOP_ONE_SWEEP: LZ_TRY(one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n)); break;
+    case LOOP_ONE_SWEEP:
+      tried_pairs = one_sweep_pair_applies(h, n);
+      LZ_TRY(tried_pairs ? run_loop_one_sweep_pair(h, n) : one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n));
+      break;
     default: LZ_TRY(run_loop_six(h, n, &sweeps)); break;
   }
   h->last_sweeps = sweeps;
@@ -1124,7 +1213,9 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   double onered_bad = 0.0;
   if (one_reduce) LZ_HIP(h, hipMemcpyAsync(&onered_bad, h->d_nrm2 + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   int gate_trips = 0;
+  int pair_flag = 0;
   if (loop == LOOP_ONE_SWEEP) LZ_HIP(h, hipMemcpyAsync(&gate_trips, h->d_osi + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (tried_pairs) LZ_HIP(h, hipMemcpyAsync(&pair_flag, h->d_osi + 3, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   std::vector<int> sweep_log;
   if (loop == LOOP_PARTIAL_DEVICE || loop == LOOP_PARTIAL_ONE_REDUCE) {
     sweep_log.resize(loop == LOOP_PARTIAL_DEVICE ? omega_state_ints(n) : omega_onered_ints(n));
@@ -1154,6 +1245,15 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
     const int rc = lz_run(h, n, v0_local, alpha_out, beta_out);
     h->flags = keep;
     h->last_engine = LOOP_ONE_REDUCE_REPEATED;
+    return rc;
+  }
+  if (pair_flag) {
+    // a pair's prediction missed by more than kOneSweepTau (k_os_pair_post): a pair has no correcting sweep, so the whole solve is
+    // repeated on the single fused form, whose gate corrects such steps; remembered until the matrix is set again
+    h->run_timed = false;
+    h->pair_tripped = true;
+    const int rc = lz_run(h, n, v0_local, alpha_out, beta_out);
+    h->last_pair_abandoned = 1;
     return rc;
   }
   if (dbg)

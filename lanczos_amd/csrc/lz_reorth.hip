@@ -1741,4 +1741,374 @@ void launch_os_sum_predict(const double* part, int np, double* sum_out, const do
     hipLaunchKernelGGL(k_os_sum_predict<false>, dim3(1), dim3(kFinalThreads), 0, s, part, np, sum_out, G, H, n, j, alpha_j, beta_j, chat, predict ? 1 : 0);
 }
 
+// ------------------------------------------------------------------ one-sweep loop, pair form: one walk per two steps
+// (run_loop_one_sweep_pair, lz_loops.hip; the arithmetic is tools/one_sweep_prototype.py's one_sweep_pair_lanczos, name for name.)
+// The speculative SpMV has left y° = A (w_j / b) and its alpha° partials.  The walk of step j applies only cn = c_hat / b = O(eps), so
+// what it owes to w_{j+1} is a combination of basis rows: A (sum cn_i V_i) = sum_i cn_i sum_l H[l, i] V_l.
+//
+// k_os_pair_predict, one block: a0 = alpha° (stored as alpha_j); column j - 1 of H gets step j's applied coefficients (H[:j, j-1] += b cn,
+// H[j, j-1] = b - known before the walk, because a pair applies the predictions and nothing else); then
+//   mu = H[:j+1, :j] cn,   gp = [cn - G[:j, :j] cn, 1],   q = H[:j, :j]^T cn + H[j, :j],   vAv = a0 - 2 cn . q
+//   p_i = sum_l H[l, i] gp_l - a0 gp_i - b G[i, j-1]  (i < j),   p_j = vAv - a0 gp_j - b gp_{j-1}      (the predictions V_i . w_{j+1})
+//   kap = mu - a0 [cn, 0] + p                                     (what the walk subtracts from z to leave u~_{j+1})
+// mu is a sum along ROWS of the column-major H: thread l of a chunk adds every nchunk-th column (coalesced in l), the chunks' sums are
+// added in order.  Every other sum is os_wave_dots' fixed tree.
+__global__ __launch_bounds__(kFinalThreads) void k_os_pair_predict(const double* __restrict__ part, int np, double* __restrict__ alpha_out,
+                                                                  const double* __restrict__ nrm2, const double* __restrict__ chat,
+                                                                  const double* __restrict__ G, double* __restrict__ H, int n, int j,
+                                                                  double* __restrict__ kap, double* __restrict__ pout) {
+  extern __shared__ double smem[];  // cn, gp, q, mu: j + 1 each; then the chunk sums of mu (kFinalThreads)
+  double* cn = smem;
+  double* gp = cn + (j + 1);
+  double* q = gp + (j + 1);
+  double* mu = q + (j + 1);
+  double* red = mu + (j + 1);
+  __shared__ double sm[kFinalThreads / 64];
+  __shared__ double s_a0, s_cq;
+  const double t0 = final_sum_1024(part, np, sm);
+  if (threadIdx.x == 0) {
+    alpha_out[0] = t0;
+    s_a0 = t0;
+  }
+  const double b = sqrt(nrm2[0]);
+  double* hc = H + (int64_t)(j - 1) * n;
+  for (int i = threadIdx.x; i < j; i += blockDim.x) {
+    const double ci = chat[i] / b;
+    cn[i] = ci;
+    hc[i] = hc[i] + b * ci;
+  }
+  if (threadIdx.x == 0) {
+    hc[j] = b;
+    cn[j] = 0.0;
+    gp[j] = 1.0;
+  }
+  __syncthreads();
+  const double a0 = s_a0;
+  os_wave_dots(
+      j, [&](int i) { return G + (int64_t)i * n; }, [&](int l) { return cn[l]; }, [&](int) { return j; },
+      [&](int i, double t) { gp[i] = cn[i] - t; });
+  os_wave_dots(
+      j, [&](int i) { return (const double*)(H + (int64_t)i * n); }, [&](int l) { return cn[l]; }, [&](int i) { return min(i + 2, j); },
+      [&](int i, double t) { q[i] = i == j - 1 ? t + b : t; });  // (H[j, i] is b at i = j - 1 and 0 before it)
+  {
+    const int Lp = (j + 1 + 63) & ~63, nchunk = kFinalThreads / Lp;  // j + 1 <= 1024 (os_pair_applies)
+    const int l = threadIdx.x % Lp, ch = threadIdx.x / Lp;
+    if (ch < nchunk) {
+      double acc = 0.0;
+      if (l <= j) {
+        int i = ch;  // H[l, i] is 0 for i < l - 1: start at the first column of this chunk that is not
+        if (i < l - 1) i += (l - 1 - i + nchunk - 1) / nchunk * nchunk;
+        for (; i < j; i += nchunk) acc = fma(H[(int64_t)i * n + l], cn[i], acc);
+      }
+      red[ch * Lp + l] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x <= j) {
+      double m = 0.0;
+      for (int c = 0; c < nchunk; ++c) m += red[c * Lp + threadIdx.x];
+      mu[threadIdx.x] = m;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < j; i += 64) acc = fma(cn[i], q[i], acc);
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) s_cq = acc;
+  }
+  __syncthreads();
+  const double* gm = G + (int64_t)(j - 1) * n;
+  os_wave_dots(
+      j, [&](int i) { return (const double*)(H + (int64_t)i * n); }, [&](int l) { return gp[l]; }, [&](int i) { return i + 2; },
+      [&](int i, double t) {
+        const double pi = (t - a0 * gp[i]) - b * gm[i];
+        pout[i] = pi;
+        kap[i] = (mu[i] - a0 * cn[i]) + pi;
+      });
+  if (threadIdx.x == 0) {
+    const double vAv = a0 - 2.0 * s_cq;
+    const double pj = (vAv - a0 * gp[j]) - b * gp[j - 1];
+    pout[j] = pj;
+    kap[j] = mu[j] + pj;
+  }
+}
+
+void launch_os_pair_predict(const double* part, int np, double* alpha_out, const double* nrm2, const double* chat, const double* G, double* H,
+                            int n, int j, double* kap, double* p, hipStream_t s) {
+  const size_t lds = ((size_t)4 * (j + 1) + kFinalThreads) * sizeof(double);
+  hipLaunchKernelGGL(k_os_pair_predict, dim3(1), dim3(kFinalThreads), lds, s, part, np, alpha_out, nrm2, chat, G, H, n, j, kap, p);
+}
+
+// The one walk of a pair (j >= 2), k_os_sweep's slice-owner shape with two vectors: w = w_j (wbuf, the three-term kernel's) and
+//   z = (y° - a0 w / b) - b V[j-1]                        (the speculative three-term step; y° in ybuf, formed in the prologue)
+// Row j - 1 is consumed in the prologue that loads it anyway, the walk covers rows 0 .. j-2: per row two running sums (c_hat against w,
+// kap against z) and two dots from the same loads.  Epilogue: u~ = w - sum c_hat_i V_i, v_j = u~ / b -> V[j];
+// u~_{j+1} = (z - sum kap_i V_i) - kap_j v_j -> ybuf, in place (each position is read and written by the same lane).
+// Per wave in LDS, one run of 2 ldp doubles per block in part: [V_i . w (i < j), u~ . u~ | V_i . z (i < j), v_j . z, u~_{j+1} . u~_{j+1}].
+// Positions are 32-bit (n2 < 2^30); out-of-range positions are clamped to a valid address and zeroed, so they add nothing.
+template <int P, int RU>
+__global__ __launch_bounds__(kTPB) void k_os_pair_sweep(const double* __restrict__ V, double* __restrict__ vj, int64_t ldv, int n2, int j,
+                                                       const double* __restrict__ chat, const double* __restrict__ kap,
+                                                       const double* __restrict__ wbuf, double* __restrict__ ybuf,
+                                                       const double* __restrict__ nrm2, const double* __restrict__ alpha0, int ldp,
+                                                       double* __restrict__ part) {
+  extern __shared__ double keep[];  // [kTPB / 64][2 ldp]: this block's per-wave dots
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
+  const int64_t ld2 = ldv >> 1;
+  const double2* V2 = reinterpret_cast<const double2*>(V);
+  double2* y2 = reinterpret_cast<double2*>(ybuf);
+  double* kw = keep + wv * 2 * ldp;
+  int pos[P];
+  bool ok[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    ok[p] = base + (int64_t)p * kTPB < n2;
+    pos[p] = ok[p] ? (int)(base + (int64_t)p * kTPB) : n2 - 1;  // valid address, result discarded
+  }
+  const double b = sqrt(nrm2[0]), a0 = alpha0[0];
+  double2 w[P], z[P];
+  double tx[P], ty[P], sx[P], sy[P];  // running sums: c_hat against w, kap against z
+  {
+    const double c1 = chat[j - 1], k1 = kap[j - 1];
+    const double2* w2 = reinterpret_cast<const double2*>(wbuf);
+    const double2* v1 = V2 + (int64_t)(j - 1) * ld2;
+    double d1 = 0.0, d2 = 0.0;
+    constexpr int PB = P < 8 ? P : 8;  // positions per batch: 3 PB loads in flight
+#pragma unroll
+    for (int p0 = 0; p0 < P; p0 += PB) {
+      double2 x[PB], y[PB], m[PB];
+#pragma unroll
+      for (int q = 0; q < PB; ++q) {
+        x[q] = w2[pos[p0 + q]];
+        y[q] = y2[pos[p0 + q]];
+        m[q] = ld_stream<1>(v1 + pos[p0 + q]);
+      }
+#pragma unroll
+      for (int q = 0; q < PB; ++q) {
+        const int p = p0 + q;
+        double2 zz;
+        zz.x = (y[q].x - a0 * (x[q].x / b)) - b * m[q].x;
+        zz.y = (y[q].y - a0 * (x[q].y / b)) - b * m[q].y;
+        if (!ok[p]) {  // so the clamped duplicates add nothing to the dots
+          x[q] = make_double2(0.0, 0.0);
+          zz = make_double2(0.0, 0.0);
+        }
+        w[p] = x[q];
+        z[p] = zz;
+        d1 = fma(m[q].x, x[q].x, d1);
+        d1 = fma(m[q].y, x[q].y, d1);
+        d2 = fma(m[q].x, zz.x, d2);
+        d2 = fma(m[q].y, zz.y, d2);
+        tx[p] = c1 * m[q].x;
+        ty[p] = c1 * m[q].y;
+        sx[p] = k1 * m[q].x;
+        sy[p] = k1 * m[q].y;
+      }
+      __builtin_amdgcn_sched_barrier(0);  // (keeps the next batch's loads behind this batch's arithmetic)
+    }
+    d1 = wave_sum(d1);
+    d2 = wave_sum(d2);
+    if (lane == 0) {
+      kw[j - 1] = d1;
+      kw[ldp + j - 1] = d2;
+    }
+  }
+  const int jw = j - 1;  // rows the walk covers
+  for (int k = 0; k < jw; k += RU) {
+    double2 q[RU][P];
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < jw) {  // block-uniform
+        const double2* row = V2 + (int64_t)(k + u) * ld2;
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(row + pos[p]);
+      }
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < jw) {
+        const double ck = chat[k + u], kk = kap[k + u];
+        double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          tx[p] = tx[p] + ck * q[u][p].x;
+          ty[p] = ty[p] + ck * q[u][p].y;
+          sx[p] = sx[p] + kk * q[u][p].x;
+          sy[p] = sy[p] + kk * q[u][p].y;
+          d1 = fma(q[u][p].x, w[p].x, d1);
+          d1 = fma(q[u][p].y, w[p].y, d1);
+          d2 = fma(q[u][p].x, z[p].x, d2);
+          d2 = fma(q[u][p].y, z[p].y, d2);
+        }
+        d1 = wave_sum(d1);
+        d2 = wave_sum(d2);
+        if (lane == 0) {
+          kw[k + u] = d1;
+          kw[ldp + k + u] = d2;
+        }
+      }
+  }
+  const double kj = kap[j];
+  double2* vo = reinterpret_cast<double2*>(vj);
+  double uu = 0.0, vz = 0.0, uu2 = 0.0;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const double2 ut = make_double2(w[p].x - tx[p], w[p].y - ty[p]);
+    const double2 v = make_double2(ut.x / b, ut.y / b);
+    const double2 u2 = make_double2((z[p].x - sx[p]) - kj * v.x, (z[p].y - sy[p]) - kj * v.y);
+    if (ok[p]) {
+      st_stream<1>(vo + pos[p], v);
+      y2[pos[p]] = u2;
+      uu = fma(ut.x, ut.x, uu);
+      uu = fma(ut.y, ut.y, uu);
+      vz = fma(v.x, z[p].x, vz);
+      vz = fma(v.y, z[p].y, vz);
+      uu2 = fma(u2.x, u2.x, uu2);
+      uu2 = fma(u2.y, u2.y, uu2);
+    }
+  }
+  uu = wave_sum(uu);
+  vz = wave_sum(vz);
+  uu2 = wave_sum(uu2);
+  if (lane == 0) {
+    kw[j] = uu;
+    kw[ldp + j] = vz;
+    kw[ldp + j + 1] = uu2;
+  }
+  __syncthreads();
+  double* mine = part + (int64_t)blockIdx.x * (2 * ldp);
+  for (int i = threadIdx.x; i < 2 * ldp; i += kTPB) {
+    const bool used = i < ldp ? i <= j : i - ldp <= j + 1;  // (the unused slots leave as zeros, not as whatever the LDS held)
+    const double t = used ? ((keep[i] + keep[2 * ldp + i]) + keep[4 * ldp + i]) + keep[6 * ldp + i] : 0.0;
+    __builtin_nontemporal_store(t, mine + i);
+  }
+}
+
+// positions per lane of the pair walk: 8 (two waves per SIMD) or 16 (one wave) for long vectors - wide16 chooses -, else os_sweep_p's choice
+static int os_pair_sweep_p(int64_t n2, bool wide16) {
+  const int P = os_sweep_p(n2);
+  return P >= 8 ? (wide16 ? 16 : 8) : P;
+}
+int os_pair_sweep_blocks(int64_t len, bool wide16) {
+  const int64_t n2 = len >> 1;
+  const int P = os_pair_sweep_p(n2, wide16);
+  return (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+}
+int os_pair_ldp(int j) { return qtw_ldp(j + 2); }
+
+int launch_os_pair_sweep(double* V, int64_t ldv, int64_t len, int j, const double* chat, const double* kap, const double* w, double* y,
+                         const double* nrm2, const double* alpha0, double* part, bool wide16, hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  const int P = os_pair_sweep_p(n2, wide16);
+  const int grid = (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+  const int ldp = os_pair_ldp(j);
+  const size_t lds = (size_t)(kTPB / 64) * 2 * ldp * sizeof(double);
+#define LZ_OSP_GO(PP, RR)                                                                                                                  \
+  hipLaunchKernelGGL((k_os_pair_sweep<PP, RR>), dim3(grid), dim3(kTPB), lds, s, V, V + (int64_t)j * ldv, ldv, (int)n2, j, chat, kap, w, y, nrm2, \
+                     alpha0, ldp, part)
+  switch (P) {
+    case 16: LZ_OSP_GO(16, 1); break;
+    case 8: LZ_OSP_GO(8, 1); break;
+    case 4: LZ_OSP_GO(4, 2); break;
+    case 2: LZ_OSP_GO(2, 4); break;
+    default: LZ_OSP_GO(1, 8); break;
+  }
+#undef LZ_OSP_GO
+  return grid;
+}
+
+// k_os_pair_post, one block: d = the second-stage sums of the walk's two runs (run length ldp).  First step: dn = d1 / b against cn = c_hat / b
+// (e1), G[:, j] = [dn - G[:j, :j] cn, u~ . u~ / ||w||^2].  Second step: b2 = sqrt(u~_{j+1} . u~_{j+1}) = beta_{j+1}, G[:j, j+1] =
+// (d2 - G[:j, :j+1] kap) / b2, G[j, j+1] = (v_j . z - G[j, :j+1] kap) / b2, G[j+1, j+1] = 1, e2 = max |G[:j+1, j+1]|; column j of H =
+// p + alpha_j e_j + b e_{j-1} + b2 e_{j+1}.  ||u~_{j+1}||^2 is left in nrm2[0] for the SpMV that scales it.  A pair has no correcting sweep: a
+// leftover above tau (or a NaN) sets the sticky flag ist[3], and lz_run repeats the run on the single form.
+__global__ __launch_bounds__(kFinalThreads) void k_os_pair_post(const double* __restrict__ d, int ldp, const double* __restrict__ chat,
+                                                               const double* __restrict__ kap, const double* __restrict__ pin,
+                                                               double* __restrict__ G, double* __restrict__ H, int n, int j,
+                                                               double* __restrict__ nrm2, const double* __restrict__ alpha_j, double tau,
+                                                               int* __restrict__ ist, double* __restrict__ elog) {
+  extern __shared__ double smem[];  // cn, dn [j]; kp, colj, col2 [j + 1]
+  double* cn = smem;
+  double* dn = cn + j;
+  double* kp = dn + j;
+  double* colj = kp + (j + 1);
+  double* col2 = colj + (j + 1);
+  __shared__ double smax[2][kFinalThreads / 64];
+  const double s2 = nrm2[0], b = sqrt(s2);
+  const double uu = d[j], vz = d[ldp + j], uu2 = d[ldp + j + 1], b2 = sqrt(uu2), a0 = alpha_j[0];
+  auto wave_max = [&](double em, double* dst) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) em = fmax(em, __shfl_down(em, off, 64));
+    if ((threadIdx.x & 63) == 0) dst[threadIdx.x >> 6] = em;
+  };
+  double em = 0.0;
+  for (int i = threadIdx.x; i < j; i += blockDim.x) {
+    const double di = d[i] / b, ci = chat[i] / b;
+    const double e = fabs(di - ci);
+    em = e == e ? fmax(em, e) : __builtin_inf();  // (a NaN leftover must trip: fmax would drop it)
+    dn[i] = di;
+    cn[i] = ci;
+    kp[i] = kap[i];
+  }
+  if (threadIdx.x == 0) {
+    kp[j] = kap[j];
+    colj[j] = uu / s2;
+  }
+  wave_max(em, smax[0]);
+  __syncthreads();
+  os_wave_dots(
+      j, [&](int i) { return (const double*)(G + (int64_t)i * n); }, [&](int l) { return cn[l]; }, [&](int) { return j; },
+      [&](int i, double t) { colj[i] = dn[i] - t; });
+  __syncthreads();
+  os_wave_dots(
+      j, [&](int i) { return (const double*)(G + (int64_t)i * n); }, [&](int l) { return kp[l]; }, [&](int) { return j; },
+      [&](int i, double t) { col2[i] = (d[ldp + i] - (t + colj[i] * kp[j])) / b2; });
+  if (threadIdx.x < 64) {
+    double acc = 0.0;
+    for (int l = threadIdx.x; l < j; l += 64) acc = fma(colj[l], kp[l], acc);
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) col2[j] = (vz - (acc + colj[j] * kp[j])) / b2;
+  }
+  __syncthreads();
+  em = 0.0;
+  for (int i = threadIdx.x; i <= j; i += blockDim.x) {
+    const double e = fabs(col2[i]);
+    em = e == e ? fmax(em, e) : __builtin_inf();
+  }
+  wave_max(em, smax[1]);
+  for (int i = threadIdx.x; i <= j; i += blockDim.x) {
+    G[(int64_t)j * n + i] = colj[i];
+    G[(int64_t)i * n + j] = colj[i];
+    G[(int64_t)(j + 1) * n + i] = col2[i];
+    G[(int64_t)i * n + j + 1] = col2[i];
+  }
+  double* hc = H + (int64_t)j * n;
+  for (int l = threadIdx.x; l < n; l += blockDim.x) {
+    double v = l <= j ? pin[l] : 0.0;
+    if (l == j - 1) v = b + v;
+    if (l == j) v = a0 + v;
+    if (l == j + 1) v = b2;
+    hc[l] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double m1 = 0.0, m2 = 0.0;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
+      m1 = fmax(m1, smax[0][k]);
+      m2 = fmax(m2, smax[1][k]);
+    }
+    G[(int64_t)(j + 1) * n + j + 1] = 1.0;
+    nrm2[0] = uu2;
+    elog[j] = m1;
+    elog[j + 1] = m2;
+    if (!(m1 <= tau) || !(m2 <= tau) || !(b2 == b2)) ist[3] = 1;
+  }
+}
+
+void launch_os_pair_post(const double* d, int ldp, const double* chat, const double* kap, const double* p, double* G, double* H, int n, int j,
+                         double* nrm2, const double* alpha_j, double tau, int* ist, double* elog, hipStream_t s) {
+  const size_t lds = ((size_t)2 * j + (size_t)3 * (j + 1)) * sizeof(double);
+  hipLaunchKernelGGL(k_os_pair_post, dim3(1), dim3(kFinalThreads), lds, s, d, ldp, chat, kap, p, G, H, n, j, nrm2, alpha_j, tau, ist, elog);
+}
+
 }  // namespace lz

@@ -264,6 +264,151 @@ def one_sweep_fused_lanczos(H, n, seed=99, v0=None, tau=1e-14):
     return alpha, bet[1:], V, stats
 
 
+def one_sweep_pair_lanczos(H, n, seed=99, v0=None, tau=1e-14):
+    """The pair form of the loop (run_loop_one_sweep_pair): one walk over the basis per two steps.  Steps 0, 1 and an odd last
+    step are the fused single form's.  A pair at step j takes the speculative SpMV of the uncorrected vo = w_j / b; the correction
+    step j owes to w_{j+1} is a combination of basis rows, A (sum cn_i V_i) = sum_i cn_i sum_l H[l, i] V_l, so the one walk over
+    rows 0..j-1 finishes v_j and forms u~_{j+1} = z - sum kap_i V_i with the dots of both.  alpha_j is the speculative SpMV's own
+    dot and beta_{j+1} = ||u~_{j+1}||.  There is no correcting sweep in a pair: a leftover above tau (or a NaN) marks the run as
+    abandoned (stats["abandoned"]); e1 / e2 hold the leftovers of the first / second step of every pair."""
+    H = scipy.sparse.csr_matrix(H)
+    M = H.shape[0]
+    V = np.zeros((n, M))
+    V[0] = start_vector(M, seed, v0)
+    alpha = np.zeros(n)
+    bet = np.zeros(n)
+    G = np.zeros((n, n))
+    Hm = np.zeros((n, n))
+    y = H @ V[0]
+    alpha[0] = np.dot(y, V[0])
+    r = y - alpha[0] * V[0]
+    emax = np.zeros(n)
+    e1s, e2s = np.zeros(n), np.zeros(n)
+    trips = []
+    abandoned = False
+    pairs = 0
+    chat = np.zeros(0)
+
+    def closing(j, b):  # y = A V[j], alpha[j], the H entries of step j and the un-normalised predictions V_i . w_{j+1}
+        y = H @ V[j]
+        alpha[j] = np.dot(V[j], y)
+        Hm[j, j] += alpha[j]
+        if j:
+            Hm[j - 1, j] += b
+        p = np.zeros(0)
+        if j + 1 < n:
+            p = np.empty(j + 1)
+            p[:j] = (Hm[: j + 1, :j] * G[: j + 1, j][:, None]).sum(axis=0) if j else p[:j]
+            p[j] = alpha[j]
+            p = p - alpha[j] * G[: j + 1, j]
+            if j:
+                p = p - b * G[: j + 1, j - 1]
+        return y, p
+
+    j = 0
+    while j < n:
+        if j >= 2 and j + 1 < n:
+            pairs += 1
+            w = y - alpha[j - 1] * V[j - 1] - bet[j - 1] * V[j - 2]
+            nrm2 = np.dot(w, w)
+            b = np.sqrt(nrm2)
+            cn = chat / b
+            vo = w / b
+            yo = H @ vo
+            a0 = np.dot(vo, yo)
+            z = yo - a0 * vo - b * V[j - 1]
+            Hc = Hm[: j + 1, :j].copy()
+            Hc[j, j - 1] += b
+            Hc[:j, j - 1] += b * cn
+            mu = Hc @ cn
+            gam = mu.copy()
+            gam[:j] -= a0 * cn
+            gp = np.concatenate([cn - G[:j, :j] @ cn, [1.0]])
+            q = Hc[:j, :].T @ cn + Hc[j, :]
+            vAv = a0 - 2.0 * np.dot(cn, q)
+            p = np.empty(j + 1)
+            p[:j] = (Hc * gp[:, None]).sum(axis=0) - a0 * gp[:j] - b * G[:j, j - 1]
+            p[j] = vAv - a0 * gp[j] - b * gp[j - 1]
+            kap = gam + p
+            # the one walk over rows 0..j-1
+            ut = w - chat @ V[:j]
+            d1 = V[:j] @ w
+            v = ut / b
+            d2 = V[:j] @ z
+            vz = np.dot(v, z)
+            ut2 = z - kap[:j] @ V[:j] - kap[j] * v
+            uu = np.dot(ut, ut)
+            uu2 = np.dot(ut2, ut2)
+            # post
+            dn = d1 / b
+            e1 = np.abs(dn - cn).max()
+            G[:j, j] = dn - G[:j, :j] @ cn
+            G[j, j] = uu / nrm2
+            G[j, :j] = G[:j, j]
+            Hm[j, j - 1] += b
+            Hm[:j, j - 1] += b * cn
+            alpha[j] = a0
+            Hm[j, j] += a0
+            Hm[j - 1, j] += b
+            bet[j] = b
+            V[j] = v
+            b2 = np.sqrt(uu2)
+            G[:j, j + 1] = (d2 - G[:j, : j + 1] @ kap) / b2
+            G[j, j + 1] = (vz - G[j, : j + 1] @ kap) / b2
+            G[j + 1, j + 1] = 1.0
+            G[j + 1, : j + 1] = G[: j + 1, j + 1]
+            e2 = np.abs(G[: j + 1, j + 1]).max()
+            V[j + 1] = ut2 / b2
+            bet[j + 1] = b2
+            Hm[j + 1, j] += b2
+            Hm[: j + 1, j] += p
+            e1s[j], e2s[j + 1] = e1, e2
+            emax[j], emax[j + 1] = e1, e2
+            if not (e1 <= tau and e2 <= tau):  # (a NaN fails both comparisons)
+                abandoned = True
+            y, chat = closing(j + 1, b2)
+            j += 2
+            continue
+        if j == 0:
+            nrm2 = np.dot(r, r)
+            b = np.sqrt(nrm2)
+            cs = nrm2 / (b * b)
+            u = r / b
+            v = 2 * u - cs * u
+            col = np.array([np.dot(v, v)])
+        else:
+            w = y - alpha[j - 1] * V[j - 1]
+            if j >= 2:
+                w = w - bet[j - 1] * V[j - 2]
+            t = chat @ V[:j]
+            ut = 2 * w - (t + w)
+            d = V[:j] @ w
+            nrm2 = np.dot(w, w)
+            b = np.sqrt(nrm2)
+            dn, cn = d / b, chat / b
+            emax[j] = np.abs(dn - cn).max()
+            col = np.concatenate([dn - G[:j, :j] @ cn, [np.dot(ut, ut) / nrm2]])
+            capp = cn.copy()
+            if emax[j] > tau:
+                trips.append(j)
+                g = col[:j].copy()
+                ut = ut - (b * g) @ V[:j]
+                Gjj = G[:j, :j]
+                col = np.concatenate([col[:j] - Gjj @ g, [col[j] - 2.0 * g @ col[:j] + g @ Gjj @ g]])
+                capp = capp + g
+            v = ut / b
+            Hm[j, j - 1] += b
+            Hm[:j, j - 1] += b * capp
+        bet[j] = b
+        V[j] = v
+        G[: j + 1, j] = col
+        G[j, : j + 1] = col
+        y, chat = closing(j, b)
+        j += 1
+    stats = {"emax": emax, "e1": e1s, "e2": e2s, "trips": trips, "G": G, "abandoned": abandoned, "pairs": pairs}
+    return alpha, bet[1:], V, stats
+
+
 def report_case(name, H, n, seed=99, v0=None):
     t0 = time.perf_counter()
     H = scipy.sparse.csr_matrix(H)
