@@ -145,6 +145,21 @@ def test_fused_equals_unfused_at_every_sweep_width(hip, name):
     assert da <= 1e-12 * scale and db <= 1e-12 * scale and dr <= 1e-12 * scale
 
 
+# the same four shapes with the walks' row loops run through: at n = 21 the last walks cover 19 or 20 rows, so k_os_sweep<2, 8> sees
+# two full groups of rows and a tail, <4, 4> and <8, 2> several groups and a tail (n = 6 never completes a group of 8 or a second
+# iteration of k).  21 steps on 250 000 rows and more are far from breakdown on the periodic Laplacian
+@pytest.mark.parametrize("name", ["lap2d_big_500x500", "lap2d_big_1000x500", "lap2d_big_1000x1000", "lap2d_big_2000x1000"])
+def test_fused_equals_unfused_at_every_sweep_width_over_full_row_groups(hip, name):
+    n = 21
+    unf, got = _run_fresh(hip, name, n, UNFUSED, basis=False), _run_fresh(hip, name, n, FUSED, basis=False)
+    assert unf["engine"] == "one-sweep" and got["engine"] == "one-sweep"
+    assert unf["fused"] == 0 and got["fused"] == 1 and unf["trips"] == 0 and got["trips"] == 0
+    scale = np.abs(np.linalg.eigvalsh(oracle.build_h_eff(unf["a"], unf["b"]))).max()
+    da, db, dr = np.abs(got["a"] - unf["a"]).max(), np.abs(got["b"] - unf["b"]).max(), np.abs(got["r"] - unf["r"]).max()
+    print(f"\n[{name} n = {n}] max |dalpha| {da:.1e}, |dbeta| {db:.1e}, |dr| {dr:.1e} (scale {scale:.2f})")
+    assert da <= 1e-12 * scale and db <= 1e-12 * scale and dr <= 1e-12 * scale
+
+
 @pytest.mark.parametrize("n", [2, 3])
 def test_first_fused_steps(hip, n):
     # n = 2: the only fused step has no beta term; n = 3: the first step with one, and still no third row to walk

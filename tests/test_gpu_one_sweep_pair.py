@@ -162,6 +162,22 @@ def test_pair_equals_single_at_every_walk_width(hip, name, knob):
     assert da <= 1e-12 * scale and db <= 1e-12 * scale and dr <= 1e-12 * scale
 
 
+# the same shapes with the walks' row loops run through: at n = 21 the last pair walks 19 rows, so k_os_pair_sweep<2, 4> and <4, 2> see
+# several full groups of rows and a tail (n = 6: at most one group), and the single steps' k_os_sweep likewise.  21 steps on 250 000 rows
+# and more are far from breakdown on the periodic Laplacian
+@pytest.mark.parametrize("name,knob", [("lap2d_500x500", PAIR), ("lap2d_1000x500", PAIR), ("lap2d_1000x1000", PAIR), ("lap2d_2000x1000", PAIR),
+                                       ("lap2d_2000x1000", PAIR16)])
+def test_pair_equals_single_at_every_walk_width_over_full_row_groups(hip, name, knob):
+    n = 21
+    one, got = _run_fresh(hip, name, n, SINGLE, basis=False), _run_fresh(hip, name, n, knob, basis=False)
+    assert one["engine"] == "one-sweep" and one["fused"] == 1 and one["pairs"] == 0 and one["trips"] == 0
+    _assert_ran_pairs(got, n)
+    scale = np.abs(np.linalg.eigvalsh(oracle.build_h_eff(one["a"], one["b"]))).max()
+    da, db, dr = np.abs(got["a"] - one["a"]).max(), np.abs(got["b"] - one["b"]).max(), np.abs(got["r"] - one["r"]).max()
+    print(f"\n[{name}, knob {knob}, n = {n}] max |dalpha| {da:.1e}, |dbeta| {db:.1e}, |dr| {dr:.1e} (scale {scale:.2f})")
+    assert da <= 1e-12 * scale and db <= 1e-12 * scale and dr <= 1e-12 * scale
+
+
 def test_pair_rerun_is_bit_identical(hip):
     r1 = _run(hip, "lap2d_64x48", 60, PAIR)
     r2 = _run_fresh(hip, "lap2d_64x48", 60, PAIR)
