@@ -489,6 +489,54 @@ int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
 int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
 
+/* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
+ * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
+ * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart
+ * policy, stopping test: lanczos_amd/svds.py); these calls do every product and every pass over the two bases.  The state is separate
+ * from the handle's square operator: lz_set_*'s matrix, a fixed-n run's V / Y and a thick-restart basis on the same handle stay as
+ * they are.  One rank only: a handle with a communicator gets LZ_ERR_STATE.  LZ_FLAG_TRL_PASS2_ALWAYS forces the second Gram-Schmidt
+ * pass of every half step (tests), as it does for lz_trl_extend.
+ * A is p x q with p >= q (the caller passes the transpose of a wide matrix); U holds vectors of length p, V of length q.  `side`
+ * arguments: 0 = U, 1 = V. */
+/* A (p x q, p >= q >= 2) and its transpose (q x p), both CSR with sorted indices; p, q, nnz < 2^31.  Validated as lz_set_csr validates.
+ * Neither matrix gets any of the square SpMV layouts: their products run through the rectangular kernel only (row blocks in SciPy's
+ * csr_matvec order, bit-identical to it; a row longer than the LDS tile - 4096 entries, tuning knob 4 - is split into segments summed
+ * by one workgroup each and added in segment order: deterministic, but another order than SciPy's).  LZ_FLAG_SPMV_STREAM set at this
+ * call keeps every long row in one workgroup (the A/B arm of the segment path).  Drops a basis of an earlier matrix. */
+int lz_gk_set_csr(lz_handle h, int64_t p, int64_t q, int64_t nnz, const int32_t* rowptr, const int32_t* colidx, const double* vals,
+                  const int32_t* rowptrT, const int32_t* colidxT, const double* valsT);
+/* allocate and zero V (m + 1 rows of the padded q) and U (m + 1 rows of the padded p; row m stays zero), 2 <= m <= min(128, q);
+ * V[0] = v0 / |v0| (v0: q doubles) */
+int lz_gk_begin(lz_handle h, int m, const double* v0);
+/* steps j = k .. m-1 without a host synchronisation: w = A V[j] made orthogonal to U[0..j) (classical Gram-Schmidt, a second pass
+ * behind the DGKS gate, decided on the device), alpha_j = |w|, U[j] = w / alpha_j; z = A^T U[j] made orthogonal to V[0..j] likewise,
+ * beta_j = |z|, V[j + 1] = z / beta_j.  colproj_out (m x m row-major): row j receives the measured coefficients of A V[j] on U[0..j)
+ * (both passes' sums), rows k .. m-1 only; alpha_out[m], beta_out[m].  Any of the three may be NULL.
+ * When U[k] was made by lz_gk_probe(h, 0, k, ..) since the last extension, restart or begin - the fresh direction behind a vanished
+ * alpha_k - step k starts at its second half: A V[k] is not formed, row k of colproj_out and alpha_out[k] are not written. */
+int lz_gk_extend(lz_handle h, int k, int m, double* colproj_out, double* alpha_out, double* beta_out);
+/* in place: U[0..kk) = P^T U[0..m), V[0..kk) = Q^T V[0..m), V[kk] = V[m] (P, Q: m x kk row-major, 1 <= kk < m); U[kk] becomes the
+ * zero row U[m] */
+int lz_gk_restart(lz_handle h, int m, int kk, const double* P, const double* Q);
+/* row k of the side's basis = x (p or q doubles) made orthogonal to the rows below it by two Gram-Schmidt passes and normalised
+ * (U: 0 <= k < m, V: 0 <= k <= m): the fresh direction after a breakdown */
+int lz_gk_probe(lz_handle h, int side, int k, const double* x);
+/* the first k rows of the side's basis as a (p or q, k) row-major array, through the staging ring */
+int lz_gk_get_vectors(lz_handle h, int side, int k, double* out);
+/* raw rows j0 .. j0 + count - 1 (j0 + count <= m + 1) of the side's basis including their padding (lz_padded_rows(p or q) doubles
+ * each), host rows ld >= that apart: tests */
+int lz_gk_set_rows(lz_handle h, int side, int j0, int count, const double* rows, int64_t ld);
+int lz_gk_get_rows(lz_handle h, int side, int j0, int count, double* rows, int64_t ld);
+/* out[i] = |A V[i] - sigma[i] U[i]|, out[k + i] = |A^T U[i] - sigma[i] V[i]| for i < k (1 <= k <= m) */
+int lz_gk_residuals(lz_handle h, int k, const double* sigma, double* out);
+/* one product through the rectangular kernel on host vectors: y = A x (transpose == 0: x q doubles, y lz_padded_rows(p) doubles) or
+ * y = A^T x (x p doubles, y lz_padded_rows(q) doubles).  y receives the padding too, which the kernel writes as zeros.  Needs
+ * lz_gk_set_csr only; uses the work vectors of lz_gk_extend. */
+int lz_gk_spmv(lz_handle h, int transpose, const double* x, double* y);
+/* *ms_out = the device time (hipEvents) of one such product, the mean of reps launches behind one warm-up launch, on whatever the work
+ * vectors hold: the measurements of tools/svds_probe.py */
+int lz_gk_spmv_time(lz_handle h, int transpose, int reps, double* ms_out);
+
 /* ---- two-sided (bi-orthogonal) Lanczos: the Irregular copy's execute_Lanczos --------------------------------
  * Replaces Python/Irregular/IrrLanczos.py:77-187 (driver loop) and :408-441 (bireorthogonalize, default branch).
  * Single rank, CSR only.  Four (n, rows) bases live on the device: 0 = q (published as V: lz_get_basis /

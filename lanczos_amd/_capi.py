@@ -177,6 +177,17 @@ SIGNATURES = {
     "lz_trl_rayleigh": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_trl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
+    "lz_gk_begin": (C.c_int, [_P, C.c_int, _D]),
+    "lz_gk_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _D]),
+    "lz_gk_restart": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_gk_probe": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_gk_get_vectors": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_gk_set_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_gk_get_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_gk_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_gk_spmv": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_gk_spmv_time": (C.c_int, [_P, C.c_int, C.c_int, _D]),
 }
 
 
@@ -875,6 +886,75 @@ class Handle:
         out = np.empty((int(count), self.padded_rows(self.rows)))
         self.check(self.lib.lz_trl_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
         return out
+
+    # -- Golub-Kahan-Lanczos (lanczos_amd.svds): a rectangular operator and two bases of their own; side 0 = U (length p), 1 = V (length q)
+    def gk_set_csr(self, A, AT):
+        """``A`` (p x q, p >= q) and ``AT`` (its transpose) as SciPy CSR with sorted indices"""
+        p, q = A.shape
+        assert AT.shape == (q, p) and A.nnz == AT.nnz
+        arrs = [np.ascontiguousarray(A.indptr, dtype=np.int32), np.ascontiguousarray(A.indices, dtype=np.int32), f64(A.data),
+                np.ascontiguousarray(AT.indptr, dtype=np.int32), np.ascontiguousarray(AT.indices, dtype=np.int32), f64(AT.data)]
+        self.check(self.lib.lz_gk_set_csr(self._h, int(p), int(q), int(A.nnz), i32ptr(arrs[0]), i32ptr(arrs[1]), dptr(arrs[2]),
+                                          i32ptr(arrs[3]), i32ptr(arrs[4]), dptr(arrs[5])))
+        self.gk_shape = (int(p), int(q))
+
+    def gk_begin(self, m, v0):
+        v0 = f64(v0)
+        assert v0.shape == (self.gk_shape[1],)
+        self.check(self.lib.lz_gk_begin(self._h, int(m), dptr(v0)))
+
+    def gk_extend(self, k, m):
+        """steps k .. m-1 -> (colproj (m, m): row j = the coefficients of A V[j] on U[0..j) for j >= k, alpha (m,), beta (m,))"""
+        colproj, alpha, beta = np.zeros((m, m)), np.zeros(m), np.zeros(m)
+        self.check(self.lib.lz_gk_extend(self._h, int(k), int(m), dptr(colproj), dptr(alpha), dptr(beta)))
+        return colproj, alpha, beta
+
+    def gk_restart(self, m, kk, P, Q):
+        P, Q = f64(P), f64(Q)
+        assert P.shape == (m, kk) and Q.shape == (m, kk)
+        self.check(self.lib.lz_gk_restart(self._h, int(m), int(kk), dptr(P), dptr(Q)))
+
+    def gk_probe(self, side, k, x):
+        x = f64(x)
+        assert x.shape == (self.gk_shape[int(side)],)
+        self.check(self.lib.lz_gk_probe(self._h, int(side), int(k), dptr(x)))
+
+    def gk_get_vectors(self, side, k):
+        out = np.empty((self.gk_shape[int(side)], int(k)))
+        self.check(self.lib.lz_gk_get_vectors(self._h, int(side), int(k), dptr(out)))
+        return out
+
+    def gk_set_rows(self, side, j0, rows):
+        """raw rows j0 .. j0 + len(rows) - 1 of a basis including their padding: rows is (count, >= padded_rows(p or q))"""
+        rows = f64(rows)
+        self.check(self.lib.lz_gk_set_rows(self._h, int(side), int(j0), rows.shape[0], dptr(rows), rows.shape[1]))
+
+    def gk_get_rows(self, side, j0, count):
+        out = np.empty((int(count), self.padded_rows(self.gk_shape[int(side)])))
+        self.check(self.lib.lz_gk_get_rows(self._h, int(side), int(j0), int(count), dptr(out), out.shape[1]))
+        return out
+
+    def gk_residuals(self, k, sigma):
+        """(2, k): |A v_i - sigma_i u_i| and |A^T u_i - sigma_i v_i|"""
+        sg = f64(sigma)[: int(k)]
+        out = np.empty((2, int(k)))
+        self.check(self.lib.lz_gk_residuals(self._h, int(k), dptr(sg), dptr(out)))
+        return out
+
+    def gk_spmv(self, x, transpose=False):
+        """one product through the rectangular kernel; the result includes the padding (``padded_rows`` doubles)"""
+        x = f64(x)
+        p, q = self.gk_shape
+        assert x.shape == ((p,) if transpose else (q,))
+        y = np.empty(self.padded_rows(q if transpose else p))
+        self.check(self.lib.lz_gk_spmv(self._h, 1 if transpose else 0, dptr(x), dptr(y)))
+        return y
+
+    def gk_spmv_time(self, transpose=False, reps=20):
+        """device milliseconds of one product (mean of ``reps`` launches)"""
+        ms = C.c_double()
+        self.check(self.lib.lz_gk_spmv_time(self._h, 1 if transpose else 0, int(reps), C.byref(ms)))
+        return ms.value
 
     def spmv_host(self, x, ncols=None):
         x = f64(x)

@@ -517,6 +517,7 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_tsm);
   big_free(h->d_tgate);
   big_free(h->d_tpart);
+  gk_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

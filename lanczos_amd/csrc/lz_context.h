@@ -54,6 +54,24 @@ struct TrlPoly {
   void clear() { kind = kNone, degree = 0; }
 };
 
+// Golub-Kahan-Lanczos bidiagonalisation (lz_gk_api.hip, lanczos_amd.svds): a rectangular operator and two bases of their own, separate
+// from the handle's square operator, its fixed-n run and its thick-restart basis.  A is p x q (p >= q), AT its transpose.
+struct GkState {
+  bool set = false;
+  int64_t p = 0, q = 0, p_pad = 0, q_pad = 0, ldp = 0, ldq = 0;  // padded lengths and row strides of the long (U) and the short (V) side
+  CsrDev A, AT;
+  int m = 0;                  // 0: no basis (lz_gk_begin)
+  int u_ready = -1;           // k: U[k] was made by lz_gk_probe, so lz_gk_extend(k, ..) starts step k at its second half
+  double* d_U = nullptr;      // m + 1 rows of ldp doubles (row m stays zero: launch_trl_restart copies it to row kk)
+  double* d_V = nullptr;      // m + 1 rows of ldq doubles
+  double* d_wu = nullptr;     // w = A V[j] (ldp)
+  double* d_wv = nullptr;     // z = A^T U[j] (ldq)
+  double* d_sm = nullptr;     // small arrays: see gk_small_layout in lz_gk_api.hip
+  int* d_gate = nullptr;      // [0] gate of the second CGS pass
+  double* d_part = nullptr;   // partials of the passes / residual norms
+  size_t part_cap = 0;
+};
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -186,6 +204,7 @@ struct lz_context {
   double* d_tpart = nullptr;   // partials of the passes / SpMV / residual norms
   size_t tpart_cap = 0;
   TrlPoly poly;  // none, the Chebyshev filter or the Chebyshev series
+  GkState gk;    // Golub-Kahan-Lanczos (lz_gk_*): freed by gk_free
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -288,6 +307,9 @@ int fill_csr_meta(lz_handle h, CsrDev& A, const int32_t* rowptr_host, int64_t ro
                   int max_nnz);
 int upload_csr(lz_handle h, CsrDev& A, const char* who, int64_t rows, int64_t ncols, int64_t nnz, const int32_t* rowptr,
                const int32_t* colidx, const double* vals, int* fixed_k_out, int* max_nnz_out);
+
+// Golub-Kahan-Lanczos state (lz_gk_api.hip): releases everything h->gk owns (lz_destroy)
+void gk_free(lz_handle h);
 
 }  // namespace api
 }  // namespace lz

@@ -79,7 +79,20 @@ struct CsrDev {
   int cls_group = 0;          // knob 23: 0 k_spmv_cls2 (two adjacent rows per lane); 1 / 3: k_spmv_cls with one / two units per workgroup (A/B)
   const int32_t* host_colidx = nullptr;  // the caller's arrays, valid ONLY inside lz_set_csr / lz_set_csr_transpose (pb_build reads them)
   const double* host_vals = nullptr;
+  // rectangular product (lz_gk.hip; only the matrices of lz_gk_set_csr have these, and they have none of the layouts above): work items
+  // of four int32 each - a block of whole rows or one segment of a long row -, the long rows and their segment partials
+  int32_t* rect_items = nullptr;
+  int n_rect = 0;
+  int32_t* rect_long = nullptr;
+  int n_rect_long = 0;
+  double* rect_seg = nullptr;
 };
+
+// ---- rectangular product (lz_gk.hip): y = A x for rows != ncols in either direction, no x_own . y epilogue, y[rows .. rows_pad) = 0.
+// rect_plan (host): the work items for tiles of nnz_cap products; split == false keeps a long row in one workgroup (A/B arm).
+void rect_plan(const int32_t* rowptr, int64_t rows, int nnz_cap, bool split, std::vector<int32_t>& items, std::vector<int32_t>& lrows,
+               int* nslots);
+hipError_t launch_spmv_rect(const CsrDev& A, const double* x, double* y, int64_t rows_pad, hipStream_t s);
 
 // ---- column-blocked two-phase SpMV (lz_spmv_pb.hip): gathers out of LDS only; y bit-identical to the CSR-stream kernel
 hipError_t pb_build(const CsrDev& A, const int32_t* rowptr_host, PbDev** out, hipStream_t s, int cap_knob = 0, int groups = 0);  // *out == nullptr: not applicable; groups > 1: the A/B arm of knob 22
