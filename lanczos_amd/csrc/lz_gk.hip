@@ -149,6 +149,12 @@ void rect_plan(const int32_t* rowptr, int64_t rows, int nnz_cap, bool split, std
 
 hipError_t launch_spmv_rect(const CsrDev& A, const double* x, double* y, int64_t rows_pad, hipStream_t s) {
   const size_t lds = (size_t)(A.blk_nnz_cap + 2) * sizeof(double);
+  // the kernel's static block_sum scratch counts against the same 64 KiB: at the upper clamp of knob 4 (8190 + 2 products = 65 536 B)
+  // the two together are past it, and the per-kernel limit has to be raised as launch_trl_restart_t does for its kernel
+  if (lds + (kTPB / 64) * sizeof(double) > 65536) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmv_rect), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+  }
   hipLaunchKernelGGL(k_spmv_rect, dim3(A.n_rect), dim3(kTPB), lds, s, reinterpret_cast<const RectItem*>(A.rect_items), A.rowptr, A.colidx,
                      A.vals, x, y, A.rows, rows_pad, A.rect_seg);
   if (A.n_rect_long > 0)
