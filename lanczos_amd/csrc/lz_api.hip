@@ -511,12 +511,9 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_omi);
   big_free(h->res_V);
   big_free(h->res_Y);
-  big_free(h->d_trl);
-  big_free(h->d_tw);
+  orth_free(h->trl);
   big_free(h->d_tW);
-  big_free(h->d_tsm);
-  big_free(h->d_tgate);
-  big_free(h->d_tpart);
+  orth_free(h->trl_wk);
   gk_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);

@@ -1,5 +1,5 @@
-// Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip): the handle,
-// the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip,
+// lz_orth.hip, lz_trl_api.hip, lz_gk_api.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -48,28 +48,48 @@ struct TrlPoly {
   int degree = 0, coef_cap = 0;  // coef_cap: the doubles behind d_coef
   double c = 0.0, inv_e = 0.0;   // the centre of the damped interval (filter) or of the map to [-1, 1] (series); 1 / e of that map
   double* d_coef = nullptr;      // filter: a[0 .. degree), b[0 .. degree) of z = a_i (A y - c y) - b_i x; series: mu[0 .. degree]
-  double* d_rot = nullptr;       // two work vectors of ld doubles each, rotated with d_tw (allocated when the first polynomial is set)
+  double* d_rot = nullptr;       // two work vectors of ld doubles each, rotated with trl.w (allocated when the first polynomial is set)
   double* d_acc = nullptr;       // the series' running sum, ld doubles (allocated when the first series is set)
   int64_t ld = 0;                // the row length d_rot and d_acc were allocated for
   void clear() { kind = kNone, degree = 0; }
 };
 
+// The Gram-Schmidt basis layer under the restart solvers (lz_orth.hip).  OrthBasis: one orthonormal row basis and the work vector that is
+// orthogonalised against it and stored as its next row.  h->trl follows the square matrix set last: trl_state (lz_trl_api.hip), which
+// every lz_trl_* entry point behind lz_trl_begin calls first, sets its len and pad from h->rows / h->rows_pad on every call; code that
+// uses h->trl without going through trl_state or trl_alloc reads the lengths of the last call that did.
+struct OrthBasis {
+  double* B = nullptr;  // nrows rows, ld doubles apart
+  double* w = nullptr;  // ld doubles; [len, ld) is zero whenever a walk reads it: the walks stream pad doubles, the products write len
+  int64_t len = 0, pad = 0, ld = 0;  // the vectors' length, padded to kPadDoubles, and the (skewed) row stride
+  int nrows = 0;        // sizes the walks' plan (orth_plan) and the head of the small arrays (orth_small_head)
+};
+// What the bases of one solver share: the small arrays (head: OrthSmallHead, the rest the solver's own), the gate and the partials.
+struct OrthWork {
+  double* sm = nullptr;
+  int* gate = nullptr;     // [0] gate of the second CGS pass
+  double* part = nullptr;  // partials of the passes, the products and the residual norms
+  size_t part_cap = 0;
+};
+// c of pass 1 and of pass 2 (row nrows is the self slot), nrm2 + a scratch slot; the solver's own arrays start at end
+struct OrthSmallHead {
+  int64_t c1, c2, nrm2, end;
+};
+inline OrthSmallHead orth_small_head(int nrows) {
+  const int64_t cl = lz::qtw_ldp(nrows + 1) + 16;
+  return {0, cl, 2 * cl, 2 * cl + 8};
+}
+
 // Golub-Kahan-Lanczos bidiagonalisation (lz_gk_api.hip, lanczos_amd.svds): a rectangular operator and two bases of their own, separate
 // from the handle's square operator, its fixed-n run and its thick-restart basis.  A is p x q (p >= q), AT its transpose.
 struct GkState {
   bool set = false;
-  int64_t p = 0, q = 0, p_pad = 0, q_pad = 0, ldp = 0, ldq = 0;  // padded lengths and row strides of the long (U) and the short (V) side
   CsrDev A, AT;
-  int m = 0;                  // 0: no basis (lz_gk_begin)
-  int u_ready = -1;           // k: U[k] was made by lz_gk_probe, so lz_gk_extend(k, ..) starts step k at its second half
-  double* d_U = nullptr;      // m + 1 rows of ldp doubles (row m stays zero: launch_trl_restart copies it to row kk)
-  double* d_V = nullptr;      // m + 1 rows of ldq doubles
-  double* d_wu = nullptr;     // w = A V[j] (ldp)
-  double* d_wv = nullptr;     // z = A^T U[j] (ldq)
-  double* d_sm = nullptr;     // small arrays: see gk_small_layout in lz_gk_api.hip
-  int* d_gate = nullptr;      // [0] gate of the second CGS pass
-  double* d_part = nullptr;   // partials of the passes / residual norms
-  size_t part_cap = 0;
+  int m = 0;         // 0: no basis (lz_gk_begin)
+  int u_ready = -1;  // k: U[k] was made by lz_gk_probe, so lz_gk_extend(k, ..) starts step k at its second half
+  OrthBasis U;       // the long side (len p): m + 1 rows (row m stays zero: launch_trl_restart copies it to row kk); w = A V[j]
+  OrthBasis V;       // the short side (len q): m + 1 rows; w = z = A^T U[j]
+  OrthWork wk;       // small arrays: see gk_small_layout in lz_gk_api.hip
 };
 
 struct lz_context {
@@ -192,17 +212,12 @@ struct lz_context {
   size_t res_V_count = 0;
   double* res_Y = nullptr;
   size_t res_Y_count = 0;
-  // thick-restart Lanczos (lz_trl_api.hip): a basis of its own (trl_m + trl_b rows of trl_ld doubles), never the fixed-n run's d_V / d_Y
-  double* d_trl = nullptr;
+  // thick-restart Lanczos (lz_trl_api.hip): a basis of its own (trl_m + trl_b rows), never the fixed-n run's d_V / d_Y
+  OrthBasis trl;               // w = A V[j], then the residual
   int trl_m = 0;
   int trl_b = 1;               // residual rows behind the m basis rows: 1 (lz_trl_begin) or the band width (lz_trl_begin_band)
-  int64_t trl_ld = 0;
-  double* d_tw = nullptr;      // w = A V[j], then the residual (rows_pad)
-  double* d_tW = nullptr;      // band Lanczos: the trl_b work vectors of a batch (trl_ld apart)
-  double* d_tsm = nullptr;     // small arrays: see trl_small_layout in lz_trl_api.hip
-  int* d_tgate = nullptr;      // [0] gate of the second CGS pass
-  double* d_tpart = nullptr;   // partials of the passes / SpMV / residual norms
-  size_t tpart_cap = 0;
+  double* d_tW = nullptr;      // band Lanczos: the trl_b work vectors of a batch (trl.ld apart)
+  OrthWork trl_wk;             // small arrays: see trl_small_layout in lz_trl_api.hip
   TrlPoly poly;  // none, the Chebyshev filter or the Chebyshev series
   GkState gk;    // Golub-Kahan-Lanczos (lz_gk_*): freed by gk_free
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
@@ -310,6 +325,32 @@ int upload_csr(lz_handle h, CsrDev& A, const char* who, int64_t rows, int64_t nc
 
 // Golub-Kahan-Lanczos state (lz_gk_api.hip): releases everything h->gk owns (lz_destroy)
 void gk_free(lz_handle h);
+
+// Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_* and lz_gk_* both do with an OrthBasis and its OrthWork
+QtwPlan orth_plan(lz_handle h, const OrthBasis& b);
+// c[0 .. n) = B[0 .. n) . w, c[n] = w . w (the self slot); gate: the launches return at once where gate[0] == 0
+int orth_dots(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int n, double* c, const int* gate = nullptr);
+// row k = w made orthogonal to rows [0, k) by two CGS passes, normalised; synchronises.  what: the name check_launch reports
+int orth_store(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int k, const char* what);
+// one extension step: w against rows [0, nb) - CGS and a second pass -, its norm to norm_slot, w / norm to row nb.  proj: where the nb
+// measured coefficients go (both passes' sums).  nb == 0: the norm only.  No check_launch, no synchronisation: the caller's.
+enum class OrthPass2 {
+  kGated,    // the DGKS gate: pass 2's launches return at once unless pass 1 cancelled more than half of |w|^2
+  kForced,   // the same gated launches, the gate always set (LZ_FLAG_TRL_PASS2_ALWAYS)
+  kUngated,  // pass 2's launches take no gate at all (the tail of a band batch, on a view of the rows the batch has made)
+};
+int orth_cgs_step(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int nb, double* proj, double* norm_slot,
+                  OrthPass2 pass2);
+int orth_upload_x(lz_handle h, const OrthBasis& b, const double* x);                     // w = x, zero beyond len
+int orth_get_vectors(lz_handle h, const OrthBasis& b, int k, double* out);              // out (len x k, row-major) = rows [0, k) transposed
+// raw rows j0 .. j0 + count - 1 with their padding.  who, top: the caller and its name for the last row, for the argument error's text
+int orth_set_rows(lz_handle h, const OrthBasis& b, const char* who, const char* top, int j0, int count, const double* rows, int64_t ld);
+int orth_get_rows(lz_handle h, const OrthBasis& b, const char* who, const char* top, int j0, int count, double* rows, int64_t ld);
+// partials that the sequences above and m residual norms need; the solver adds its own terms and reserves the largest
+size_t orth_part_need(const OrthBasis& b, const QtwPlan& plan, int m);
+int orth_part_reserve(lz_handle h, OrthWork& wk, size_t need);
+void orth_free(OrthBasis& b);
+void orth_free(OrthWork& wk);
 
 }  // namespace api
 }  // namespace lz

@@ -1,5 +1,8 @@
 // C ABI of the thick-restart Lanczos solver (include/lanczos_hip.h, "thick-restart Lanczos"): the device half of lanczos_amd.eigsh.
-// The basis is a buffer of its own (d_trl: trl_m + trl_b rows of trl_ld doubles); the fixed-n run's V / Y on the same handle are untouched.
+// The basis is a buffer of its own (h->trl: trl_m + trl_b rows); the fixed-n run's V / Y on the same handle are untouched.
+// What is here is the solver's own: the operator (A or a polynomial of A), the band batch, the restart, the residuals and the Rayleigh
+// quotient.  Orthogonalising a vector against the basis and storing it, the gated two-pass step of an extension and the row transfers
+// are the basis layer's (lz_orth.hip), shared with the Golub-Kahan-Lanczos solver.
 #include "lz_context.h"
 
 using namespace lz;
@@ -7,21 +10,18 @@ using namespace lz::api;
 
 namespace {
 
-// d_tsm: c of pass 1 and of pass 2 (cl doubles each), nrm2 + a scratch beta slot, the projected rows (m x m; band: m x (m + b)), beta (m),
-// the restart's S (m x m), theta and the residual norms (m each); band only: the block coefficients of both passes ((m + b) x b each)
-// and the b squared norms of a batch
-struct TrlSmall {
-  int64_t c1, c2, nrm2, proj, beta, S, theta, res, C1, C2, nrmb, total;
+// trl_wk.sm: the basis layer's head (c of both passes, nrm2), the projected rows (m x m; band: m x (m + b)), beta (m), the restart's
+// S (m x m), theta and the residual norms (m each); band only: the block coefficients of both passes ((m + b) x b each) and the b
+// squared norms of a batch
+struct TrlSmall : OrthSmallHead {
+  int64_t proj, beta, S, theta, res, C1, C2, nrmb, total;
   int ldf;  // row length of proj
 };
 TrlSmall trl_small_layout(int m, int b = 1) {
   TrlSmall L;
-  const int64_t cl = qtw_ldp(m + b + 1) + 16;
+  static_cast<OrthSmallHead&>(L) = orth_small_head(m + b);
   L.ldf = b > 1 ? m + b : m;
-  L.c1 = 0;
-  L.c2 = cl;
-  L.nrm2 = 2 * cl;
-  L.proj = L.nrm2 + 8;
+  L.proj = L.end;
   L.beta = L.proj + (int64_t)m * L.ldf;
   L.S = L.beta + m + 8;
   L.theta = L.S + (int64_t)m * m;
@@ -35,54 +35,29 @@ TrlSmall trl_small_layout(int m, int b = 1) {
 }
 TrlSmall trl_small_layout(lz_handle h) { return trl_small_layout(h->trl_m, h->trl_b); }
 
-QtwPlan trl_plan(lz_handle h) {
-  return plan_qtw(h->rows_pad, h->flags & ~(LZ_FLAG_QTW_MFMA | LZ_FLAG_ONE_REDUCE), h->tune, h->trl_m + h->trl_b + 1);
-}
-
 int trl_state(lz_handle h, const char* who) {
   if (!h) return LZ_ERR_ARG;
-  if (!h->d_trl) return fail(h, LZ_ERR_STATE, std::string(who) + ": no thick-restart basis (lz_trl_begin first)");
-  if (h->kind == 0 || skew_stride(h, h->rows_pad) != h->trl_ld) return fail(h, LZ_ERR_STATE, std::string(who) + ": the matrix changed since lz_trl_begin");
+  if (!h->trl.B) return fail(h, LZ_ERR_STATE, std::string(who) + ": no thick-restart basis (lz_trl_begin first)");
+  if (h->kind == 0 || skew_stride(h, h->rows_pad) != h->trl.ld) return fail(h, LZ_ERR_STATE, std::string(who) + ": the matrix changed since lz_trl_begin");
+  // the view follows the matrix set last (one of another row count passes the test above where it pads to the same length): every
+  // entry point behind lz_trl_begin comes through here before it touches h->trl (see OrthBasis, lz_context.h)
+  h->trl.len = h->rows;
+  h->trl.pad = h->rows_pad;
   LZ_HIP(h, hipSetDevice(h->dev));
   return LZ_OK;
 }
 
-// V[k] = x (in d_tw) made orthogonal to V[0..k) by two CGS passes, then normalised
-int trl_orth_store(lz_handle h, int k) {
-  const TrlSmall L = trl_small_layout(h);
-  double* V = h->d_trl;
-  const QtwPlan plan = trl_plan(h);
-  int np = 0;
-  for (int pass = 0; pass < (k > 0 ? 2 : 0); ++pass) {
-    LZ_HIP(h, launch_qtw(V, h->trl_ld, h->rows_pad, k + 1, k, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
-    launch_final_rows(h->d_tpart, k + 1, plan.P, h->d_tsm + L.c1, h->stream, plan.family == 2);
-    np = launch_trl_cgs(V, h->trl_ld, h->rows_pad, k, h->d_tsm + L.c1, h->d_tw, h->d_tpart, nullptr, h->stream);
-  }
-  if (k == 0) np = launch_trl_cgs(V, h->trl_ld, h->rows_pad, 0, h->d_tsm + L.c1, h->d_tw, h->d_tpart, nullptr, h->stream);  // |x|^2 only
-  launch_trl_post(2, h->d_tpart, np, nullptr, 0, h->d_tsm + L.nrm2, nullptr, h->d_tgate, 0, h->stream);
-  launch_scale_store(V + (int64_t)k * h->trl_ld, h->d_tw, h->d_tsm + L.nrm2, h->d_tsm + L.nrm2 + 1, h->rows_pad, h->stream);
-  LZ_TRY(check_launch(h, "trl orthogonalise"));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  return LZ_OK;
-}
-
-int trl_upload_x(lz_handle h, const double* x) {
-  LZ_HIP(h, hipMemsetAsync(h->d_tw, 0, (size_t)h->trl_ld * sizeof(double), h->stream));
-  LZ_TRY(upload(h, h->d_tw, x, (size_t)h->rows * sizeof(double)));
-  return LZ_OK;
-}
-
-// out = A x or, with a polynomial set (h->poly), p(A) x (x: a device vector of trl_ld doubles with a zero-or-ignored padding, never
-// written; out: d_tw, or a work vector of a band batch).  The recurrence runs through three rotating work vectors (out and the two of
+// out = A x or, with a polynomial set (h->poly), p(A) x (x: a device vector of trl.ld doubles with a zero-or-ignored padding, never
+// written; out: trl.w, or a work vector of a band batch).  The recurrence runs through three rotating work vectors (out and the two of
 // poly.d_rot) so that step d lands in out;
 // every product is the plain SpMV / GEMV launch, every recurrence step one streaming kernel in place on that product.
 // Filter: the scaled Chebyshev recurrence, one k_cheb_step per step.  Series: sum_i mu_i T_i, the same rotation for the terms and the
 // running sum in poly.d_acc beside them (k_cheb_series_step); the last term is only added, never stored, and the sum goes to its slot, out.
 void trl_matvec(lz_handle h, const double* x, double* y) {
   if (h->kind == 1)
-    launch_spmv_csr(h->csr, x, y, x, h->d_tpart, h->flags, h->stream);
+    launch_spmv_csr(h->csr, x, y, x, h->trl_wk.part, h->flags, h->stream);
   else
-    launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, y, h->d_tpart, h->stream);
+    launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, y, h->trl_wk.part, h->stream);
 }
 void trl_apply_op(lz_handle h, const double* x, double* out) {
   const TrlPoly& P = h->poly;
@@ -114,7 +89,7 @@ void trl_apply_op(lz_handle h, const double* x, double* out) {
         ch.acc_in = P.d_acc;
         ch.acc = last ? out : P.d_acc;
       }
-      launch_spmv_ell(h->csr, cur, z, cur, h->d_tpart, h->stream, nullptr, &ch);
+      launch_spmv_ell(h->csr, cur, z, cur, h->trl_wk.part, h->stream, nullptr, &ch);
     } else {
       trl_matvec(h, cur, z);
       if (series)
@@ -134,10 +109,10 @@ int trl_set_poly(lz_handle h, TrlPoly::Kind kind, int degree, const double* coef
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   P.clear();  // one polynomial at a time: setting (or clearing) either kind drops what was set
   if (degree == 0) return LZ_OK;
-  if (!P.d_rot || P.ld != h->trl_ld) {
+  if (!P.d_rot || P.ld != h->trl.ld) {
     LZ_TRY(dev_free(h, P.d_acc));  // (of the old row length)
-    LZ_TRY(dev_alloc(h, P.d_rot, 2 * (size_t)h->trl_ld));
-    P.ld = h->trl_ld;
+    LZ_TRY(dev_alloc(h, P.d_rot, 2 * (size_t)h->trl.ld));
+    P.ld = h->trl.ld;
   }
   if (kind == TrlPoly::kSeries && !P.d_acc) LZ_TRY(dev_alloc(h, P.d_acc, (size_t)P.ld));
   if ((size_t)P.coef_cap < n0 + n1) {
@@ -171,41 +146,44 @@ int trl_alloc(lz_handle h, int m, int b, const char* who) {
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   const int64_t ld = skew_stride(h, h->rows_pad);
   const size_t nrows = (size_t)(m + b);
-  if (!h->d_trl || h->trl_m != m || h->trl_b != b || h->trl_ld != ld) {
+  if (!h->trl.B || h->trl_m != m || h->trl_b != b || h->trl.ld != ld) {
     h->poly.clear();  // its work vectors belong to the old row length
-    LZ_TRY(dev_alloc(h, h->d_trl, nrows * (size_t)ld));
-    LZ_TRY(dev_alloc(h, h->d_tw, (size_t)ld));
+    LZ_TRY(dev_alloc(h, h->trl.B, nrows * (size_t)ld));
+    LZ_TRY(dev_alloc(h, h->trl.w, (size_t)ld));
     if (b > 1)
       LZ_TRY(dev_alloc(h, h->d_tW, (size_t)b * (size_t)ld));
     else
       LZ_TRY(dev_free(h, h->d_tW));
-    LZ_TRY(dev_alloc(h, h->d_tsm, (size_t)trl_small_layout(m, b).total));
-    LZ_TRY(dev_alloc(h, h->d_tgate, 4));
+    LZ_TRY(dev_alloc(h, h->trl_wk.sm, (size_t)trl_small_layout(m, b).total));
+    LZ_TRY(dev_alloc(h, h->trl_wk.gate, 4));
     h->trl_m = m;
     h->trl_b = b;
-    h->trl_ld = ld;
+    h->trl.ld = ld;
+    h->trl.nrows = m + b;
   }
-  const QtwPlan plan = trl_plan(h);
-  size_t need = (size_t)(m + b + 1 + 32) * (size_t)plan.P;
-  need = std::max<size_t>(need, (size_t)trl_cgs_blocks(h->rows_pad));
+  h->trl.len = h->rows;
+  h->trl.pad = h->rows_pad;
+  size_t need = orth_part_need(h->trl, orth_plan(h, h->trl), m);
   need = std::max<size_t>(need, (size_t)h->rows / 4 + 64);  // dense GEMV / scalar SpMV partials
   need = std::max<size_t>(need, (size_t)h->csr.n_rowblk + 64);
   if (h->csr.pb) need = std::max<size_t>(need, (size_t)pb_num_partials(h->csr.pb) + 64);
-  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64);  // residual norms
+  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64);  // residual norms + a dense product's
   if (b > 1) {  // the block Gram-Schmidt's coefficient runs and squared-norm partials
     need = std::max<size_t>(need, (size_t)trl_band_dots_blocks(h->rows_pad, b) * (size_t)trl_band_run(m + b, b));
     need = std::max<size_t>(need, (size_t)b * (size_t)trl_band_update_blocks(h->rows_pad));
   }
-  need += 8192;
-  if (need > h->tpart_cap) {
-    LZ_TRY(dev_alloc(h, h->d_tpart, need));
-    h->tpart_cap = need;
-  }
-  LZ_HIP(h, hipMemsetAsync(h->d_trl, 0, nrows * (size_t)ld * sizeof(double), h->stream));
+  LZ_TRY(orth_part_reserve(h, h->trl_wk, need));
+  LZ_HIP(h, hipMemsetAsync(h->trl.B, 0, nrows * (size_t)ld * sizeof(double), h->stream));
   if (b > 1) LZ_HIP(h, hipMemsetAsync(h->d_tW, 0, (size_t)b * (size_t)ld * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_tsm, 0, (size_t)trl_small_layout(m, b).total * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_tgate, 0, 4 * sizeof(int), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->trl_wk.sm, 0, (size_t)trl_small_layout(m, b).total * sizeof(double), h->stream));
+  LZ_HIP(h, hipMemsetAsync(h->trl_wk.gate, 0, 4 * sizeof(int), h->stream));
   return LZ_OK;
+}
+
+// V[k] = x made orthogonal to V[0..k), normalised
+int trl_store_x(lz_handle h, int k, const double* x) {
+  LZ_TRY(orth_upload_x(h, h->trl, x));
+  return orth_store(h, h->trl, h->trl_wk, orth_plan(h, h->trl), k, "trl orthogonalise");
 }
 
 }  // namespace
@@ -215,18 +193,14 @@ extern "C" {
 int lz_trl_begin(lz_handle h, int m, const double* v0) {
   if (!h || !v0) return LZ_ERR_ARG;
   LZ_TRY(trl_alloc(h, m, 1, "lz_trl_begin"));
-  LZ_TRY(trl_upload_x(h, v0));
-  return trl_orth_store(h, 0);
+  return trl_store_x(h, 0, v0);
 }
 
 int lz_trl_begin_band(lz_handle h, int m, int b, const double* X) {
   if (!h || !X) return LZ_ERR_ARG;
   if (b < 2 || b > 8) return fail(h, LZ_ERR_ARG, "lz_trl_begin_band: need 2 <= b <= 8");
   LZ_TRY(trl_alloc(h, m, b, "lz_trl_begin_band"));
-  for (int i = 0; i < b; ++i) {
-    LZ_TRY(trl_upload_x(h, X + (int64_t)i * h->rows));
-    LZ_TRY(trl_orth_store(h, i));
-  }
+  for (int i = 0; i < b; ++i) LZ_TRY(trl_store_x(h, i, X + (int64_t)i * h->rows));
   return LZ_OK;
 }
 
@@ -235,27 +209,14 @@ int lz_trl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out)
   if (h->trl_b != 1) return fail(h, LZ_ERR_STATE, "lz_trl_extend: the basis was begun as a band (lz_trl_extend_band)");
   if (m != h->trl_m || k < 0 || k >= m) return fail(h, LZ_ERR_ARG, "lz_trl_extend: need m == the m of lz_trl_begin and 0 <= k < m");
   const TrlSmall L = trl_small_layout(h);
-  double* V = h->d_trl;
-  double* sm = h->d_tsm;
-  const int64_t ld = h->trl_ld;
-  const QtwPlan plan = trl_plan(h);
-  const int force = (h->flags & LZ_FLAG_TRL_PASS2_ALWAYS) != 0;
-  QtwFuse gated;
-  gated.gate = h->d_tgate;
+  const OrthBasis& V = h->trl;
+  double* sm = h->trl_wk.sm;
+  const QtwPlan plan = orth_plan(h, V);
+  const OrthPass2 pass2 = (h->flags & LZ_FLAG_TRL_PASS2_ALWAYS) ? OrthPass2::kForced : OrthPass2::kGated;
   for (int j = k; j < m; ++j) {
-    trl_apply_op(h, V + (int64_t)j * ld, h->d_tw);  // w = A V[j], or p(A) V[j] with a filter set
-    // pass 1: c = V[0..j] . w (row j + 1 is the self slot: c[j + 1] = w.w), w -= sum c_i V_i
-    LZ_HIP(h, launch_qtw(V, ld, h->rows_pad, j + 2, j + 1, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
-    launch_final_rows(h->d_tpart, j + 2, plan.P, sm + L.c1, h->stream, plan.family == 2);
-    int np = launch_trl_cgs(V, ld, h->rows_pad, j + 1, sm + L.c1, h->d_tw, h->d_tpart, nullptr, h->stream);
-    launch_trl_post(0, h->d_tpart, np, sm + L.c1, j, sm + L.nrm2, sm + L.proj + (int64_t)j * m, h->d_tgate, force, h->stream);
-    // pass 2, only where pass 1 cancelled more than half of |w| (or LZ_FLAG_TRL_PASS2_ALWAYS forces it)
-    LZ_HIP(h, launch_qtw(V, ld, h->rows_pad, j + 2, j + 1, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream, &gated));
-    launch_final_rows(h->d_tpart, j + 2, plan.P, sm + L.c2, h->stream, plan.family == 2, h->d_tgate);
-    np = launch_trl_cgs(V, ld, h->rows_pad, j + 1, sm + L.c2, h->d_tw, h->d_tpart, h->d_tgate, h->stream);
-    launch_trl_post(1, h->d_tpart, np, sm + L.c2, j, sm + L.nrm2, sm + L.proj + (int64_t)j * m, h->d_tgate, force, h->stream);
-    // beta = |w|, V[j + 1] = w / beta
-    launch_scale_store(V + (int64_t)(j + 1) * ld, h->d_tw, sm + L.nrm2, sm + L.beta + j, h->rows_pad, h->stream);
+    trl_apply_op(h, V.B + (int64_t)j * V.ld, V.w);  // w = A V[j], or p(A) V[j] with a filter set
+    // w against V[0..j]: row j of the projection; beta_j = |w|, V[j + 1] = w / beta_j
+    LZ_TRY(orth_cgs_step(h, V, h->trl_wk, plan, j + 1, sm + L.proj + (int64_t)j * m, sm + L.beta + j, pass2));
     LZ_TRY(check_launch(h, "trl extend"));
   }
   if (proj_out) LZ_HIP(h, hipMemcpyAsync(proj_out, sm + L.proj, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -270,11 +231,11 @@ int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta
   if (m != h->trl_m || k < 0 || k >= m) return fail(h, LZ_ERR_ARG, "lz_trl_extend_band: need m == the m of lz_trl_begin_band and 0 <= k < m");
   const int b = h->trl_b;
   const TrlSmall L = trl_small_layout(h);
-  double* V = h->d_trl;
+  double* V = h->trl.B;
   double* W = h->d_tW;
-  double* sm = h->d_tsm;
-  const int64_t ld = h->trl_ld;
-  const QtwPlan plan = trl_plan(h);
+  double* sm = h->trl_wk.sm;
+  const int64_t ld = h->trl.ld;
+  const QtwPlan plan = orth_plan(h, h->trl);
   // the sweeps stream rows_pad, the products write rows: a breakdown in an earlier call (0 / 0 behind a vanished residual) may have left
   // NaN in a work vector's padding, which no product would clear
   if (h->rows_pad > h->rows)
@@ -291,29 +252,22 @@ int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta
     int nu = 0;
     for (int pass = 0; pass < 2; ++pass) {
       double* C = sm + (pass == 0 ? L.C1 : L.C2);
-      LZ_HIP(h, launch_trl_band_dots(V, ld, h->rows_pad, r0, W, ld, b, h->d_tpart, h->stream));
-      launch_final_rows_t(h->d_tpart, G, run, r0 * b, C, h->stream);
-      nu = launch_trl_band_update(V, ld, h->rows_pad, r0, C, W, ld, b, h->d_tpart, h->stream);
+      LZ_HIP(h, launch_trl_band_dots(V, ld, h->rows_pad, r0, W, ld, b, h->trl_wk.part, h->stream));
+      launch_final_rows_t(h->trl_wk.part, G, run, r0 * b, C, h->stream);
+      nu = launch_trl_band_update(V, ld, h->rows_pad, r0, C, W, ld, b, h->trl_wk.part, h->stream);
     }
-    launch_final_rows(h->d_tpart, b, nu, sm + L.nrmb, h->stream);  // |w_i|^2 after the second pass
+    launch_final_rows(h->trl_wk.part, b, nu, sm + L.nrmb, h->stream);  // |w_i|^2 after the second pass
     launch_trl_band_proj(sm + L.C1, sm + L.C2, r0, b, nb, sm + L.proj + (int64_t)j * L.ldf, L.ldf, h->stream);
-    // in-batch tail: w_i against the rows this batch has made so far (the single-vector kernels, based at row r0), then V[r0 + i] = w_i / |w_i|
-    double* Vn = V + (int64_t)r0 * ld;
+    // in-batch tail: w_i against the rows this batch has made so far (the single-vector step on a view based at row r0, both passes
+    // always), then V[r0 + i] = w_i / |w_i|
+    OrthBasis tail = h->trl;  // (nrows as the basis': the plan and the small arrays are the whole basis')
+    tail.B = V + (int64_t)r0 * ld;
     for (int i = 0; i < nb; ++i) {
-      double* w = W + (int64_t)i * ld;
-      const double* nrm2 = sm + L.nrmb;  // i == 0: nothing new to orthogonalise against, the sweep's own norm
-      if (i > 0) {
-        double* proj = sm + L.proj + (int64_t)(j + i) * L.ldf + r0;
-        for (int pass = 0; pass < 2; ++pass) {
-          double* c = sm + (pass == 0 ? L.c1 : L.c2);
-          LZ_HIP(h, launch_qtw(Vn, ld, h->rows_pad, i + 1, i, w, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
-          launch_final_rows(h->d_tpart, i + 1, plan.P, c, h->stream, plan.family == 2);
-          const int np = launch_trl_cgs(Vn, ld, h->rows_pad, i, c, w, h->d_tpart, nullptr, h->stream);
-          launch_trl_post(pass, h->d_tpart, np, c, i - 1, sm + L.nrm2, proj, h->d_tgate, 1, h->stream);  // (force: the gate is set, both passes run)
-        }
-        nrm2 = sm + L.nrm2;
-      }
-      launch_scale_store(Vn + (int64_t)i * ld, w, nrm2, sm + L.beta + j + i, h->rows_pad, h->stream);
+      tail.w = W + (int64_t)i * ld;
+      if (i == 0)  // nothing new to orthogonalise against: the sweep's own norm
+        launch_scale_store(tail.B, tail.w, sm + L.nrmb, sm + L.beta + j, h->rows_pad, h->stream);
+      else
+        LZ_TRY(orth_cgs_step(h, tail, h->trl_wk, plan, i, sm + L.proj + (int64_t)(j + i) * L.ldf + r0, sm + L.beta + j + i, OrthPass2::kUngated));
     }
     LZ_TRY(check_launch(h, "trl extend band"));
   }
@@ -327,10 +281,10 @@ int lz_trl_restart(lz_handle h, int m, int kk, const double* S) {
   LZ_TRY(trl_state(h, "lz_trl_restart"));
   if (!S || m != h->trl_m || kk < 1 || kk >= m) return fail(h, LZ_ERR_ARG, "lz_trl_restart: need m == the m of lz_trl_begin, 1 <= kk < m, S");
   const TrlSmall L = trl_small_layout(h);
-  LZ_TRY(upload(h, h->d_tsm + L.S, S, (size_t)m * kk * sizeof(double)));
-  LZ_HIP(h, launch_trl_restart(h->d_trl, h->trl_ld, h->rows, m, kk, h->d_tsm + L.S, h->stream));
+  LZ_TRY(upload(h, h->trl_wk.sm + L.S, S, (size_t)m * kk * sizeof(double)));
+  LZ_HIP(h, launch_trl_restart(h->trl.B, h->trl.ld, h->rows, m, kk, h->trl_wk.sm + L.S, h->stream));
   for (int r = 1; r < h->trl_b; ++r)  // band: the other residual rows follow V[m] (ascending: a destination is never a source still to be copied)
-    LZ_HIP(h, hipMemcpyAsync(h->d_trl + (int64_t)(kk + r) * h->trl_ld, h->d_trl + (int64_t)(m + r) * h->trl_ld, (size_t)h->rows * sizeof(double),
+    LZ_HIP(h, hipMemcpyAsync(h->trl.B + (int64_t)(kk + r) * h->trl.ld, h->trl.B + (int64_t)(m + r) * h->trl.ld, (size_t)h->rows * sizeof(double),
                              hipMemcpyDeviceToDevice, h->stream));
   LZ_TRY(check_launch(h, "trl restart"));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
@@ -340,44 +294,35 @@ int lz_trl_restart(lz_handle h, int m, int kk, const double* S) {
 int lz_trl_probe(lz_handle h, int k, const double* x) {
   LZ_TRY(trl_state(h, "lz_trl_probe"));
   if (!x || k < 0 || k > h->trl_m + h->trl_b - 1) return fail(h, LZ_ERR_ARG, "lz_trl_probe: need 0 <= k <= m (band: m + b - 1) and x");
-  LZ_TRY(trl_upload_x(h, x));
-  return trl_orth_store(h, k);
+  return trl_store_x(h, k, x);
 }
 
 int lz_trl_get_vectors(lz_handle h, int k, double* Y_out) {
   LZ_TRY(trl_state(h, "lz_trl_get_vectors"));
   if (!Y_out || k < 1 || k > h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_get_vectors: need 1 <= k <= m and Y_out");
-  std::vector<double> rowsk((size_t)k * (size_t)h->rows);
-  LZ_HIP(h, xfer_d2h(h->dev, h->stream, h->xfer, rowsk.data(), (size_t)h->rows * sizeof(double), h->d_trl, (size_t)h->trl_ld * sizeof(double),
-                     (size_t)h->rows * sizeof(double), (size_t)k));
-  const int64_t M = h->rows;
-  parallel_ranges(M, 1 << 16, [&](int, int64_t lo, int64_t hi) {
-    for (int64_t r = lo; r < hi; ++r)
-      for (int i = 0; i < k; ++i) Y_out[r * k + i] = rowsk[(size_t)i * M + r];
-  });
-  return LZ_OK;
+  return orth_get_vectors(h, h->trl, k, Y_out);
 }
 
 int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
   LZ_TRY(trl_state(h, "lz_trl_residuals"));
   if (!theta || !out || k < 1 || k > h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_residuals: need 1 <= k <= m, theta and out");
   const TrlSmall L = trl_small_layout(h);
-  double* dth = h->d_tsm + L.theta;
+  double* dth = h->trl_wk.sm + L.theta;
   LZ_TRY(upload(h, dth, theta, (size_t)k * sizeof(double)));
   int G = 0;
   if (h->kind == 1) {
-    G = launch_trl_resid_csr(h->csr, h->d_trl, h->trl_ld, k, dth, h->d_tpart, h->stream);
+    G = launch_trl_resid_csr(h->csr, h->trl.B, h->trl.ld, k, dth, h->trl_wk.part, h->stream);
   } else {
     const int Gd = (int)((h->rows + kTPB - 1) / kTPB);
     for (int i = 0; i < k; ++i) {
-      const double* x = h->d_trl + (int64_t)i * h->trl_ld;
-      launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, h->d_tw, h->d_tpart + (size_t)k * Gd, h->stream);
-      G = launch_trl_resid_diff(h->d_tw, x, h->rows, dth, i, h->d_tpart, h->stream);
+      const double* x = h->trl.B + (int64_t)i * h->trl.ld;
+      launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, h->trl.w, h->trl_wk.part + (size_t)k * Gd, h->stream);
+      G = launch_trl_resid_diff(h->trl.w, x, h->rows, dth, i, h->trl_wk.part, h->stream);
     }
   }
-  launch_trl_rownorm(h->d_tpart, G, k, h->d_tsm + L.res, h->stream);
+  launch_trl_rownorm(h->trl_wk.part, G, k, h->trl_wk.sm + L.res, h->stream);
   LZ_TRY(check_launch(h, "trl residuals"));
-  LZ_HIP(h, hipMemcpyAsync(out, h->d_tsm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(out, h->trl_wk.sm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   return LZ_OK;
 }
@@ -400,12 +345,12 @@ int lz_trl_filter_apply(lz_handle h, const double* x, double* y) {
   if (!x || !y) return fail(h, LZ_ERR_ARG, "lz_trl_filter_apply: need x and y");
   if (h->poly.kind == TrlPoly::kNone)
     return fail(h, LZ_ERR_STATE, "lz_trl_filter_apply: no filter set (lz_trl_set_filter or lz_trl_set_series first)");
-  double* vm = h->d_trl + (int64_t)h->trl_m * h->trl_ld;  // the residual row carries x and then the result
+  double* vm = h->trl.B + (int64_t)h->trl_m * h->trl.ld;  // the residual row carries x and then the result
   LZ_TRY(upload(h, vm, x, (size_t)h->rows * sizeof(double)));
-  trl_apply_op(h, vm, h->d_tw);
+  trl_apply_op(h, vm, h->trl.w);
   LZ_TRY(check_launch(h, "trl filter apply"));
-  LZ_HIP(h, hipMemcpyAsync(vm, h->d_tw, (size_t)h->rows_pad * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(y, h->d_tw, (size_t)h->rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(vm, h->trl.w, (size_t)h->rows_pad * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(y, h->trl.w, (size_t)h->rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   return LZ_OK;
 }
@@ -414,14 +359,13 @@ int lz_trl_rayleigh(lz_handle h, int k, double* G_out) {
   LZ_TRY(trl_state(h, "lz_trl_rayleigh"));
   if (!G_out || k < 1 || k >= h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_rayleigh: need 1 <= k < m and G_out");
   const TrlSmall L = trl_small_layout(h);
-  double* V = h->d_trl;
-  double* G = h->d_tsm + L.S;  // k x k in the restart's S area
-  const QtwPlan plan = trl_plan(h);
+  const OrthBasis& V = h->trl;
+  double* G = h->trl_wk.sm + L.S;  // k x k in the restart's S area
+  const QtwPlan plan = orth_plan(h, V);
   for (int i = 0; i < k; ++i) {
-    trl_matvec(h, V + (int64_t)i * h->trl_ld, h->d_tw);  // A itself, filter or not
-    LZ_HIP(h, launch_qtw(V, h->trl_ld, h->rows_pad, k + 1, k, h->d_tw, nullptr, nullptr, plan, h->d_tpart, 2, h->stream));
-    launch_final_rows(h->d_tpart, k + 1, plan.P, h->d_tsm + L.c1, h->stream, plan.family == 2);
-    LZ_HIP(h, hipMemcpyAsync(G + (int64_t)i * k, h->d_tsm + L.c1, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    trl_matvec(h, V.B + (int64_t)i * V.ld, V.w);  // A itself, filter or not
+    LZ_TRY(orth_dots(h, V, h->trl_wk, plan, k, h->trl_wk.sm + L.c1));
+    LZ_HIP(h, hipMemcpyAsync(G + (int64_t)i * k, h->trl_wk.sm + L.c1, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     LZ_TRY(check_launch(h, "trl rayleigh"));
   }
   LZ_HIP(h, hipMemcpyAsync(G_out, G, (size_t)k * k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -431,22 +375,12 @@ int lz_trl_rayleigh(lz_handle h, int k, double* G_out) {
 
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld) {
   LZ_TRY(trl_state(h, "lz_trl_set_rows"));
-  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + h->trl_b || ld < h->rows_pad)
-    return fail(h, LZ_ERR_ARG, "lz_trl_set_rows: need rows j0 .. j0 + count - 1 <= m (band: m + b - 1) and ld >= the padded row length");
-  LZ_TRY(upload2d(h, h->d_trl + (int64_t)j0 * h->trl_ld, (size_t)h->trl_ld * sizeof(double), rows, (size_t)ld * sizeof(double),
-                  (size_t)h->rows_pad * sizeof(double), (size_t)count));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  return LZ_OK;
+  return orth_set_rows(h, h->trl, "lz_trl_set_rows", "m (band: m + b - 1)", j0, count, rows, ld);
 }
 
 int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld) {
   LZ_TRY(trl_state(h, "lz_trl_get_rows"));
-  if (!rows || j0 < 0 || count < 1 || j0 + count > h->trl_m + h->trl_b || ld < h->rows_pad)
-    return fail(h, LZ_ERR_ARG, "lz_trl_get_rows: need rows j0 .. j0 + count - 1 <= m (band: m + b - 1) and ld >= the padded row length");
-  LZ_HIP(h, hipMemcpy2DAsync(rows, (size_t)ld * sizeof(double), h->d_trl + (int64_t)j0 * h->trl_ld, (size_t)h->trl_ld * sizeof(double),
-                             (size_t)h->rows_pad * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  return LZ_OK;
+  return orth_get_rows(h, h->trl, "lz_trl_get_rows", "m (band: m + b - 1)", j0, count, rows, ld);
 }
 
 }  // extern "C"

@@ -189,9 +189,9 @@ PROBES = [(1, 0), (1, 5), (1, M17), (0, 0), (0, 5), (0, M17 - 1)]
 
 
 def test_probe_matches_numpy(factored):
-    """Guards lz_gk_api.hip: lz_gk_probe's bound `k > h->gk.m - (side == 0 ? 1 : 0)`, gk_upload_x's memset of the work vector's
-    padding, gk_orth_store's two CGS passes over rows [0, k) (`launch_qtw(s.B, s.ld, s.pad, k + 1, k, ...)`: row k is the self slot
-    and is not read), its `k == 0` norm-only branch and launch_scale_store's write of row k alone."""
+    """Guards lz_gk_api.hip: lz_gk_probe's bound `k > h->gk.m - (side == 0 ? 1 : 0)`; lz_orth.hip: orth_upload_x's memset of the work
+    vector's padding, orth_store's two CGS passes over rows [0, k) (orth_dots' `launch_qtw(b.B, b.ld, b.pad, n + 1, n, ...)`: row k is
+    the self slot and is not read), its `k == 0` norm-only branch and launch_scale_store's write of row k alone."""
     pr, U, V, *_ = factored
     rng = np.random.default_rng(3)
     for side, k in PROBES:
@@ -287,7 +287,7 @@ def orthonormal_rows(count, n, rng):
 
 @pytest.mark.parametrize("k,m", [(0, 17), (5, 17), (0, 23), (5, 23)])
 def test_extension_never_reads_dead_rows(k, m, anorm):
-    """Guards lz_gk_api.hip, gk_half_step: `launch_qtw(s.B, s.ld, s.pad, nb + 1, nb, ...)` and `launch_trl_cgs(.., nb, ..)` read rows
+    """Guards lz_orth.hip, orth_cgs_step: orth_dots' `launch_qtw(b.B, b.ld, b.pad, n + 1, n, ...)` and `launch_trl_cgs(.., nb, ..)` read rows
     [0, nb) only - lz_reorth.hip's tile_rows clamps the rows of a ragged last tile to `nrows - 1` and steps off row j (`i == jskip`)
     instead of multiplying whatever lies there by zero - and launch_spmv_rect reads x at column indices only, never its padding.
     Rows at and behind the first one an extension writes are NaN, padding included, as a vanished alpha or beta leaves them."""
@@ -314,7 +314,7 @@ def test_extension_never_reads_dead_rows(k, m, anorm):
 
 
 def test_probe_never_reads_dead_rows(factored):
-    """Guards lz_gk_api.hip, gk_orth_store (see test_probe_matches_numpy): with U[5 ..] or V[6 ..] NaN, padding included, a probe of a
+    """Guards lz_orth.hip, orth_store (see test_probe_matches_numpy): with U[5 ..] or V[6 ..] NaN, padding included, a probe of a
     row in front of them, or of the first dead row itself, still gives NumpyGKBackend's row."""
     pr, U, V, *_ = factored
     Ud, Vd = U.copy(), V.copy()
@@ -368,8 +368,8 @@ def test_restart_with_a_dead_last_row(m, kk):
 @pytest.mark.parametrize("M,N,k,ncv", TINY)
 def test_svds_at_the_size_limits(M, N, k, ncv):
     """Guards lz_gk_api.hip: lz_gk_set_csr's `q < 2 || p < q` and its padded lengths (`round_up(q, kPadDoubles)` with q below one
-    padded row), lz_gk_begin's `m > g.q`; and, since every case has ncv = min(M, N), the device's exhausted short space: the
-    unsynchronised `w / 0` of the last half step (gk_half_step's launch_scale_store) leaves V[m] NaN, which lz_gk_restart copies to
+    padded row), lz_gk_begin's `m > g.V.len`; and, since every case has ncv = min(M, N), the device's exhausted short space: the
+    unsynchronised `w / 0` of the last half step (orth_cgs_step's launch_scale_store) leaves V[m] NaN, which lz_gk_restart copies to
     V[k] and lz_gk_residuals / lz_gk_get_vectors (rows [0, k)) never read."""
     A = tiny_matrix(M, N)
     info = {}
