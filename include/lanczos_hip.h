@@ -385,7 +385,7 @@ int lz_last_one_sweep_fused(lz_handle h, int* fused);
  * correction owes to w_{j+1} is applied as a combination of basis rows): (n - 2) / 2 pairs, an odd last step runs the single form.
  * 0 after the single forms, after any other loop, and after a run that abandoned its pairs.  lz_last_one_sweep_fused stays 1. */
 int lz_last_one_sweep_pairs(lz_handle h, int* pairs);
-/* 1 when the last lz_run tried the pair form and a pair's prediction missed by more than the gate (1e-14): a pair has no correcting
+/* 1 when the last run (lz_run or a resume) tried the pair form and a pair's prediction missed by more than the gate (1e-14): a pair has no correcting
  * sweep, so the whole run was repeated on the single fused form (what was returned is that run's result, bit for bit).  The handle
  * remembers it until a matrix is set again: later runs take the single form at once and report 0 here. */
 int lz_last_pair_abandoned(lz_handle h, int* abandoned);
@@ -395,8 +395,8 @@ int lz_last_pair_abandoned(lz_handle h, int* abandoned);
  * measured dots d[i] = V_i . u_j, nrm2 = ||w_j||^2. */
 int lz_one_sweep_host_predict(int n, int j, const double* H, const double* G, double alpha_j, double beta_j, double nrm2, double* chat);
 int lz_one_sweep_host_post(int n, int j, const double* G, const double* d, const double* chat, double nrm2, double* col);
-/* Host <-> device synchronisations lz_run made between its first and its last launch (the final wait for alpha / beta is not
- * counted).  0 for every loop on one rank and over RCCL - including, since round 4, the partial re-orthogonalisation mode
+/* Host <-> device synchronisations the last run (lz_run or a resume) made between its first and its last launch (the final wait for
+ * alpha / beta is not counted).  0 for every loop on one rank and over RCCL - including, since round 4, the partial re-orthogonalisation mode
  * (engine 7: Simon's omega-recurrence and the sweep decision live on the device; lz_set_tuning(h, 18, 1) selects the former
  * host-decided loop, engine 0, which reads two scalars back per step).  The host-staged collective backend (tests) counts two
  * per collective. */

@@ -185,6 +185,8 @@ struct lz_context {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
   hipEvent_t run_a = nullptr, run_b = nullptr;
   bool run_timed = false;
+  // the per-run record - last_engine, last_sweeps, last_misses, last_gate_trips, last_os_fused, last_os_pairs, last_pair_abandoned, sweep_log,
+  // host_syncs, r_state: reset in one place, RunFrame::begin (lz_loops.hip), by lz_run and by both resumes
   int last_sweeps = 0;
   std::vector<int> sweep_log;  // per step of the last lz_run: 1 = the re-orthogonalisation sweep ran (lz_last_sweep_log; device-decided loops only, else all 1)
   int last_misses = 0;  // one-reduce partial loop: vectors whose exact omega exceeded sqrt(eps) although the look-ahead gate had not swept them
@@ -198,13 +200,13 @@ struct lz_context {
   int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
   int last_os_fused = 0;       // one-sweep loop: 1 = the last lz_run took the fused form (no three-term pass)
   int last_os_pairs = 0;       // one-sweep loop: pair walks (one walk per two steps) behind the last lz_run's result; 0 after a repeat
-  int last_pair_abandoned = 0; // 1 = the last lz_run tried the pair form, a leftover exceeded kOneSweepTau and the run was repeated on the single form
+  int last_pair_abandoned = 0; // 1 = the last run (lz_run or a resume) tried the pair form, a leftover exceeded kOneSweepTau and the run was repeated on the single form
   bool pair_tripped = false;   // remembered until the matrix is set again: the pair form is not tried a second time
   double* d_om = nullptr;      // device-resident partial re-orthogonalisation: omega-recurrence state (omega_state_doubles)
   int* d_omi = nullptr;        //   ... gate of the coming step, sweep count, per-step sweep log (omega_state_ints)
   int om_n = 0;
   int om_run_n = 0;            // n of the last device-decided partial run: the layout of d_om (lz_get_omega_state)
-  int64_t host_syncs = 0;      // host <-> device synchronisations between the first and the last launch of the last lz_run
+  int64_t host_syncs = 0;      // host <-> device synchronisations between the first and the last launch of the last run (lz_run or a resume)
   // lz_reserve (may be called from a second host thread while this one prepares the matrix): device buffers for the basis and
   // the Ritz vectors of the coming run, adopted by basis_alloc / lz_ritz_vectors.  Only these fields are touched by it.
   std::mutex res_mu;
@@ -307,7 +309,8 @@ double spmv_bytes(lz_handle h, bool ell = false);  // ell: the launch takes the 
 double spmv_flops(lz_handle h);
 int step_spmv(lz_handle h, int j, double* alpha_dst = nullptr, bool reduce = true, int* np_out = nullptr);
 int step_reorth(lz_handle h, int j, int nrows, bool scale, int beta_idx, bool in_run_loop = false);
-int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm = true, int* np_out = nullptr);
+int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm = true, int* np_out = nullptr,
+                    double* r = nullptr, const char* what = "three_term");  // r: the residual buffer, nullptr = h->d_r; what: check_launch's name
 size_t fused_coff(lz_handle h);
 size_t onered_part_off(lz_handle h);
 int breakdown_status(lz_handle h, int n, const double* alpha_out, const double* beta_out);

@@ -1,5 +1,6 @@
 // The Krylov loops of lz_run: the individual steps, the six- / five- / three-launch loops, the one-reduce loop, the partial
-// re-orthogonalisation loops (host-decided and device-resident), loop selection, lz_run / lz_run_resume / lz_get_residual / lz_reserve.
+// re-orthogonalisation loops (host-decided and device-resident), loop selection, the run frame (RunFrame) that lz_run, lz_run_resume and
+// lz_run_resume_partial share, lz_get_residual / lz_reserve.
 #include "lz_context.h"
 
 using namespace lz;
@@ -7,6 +8,18 @@ using namespace lz::api;
 
 namespace lz {
 namespace api {
+
+// ---- the loops' common idioms --------------------------------------------------------------------------------------------
+inline double* basis_row(lz_handle h, int j) { return h->d_V + (int64_t)j * h->ldv; }
+// where step j of an n-step run parks the norm that forms V[j]: beta[j-1], with Python's negative index at j = 0
+inline int beta_index(int n, int j) { return (j + n - 2) % (n - 1); }
+inline double* beta_slot(lz_handle h, int n, int j) { return h->d_beta + beta_index(n, j); }
+// profile sampling (tune[7]): the centred sample of every stride - same mean j as the full run
+inline bool iter_sampled(lz_handle h, int j) {
+  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
+  return (j % pstride) == pstride / 2;
+}
+inline void begin_iter(lz_handle h, int j) { h->prof_iter = iter_sampled(h, j); }
 
 // ---- the individual steps (device-resident scalars, no host sync) --------
 int ensure_part(lz_handle h, size_t need) {
@@ -25,6 +38,13 @@ double spmv_bytes(lz_handle h, bool ell) {
 }
 double spmv_flops(lz_handle h) { return h->kind == 1 ? 2.0 * h->csr.nnz : 2.0 * (double)h->rows * (double)h->Mg; }
 
+// dst[0] = the sum of the np block partials a kernel left in d_part (this rank's share of a dot product)
+static int step_final_sum(lz_handle h, int np, double* dst, const char* what) {
+  Scope sc(h, LZ_K_FINAL, 0, 0);
+  launch_final_sum(h->d_part, np, dst, h->stream);
+  return check_launch(h, what);
+}
+
 // r = A V[j]; alpha_dst[0] = V[j] . r, summed over ranks unless reduce == false (one-reduce mode: the partial sum rides
 // in the next all-reduce)
 int step_spmv(lz_handle h, int j, double* alpha_dst, bool reduce, int* np_out) {
@@ -32,12 +52,12 @@ int step_spmv(lz_handle h, int j, double* alpha_dst, bool reduce, int* np_out) {
   const double* x = nullptr;
   if (h->halo_inflight_j == j) {  // exchange already issued on the comm stream behind the boundary update
     LZ_HIP(h, hipStreamWaitEvent(h->stream, h->e_halo, 0));
-    x = h->d_V + (int64_t)j * h->ldv;
+    x = basis_row(h, j);
     h->halo_inflight_j = -1;
   } else {
     LZ_TRY(comm_exchange_x(h, j, &x));
   }
-  const double* xown = h->d_V + (int64_t)j * h->ldv;
+  const double* xown = basis_row(h, j);
   int np = 0;
   {
     Scope sc(h, LZ_K_SPMV, spmv_bytes(h), spmv_flops(h));
@@ -51,11 +71,7 @@ int step_spmv(lz_handle h, int j, double* alpha_dst, bool reduce, int* np_out) {
     *np_out = np;
     return LZ_OK;
   }
-  {
-    Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_final_sum(h->d_part, np, alpha_dst, h->stream);
-    LZ_TRY(check_launch(h, "final_sum(alpha)"));
-  }
+  LZ_TRY(step_final_sum(h, np, alpha_dst, "final_sum(alpha)"));
   return reduce ? comm_allreduce(h, alpha_dst, 1) : LZ_OK;
 }
 
@@ -95,7 +111,7 @@ int step_reorth(lz_handle h, int j, int nrows, bool scale, int beta_idx, bool in
     return LZ_OK;
   }
   // 1. boundary positions (the faces the neighbours need), 2. their exchange on the comm stream, 3. interior
-  double* vj = h->d_V + (int64_t)j * h->ldv;
+  double* vj = basis_row(h, j);
   {
     Scope sc(h, LZ_K_UPDATE, 8.0 * (nrows - 1) * M + 16.0 * M, 2.0 * nrows * M);
     // both faces leave in ONE launch of the small-range kernel (the face kernel is a latency chain over the rows)
@@ -134,24 +150,69 @@ int step_reorth(lz_handle h, int j, int nrows, bool scale, int beta_idx, bool in
   return LZ_OK;
 }
 
-// r = r - alpha V[j] - beta V[jm1]; d_nrm2[0] = sum over ranks of ||r||^2
-int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm, int* np_out) {
+// r = r - alpha V[j] - beta V[jm1]; d_nrm2[0] = sum over ranks of ||r||^2.  r: the residual buffer (nullptr: h->d_r); what: the launch's
+// name in an error's text
+int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const double* d_beta, bool need_norm, int* np_out, double* r,
+                    const char* what) {
   const double M = (double)h->rows;
   int np = 0;
   {
     Scope sc(h, LZ_K_THREE, (jm1 >= 0 ? 32.0 : 24.0) * M, (jm1 >= 0 ? 6.0 : 4.0) * M);
-    np = launch_three_term(h->d_r, h->d_V + (int64_t)j * h->ldv, jm1 >= 0 ? h->d_V + (int64_t)jm1 * h->ldv : nullptr, d_alpha,
-                           d_beta, h->rows_pad, h->d_part, h->stream);
-    LZ_TRY(check_launch(h, "three_term"));
+    np = launch_three_term(r ? r : h->d_r, basis_row(h, j), jm1 >= 0 ? basis_row(h, jm1) : nullptr, d_alpha, d_beta, h->rows_pad, h->d_part,
+                           h->stream);
+    LZ_TRY(check_launch(h, what));
   }
   if (np_out) *np_out = np;  // (the caller's own kernel adds the partials)
   if (!need_norm) return LZ_OK;  // fused-norm mode: ||r||^2 travels with the next Q^T r all-reduce
-  {
-    Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_final_sum(h->d_part, np, h->d_nrm2, h->stream);
-    LZ_TRY(check_launch(h, "final_sum(nrm2)"));
-  }
+  LZ_TRY(step_final_sum(h, np, h->d_nrm2, "final_sum(nrm2)"));
   return comm_allreduce(h, h->d_nrm2, 1);
+}
+
+// warm-up (Lanczos.py:108-110): r = A v0; alpha0 = r.v0; r = r - alpha0 v0, ||r||^2 if need_norm
+static int warm_up(lz_handle h, bool need_norm) {
+  LZ_TRY(step_spmv(h, 0));
+  return step_three_term(h, 0, -1, h->d_alpha, nullptr, need_norm);
+}
+
+// r = r - coef[0] v: the one-reduce loops' halves of the recurrence
+static int step_two_term(lz_handle h, const double* v, const double* coef, const char* what) {
+  Scope sc(h, LZ_K_THREE, 24.0 * (double)h->rows, 2.0 * (double)h->rows);
+  launch_three_term(h->d_r, v, nullptr, coef, nullptr, h->rows_pad, h->d_part, h->stream);
+  return check_launch(h, what);
+}
+
+// The scale-on-read SpMV (ELL copy): V[j] = src / sqrt(nrm2[0]) wherever it reads x, beta -> its slot, dst = A V[j]; the alpha partials
+// stay in d_part, *np of them.  src and dst are the two residual buffers, never the same one (it reads src through its gathers).
+// gate: the kernel scales where gate[0] == 0 - the partial loop's sweep gate (a swept step's V[j] is in place), or a word that stays 0.
+static int step_scaling_spmv(lz_handle h, int n, int j, const double* src, double* dst, const int* gate, int* np) {
+  const double M = (double)h->rows;
+  double* vj = basis_row(h, j);
+  SpmvScale ss;
+  ss.r = src;
+  ss.nrm2 = h->d_nrm2;
+  ss.vj = vj;
+  ss.beta_slot = beta_slot(h, n, j);
+  ss.gate = gate;
+  // (the scale pass's 16M bytes ride here: BASELINE.md's accounting of the step is unchanged.  With a row-class coded matrix the
+  // launch moves 25 bytes per row - r once, y, V[j], the class byte - so only V[j]'s 8 are added: counting r twice would be a
+  // third of the total there)
+  Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
+  *np = launch_spmv_ell(h->csr, vj, dst, vj, h->d_part, h->stream, &ss);
+  return check_launch(h, "spmv(ell, scale fused)");
+}
+
+// The three-term recurrence in the prologue of step j's pass 1 (engines 2 and 3): r = (y - alpha v_{j-1}) - beta v_{j-2} -> d_r2.
+// apart / np: the SpMV's alpha partials the prologue adds itself, or nullptr / 0: alpha is read from its slot.
+static QtwFuse qtw_prologue_fuse(lz_handle h, int j, const double* apart, int np) {
+  QtwFuse fz;
+  fz.apart = apart;
+  fz.np = np;
+  fz.jprev = j > 0 ? j - 1 : 0;     // j == 0: the warm-up's alpha0 and r = A v0 - alpha0 v0 (Lanczos.py:109-110)
+  fz.jprev2 = j >= 2 ? j - 2 : -1;  // the reference's V[-1] term at its step 0 is the zero row
+  fz.beta_prev = h->d_beta + (j >= 2 ? j - 2 : 0);
+  fz.alpha_out = h->d_alpha + fz.jprev;
+  fz.r_out = h->d_r2;
+  return fz;
 }
 
 // ---- one-reduce mode (LZ_FLAG_ONE_REDUCE): the whole Krylov loop with ONE all-reduce per iteration ---------------------
@@ -164,50 +225,56 @@ int step_three_term(lz_handle h, int j, int jm1, const double* d_alpha, const do
 inline int onered_ldp(int m) { return qtw_ldp(m + 2); }
 inline int onered_slot(int m) { return onered_ldp(m) + m + 2; }  // where alpha lives in the reduce buffer at a step with m rows
 
+// The head of step j in both one-reduce loops (engines 6 and 8): pass 1 dots rows 0..j-1 against both columns (r'', u = row urow), the
+// second stage adds the blocks' runs into buf - unless pass 1's last block does that itself (ticket: the folded form) -, and buf travels
+// in THE all-reduce of the iteration.  part: where pass 1 leaves its partials.  gate == nullptr: the ungated form, its bytes counted
+// here; with a gate the launches return at once where gate[0] == 0 and what really ran is accounted after the run (account_partial_device).
+static int step_onereduce_head(lz_handle h, int j, int urow, double* part, double* buf, const int* gate, unsigned* ticket) {
+  const double M = (double)h->rows;
+  const int ldp = onered_ldp(j);
+  QtwFuse fz;
+  fz.gate = gate;
+  if (ticket) {
+    fz.ticket = ticket;
+    fz.c_out = buf;
+  }
+  h->qplan.variant = 0;
+  {
+    Scope sc(h, LZ_K_QTW, gate ? 0.0 : 8.0 * j * M + 16.0 * M, gate ? 0.0 : 4.0 * (j + 1) * M);
+    LZ_HIP(h, launch_qtw(h->d_V, h->ldv, h->rows_pad, j, urow, h->d_r, nullptr, nullptr, h->qplan, part, 3, h->stream, gate ? &fz : nullptr));
+    LZ_TRY(check_launch(h, gate ? "qtw(two columns, gated)" : "qtw(two columns)"));
+  }
+  if (!ticket) {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_final_rows_t(part, h->qplan.G, 2 * ldp, ldp + j + 2, buf, h->stream, gate);
+    LZ_TRY(check_launch(h, gate ? "final_rows(gated)" : "final_rows"));
+  }
+  return comm_allreduce(h, buf, onered_slot(j) + 1);
+}
+
 int run_loop_onereduce(lz_handle h, int n) {
   const double M = (double)h->rows;
   LZ_TRY(step_spmv(h, 0, h->d_c + onered_slot(0), false));  // warm-up: r'' = A v0 (Lanczos.py:108), alpha0 partial
   for (int j = 0; j < n; ++j) {
-    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
-    const int m = j, urow = j > 0 ? j - 1 : 0, ldp = onered_ldp(m);
-    double* u = h->d_V + (int64_t)urow * h->ldv;
-    h->qplan.variant = 0;
-    {
-      Scope sc(h, LZ_K_QTW, 8.0 * m * M + 16.0 * M, 4.0 * (m + 1) * M);
-      LZ_HIP(h, launch_qtw(h->d_V, h->ldv, h->rows_pad, m, urow, h->d_r, nullptr, nullptr, h->qplan, h->d_part, 3, h->stream));
-      LZ_TRY(check_launch(h, "qtw(two columns)"));
-    }
+    begin_iter(h, j);
+    const int urow = j > 0 ? j - 1 : 0;
+    LZ_TRY(step_onereduce_head(h, j, urow, h->d_part, h->d_c, nullptr, nullptr));
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_final_rows_t(h->d_part, h->qplan.G, 2 * ldp, ldp + m + 2, h->d_c, h->stream);
-      LZ_TRY(check_launch(h, "final_rows"));
-    }
-    LZ_TRY(comm_allreduce(h, h->d_c, onered_slot(m) + 1));  // THE collective of this iteration
-    {
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_onereduce_prepare(h->d_c, m, ldp, h->d_alpha + urow, h->d_nrm2 + 1, h->stream);  // j = 0: alpha[0] of the warm-up, rewritten below
+      launch_onereduce_prepare(h->d_c, j, onered_ldp(j), h->d_alpha + urow, h->d_nrm2 + 1, h->stream);  // j = 0: alpha[0] of the warm-up, rewritten below
       LZ_TRY(check_launch(h, "onereduce_prepare"));
     }
-    {
-      Scope sc(h, LZ_K_THREE, 24.0 * M, 2.0 * M);
-      launch_three_term(h->d_r, u, nullptr, h->d_alpha + urow, nullptr, h->rows_pad, h->d_part, h->stream);  // r = r'' - alpha u
-      LZ_TRY(check_launch(h, "three_term(alpha)"));
-    }
+    LZ_TRY(step_two_term(h, basis_row(h, urow), h->d_alpha + urow, "three_term(alpha)"));  // r = r'' - alpha u
     {
       Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 2.0 * (j + 1) * M);
-      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, h->d_r, h->d_beta + bidx, h->tune[8] == 0 || h->tune[8] >= 3 ? h->tune[8] : 0,
+      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, h->d_r, beta_slot(h, n, j), h->tune[8] == 0 || h->tune[8] >= 3 ? h->tune[8] : 0,
                     h->stream, 0, -1, 1);
       LZ_TRY(check_launch(h, "update"));
     }
     const bool last = j == n - 1;
     LZ_TRY(step_spmv(h, j, last ? h->d_alpha + j : h->d_c + onered_slot(j + 1), last));  // the last alpha has no pass to ride on
-    if (!last && j > 0) {
-      Scope sc(h, LZ_K_THREE, 24.0 * M, 2.0 * M);
-      launch_three_term(h->d_r, h->d_V + (int64_t)(j - 1) * h->ldv, nullptr, h->d_beta + bidx, nullptr, h->rows_pad, h->d_part, h->stream);
-      LZ_TRY(check_launch(h, "three_term(beta)"));  // r'' = A V[j] - beta V[j-1]; at j = 0 the reference's V[-1] is the zero row
-    }
+    // r'' = A V[j] - beta V[j-1]; at j = 0 the reference's V[-1] is the zero row
+    if (!last && j > 0) LZ_TRY(step_two_term(h, basis_row(h, j - 1), beta_slot(h, n, j), "three_term(beta)"));
   }
   return LZ_OK;
 }
@@ -236,17 +303,8 @@ int run_loop_fused_small(lz_handle h, int n) {
   int np = 0;
   LZ_TRY(step_spmv(h, 0, nullptr, false, &np));  // warm-up: y = A v0 (Lanczos.py:108)
   for (int j = 0; j < n; ++j) {
-    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
-    QtwFuse fz;
-    fz.apart = h->d_part;
-    fz.np = np;
-    fz.jprev = j > 0 ? j - 1 : 0;   // j == 0: the warm-up's alpha0 and r = A v0 - alpha0 v0 (Lanczos.py:109-110)
-    fz.jprev2 = j >= 2 ? j - 2 : -1;  // the reference's V[-1] term at its step 0 is the zero row
-    fz.beta_prev = h->d_beta + (j >= 2 ? j - 2 : 0);
-    fz.alpha_out = h->d_alpha + fz.jprev;
-    fz.r_out = h->d_r2;
+    begin_iter(h, j);
+    const QtwFuse fz = qtw_prologue_fuse(h, j, h->d_part, np);
     h->qplan.variant = 0;
     {
       Scope sc(h, LZ_K_QTW, 8.0 * j * M + 40.0 * M, 2.0 * (j + 1) * M + 4.0 * M);
@@ -255,17 +313,14 @@ int run_loop_fused_small(lz_handle h, int n) {
     }
     {
       Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 2.0 * (j + 1) * M);
-      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_part + coff, h->d_r2, h->d_beta + bidx, 0, h->stream, 0, -1, 2, 0, 0, h->qplan.G,
+      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_part + coff, h->d_r2, beta_slot(h, n, j), 0, h->stream, 0, -1, 2, 0, 0, h->qplan.G,
                     qtw_ldp(j + 1));
       LZ_TRY(check_launch(h, "update(fused reduction)"));
     }
     LZ_TRY(step_spmv(h, j, nullptr, false, &np));
   }
-  {
-    Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_final_sum(h->d_part, np, h->d_alpha + (n - 1), h->stream);  // the last alpha has no consumer kernel to ride in
-    LZ_TRY(check_launch(h, "final_sum(alpha)"));
-  }
+  LZ_TRY(step_final_sum(h, np, h->d_alpha + (n - 1), "final_sum(alpha)"));  // the last alpha has no consumer kernel to ride in
+  h->r_state = 2;  // d_r holds y = A v_{n-1}: the recurrence rode in the next step's pass 1 (lz_get_residual forms r)
   return LZ_OK;
 }
 
@@ -283,17 +338,8 @@ int run_loop_three_term_fused(lz_handle h, int n) {
   const double M = (double)h->rows;
   LZ_TRY(step_spmv(h, 0));  // warm-up: y = A v0, alpha_0 (Lanczos.py:108-109)
   for (int j = 0; j < n; ++j) {
-    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
-    QtwFuse fz;
-    fz.apart = nullptr;
-    fz.np = 0;
-    fz.jprev = j > 0 ? j - 1 : 0;     // j == 0: the warm-up's r = A v0 - alpha0 v0 (Lanczos.py:110)
-    fz.jprev2 = j >= 2 ? j - 2 : -1;  // the reference's V[-1] term at its step 0 is the zero row
-    fz.beta_prev = h->d_beta + (j >= 2 ? j - 2 : 0);
-    fz.alpha_out = h->d_alpha + fz.jprev;
-    fz.r_out = h->d_r2;
+    begin_iter(h, j);
+    const QtwFuse fz = qtw_prologue_fuse(h, j, nullptr, 0);
     h->qplan.variant = 0;
     {
       Scope sc(h, LZ_K_QTW, 8.0 * j * M + 40.0 * M, 2.0 * (j + 1) * M + 4.0 * M);
@@ -308,11 +354,12 @@ int run_loop_three_term_fused(lz_handle h, int n) {
     LZ_TRY(comm_allreduce(h, h->d_c, j + 1));
     {
       Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 2.0 * (j + 1) * M);
-      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, h->d_r2, h->d_beta + bidx, 0, h->stream, 0, -1, 1);
+      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, h->d_r2, beta_slot(h, n, j), 0, h->stream, 0, -1, 1);
       LZ_TRY(check_launch(h, "update"));
     }
     LZ_TRY(step_spmv(h, j));
   }
+  h->r_state = 2;  // as after run_loop_fused_small
   return LZ_OK;
 }
 
@@ -445,15 +492,14 @@ static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_block
 // post, gated correction of step j
 static int one_sweep_step(lz_handle h, int n, int j, const OneSweepState& st, bool fused) {
   const double M = (double)h->rows;
-  const int bidx = (j + n - 2) % (n - 1);  // beta[j-1] with Python's negative index at j = 0
-  double* dst = fused ? h->d_r2 : h->d_V + (int64_t)j * h->ldv;
+  double* dst = fused ? h->d_r2 : basis_row(h, j);
   {
     Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 16.0 * M, 4.0 * (j + 1) * M);
     if (fused)  // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-2} v_{j-2}: the beta that formed v_{j-1} sits at step j - 1's slot
       launch_os_sweep(2, h->d_V, h->ldv, h->rows_pad, j, st.chat, h->d_r, nullptr, nullptr, h->d_part, nullptr, h->stream, dst, h->d_alpha + (j - 1),
-                      h->d_beta + (j - 1 + n - 2) % (n - 1));
+                      beta_slot(h, n, j - 1));
     else
-      launch_os_sweep(0, h->d_V, h->ldv, h->rows_pad, j, st.chat, h->d_r, h->d_nrm2, h->d_beta + bidx, h->d_part, nullptr, h->stream);
+      launch_os_sweep(0, h->d_V, h->ldv, h->rows_pad, j, st.chat, h->d_r, h->d_nrm2, beta_slot(h, n, j), h->d_part, nullptr, h->stream);
     LZ_TRY(check_launch(h, "one-sweep"));
   }
   {
@@ -475,26 +521,22 @@ static int one_sweep_step(lz_handle h, int n, int j, const OneSweepState& st, bo
 int run_loop_one_sweep(lz_handle h, int n) {
   OneSweepState st;
   LZ_TRY(one_sweep_setup(h, n, st));
-  h->last_os_fused = 0;
-  // warm-up (Lanczos.py:108-110): r = A v0; alpha0 = r.v0; r = r - alpha0 v0, ||r||^2
-  LZ_TRY(step_spmv(h, 0));
-  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
+  LZ_TRY(warm_up(h, true));
   for (int j = 0; j < n; ++j) {
-    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
+    begin_iter(h, j);
     LZ_TRY(one_sweep_step(h, n, j, st, false));
     LZ_TRY(step_spmv(h, j));
     // at j = 0 the reference subtracts beta * V[-1], the still-zero last row: a no-op
     int np = 0;
-    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, false, &np));
+    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, beta_slot(h, n, j), false, &np));
     {  // ||w_{j+1}||^2 from the three-term kernel's partials and the next step's predictions, one launch
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_sum_predict(h->d_part, np, h->d_nrm2, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, false,
+      launch_os_sum_predict(h->d_part, np, h->d_nrm2, st.G, st.H, n, j, h->d_alpha + j, beta_slot(h, n, j), st.chat, false,
                             j + 1 < n, h->stream);
       LZ_TRY(check_launch(h, "final_sum(nrm2) + one-sweep predict"));
     }
   }
+  h->r_state = 1;
   return LZ_OK;
 }
 
@@ -514,26 +556,9 @@ bool one_sweep_fused_applies(lz_handle h, int n) {
   return one_rank && h->kind == 1 && ell_usable(h->csr, h->flags) && (h->csr.fixed_k == 5 || h->csr.fixed_k == 7) && n <= kOneSweepFusedMaxN &&
          h->tune[15] != 7;
 }
-// The scale-on-read SpMV of the fused and the pair form: V[j] = src / sqrt(nrm2[0]) wherever it reads x, beta -> its slot, dst = A V[j];
-// returns the alpha partials in d_part (src and dst are the two residual buffers, never the same one)
-static int one_sweep_scaling_spmv(lz_handle h, int n, int j, const double* src, double* dst, int* npa) {
-  const double M = (double)h->rows;
-  double* vj = h->d_V + (int64_t)j * h->ldv;
-  SpmvScale ss;
-  ss.r = src;
-  ss.nrm2 = h->d_nrm2;
-  ss.vj = vj;
-  ss.beta_slot = h->d_beta + (j + n - 2) % (n - 1);
-  ss.gate = h->d_osi + 2;  // always 0: scale on read
-  // (bytes as the partial loop counts its fused SpMV: with a row-class coded matrix u~ once, y, V[j] and the class byte)
-  Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
-  *npa = launch_spmv_ell(h->csr, vj, dst, vj, h->d_part, h->stream, &ss);
-  return check_launch(h, "spmv(ell, scale fused)");
-}
 // one step of the fused form: sweep / post / gated correction, SpMV, alpha sum + the next step's predictions
 static int one_sweep_fused_iter(lz_handle h, int n, int j, const OneSweepState& st) {
-  const int bidx = (j + n - 2) % (n - 1);
-  double* vj = h->d_V + (int64_t)j * h->ldv;
+  double* vj = basis_row(h, j);
   LZ_TRY(one_sweep_step(h, n, j, st, j > 0));
   int npa = 0;
   if (j == 0) {  // step 0 is the unfused form's: V[0] is in place, a plain SpMV
@@ -541,29 +566,32 @@ static int one_sweep_fused_iter(lz_handle h, int n, int j, const OneSweepState& 
     npa = launch_spmv_csr(h->csr, vj, h->d_r, vj, h->d_part, h->flags, h->stream);
     LZ_TRY(check_launch(h, "spmv"));
   } else {
-    LZ_TRY(one_sweep_scaling_spmv(h, n, j, h->d_r2, h->d_r, &npa));
+    LZ_TRY(step_scaling_spmv(h, n, j, h->d_r2, h->d_r, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
   }
   {  // alpha_j from the SpMV's partials and the next step's predictions, one launch
     Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_os_sum_predict(h->d_part, npa, h->d_alpha + j, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + bidx, st.chat, true, j + 1 < n, h->stream);
+    launch_os_sum_predict(h->d_part, npa, h->d_alpha + j, st.G, st.H, n, j, h->d_alpha + j, beta_slot(h, n, j), st.chat, true, j + 1 < n, h->stream);
     LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
   }
+  return LZ_OK;
+}
+// after the last step of the fused and the pair form: r = (A v_{n-1} - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2}, ||r||^2 - the
+// residual entering step n
+static int one_sweep_fused_tail(lz_handle h, int n) {
+  LZ_TRY(step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), beta_slot(h, n, n - 1), true));
+  h->r_state = 1;
   return LZ_OK;
 }
 int run_loop_one_sweep_fused(lz_handle h, int n) {
   OneSweepState st;
   LZ_TRY(one_sweep_setup(h, n, st));
   h->last_os_fused = 1;
-  h->last_os_pairs = 0;
-  LZ_TRY(step_spmv(h, 0));
-  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
+  LZ_TRY(warm_up(h, true));
   for (int j = 0; j < n; ++j) {
-    const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-    h->prof_iter = (j % pstride) == pstride / 2;
+    begin_iter(h, j);
     LZ_TRY(one_sweep_fused_iter(h, n, j, st));
   }
-  // r = (A v_{n-1} - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2}, ||r||^2: the residual entering step n
-  return step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 1 + n - 2) % (n - 1), true);
+  return one_sweep_fused_tail(h, n);
 }
 
 // The pair form of the fused loop: ONE walk over the basis per TWO steps.  A walk applies coefficients of size O(eps) and measures dots
@@ -585,25 +613,22 @@ int run_loop_one_sweep_pair(lz_handle h, int n) {
   const int nbp = os_pair_sweep_blocks(h->rows_pad, wide16);
   LZ_TRY(one_sweep_setup(h, n, st, nbp));
   h->last_os_fused = 1;
-  h->last_os_pairs = 0;
   double* kap = st.g;  // (the correcting sweep's coefficient buffers are free while a pair runs)
   double* pp = st.g + n + 1;
-  LZ_TRY(step_spmv(h, 0));
-  LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, true));
-  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-  auto sampled = [&](int j) { return (j % pstride) == pstride / 2; };
+  const int* scale = h->d_osi + 2;  // (stays 0: the SpMVs always scale on read)
+  LZ_TRY(warm_up(h, true));
   for (int j = 0; j < n;) {
     if (j < 2 || j + 1 >= n) {
-      h->prof_iter = sampled(j);
+      begin_iter(h, j);
       LZ_TRY(one_sweep_fused_iter(h, n, j, st));
       j += 1;
       continue;
     }
-    h->prof_iter = sampled(j) || sampled(j + 1);
+    h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1);
     // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-1} v_{j-2} -> d_r, ||w_j||^2 -> d_nrm2
     LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
     int npa = 0;
-    LZ_TRY(one_sweep_scaling_spmv(h, n, j, h->d_r, h->d_r2, &npa));  // y° = A (w_j / b); the V[j] it stores is provisional
+    LZ_TRY(step_scaling_spmv(h, n, j, h->d_r, h->d_r2, scale, &npa));  // y° = A (w_j / b); the V[j] it stores is provisional
     const int ldp = os_pair_ldp(j);
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
@@ -622,7 +647,7 @@ int run_loop_one_sweep_pair(lz_handle h, int n) {
       launch_os_pair_post(h->d_c, ldp, st.chat, kap, pp, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, kOneSweepTau, h->d_osi, st.elog, h->stream);
       LZ_TRY(check_launch(h, "one-sweep pair post"));
     }
-    LZ_TRY(one_sweep_scaling_spmv(h, n, j + 1, h->d_r2, h->d_r, &npa));  // V[j+1] = u~_{j+1} / beta_{j+1}, y = A V[j+1]
+    LZ_TRY(step_scaling_spmv(h, n, j + 1, h->d_r2, h->d_r, scale, &npa));  // V[j+1] = u~_{j+1} / beta_{j+1}, y = A V[j+1]
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
       launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 1), st.G, st.H, n, j + 1, h->d_alpha + (j + 1), h->d_beta + j, st.chat, true,
@@ -632,7 +657,7 @@ int run_loop_one_sweep_pair(lz_handle h, int n) {
     h->last_os_pairs += 1;
     j += 2;
   }
-  return step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 1 + n - 2) % (n - 1), true);
+  return one_sweep_fused_tail(h, n);
 }
 
 // ---- which loop structure runs the Krylov iteration --------------------------------------------------------------------
@@ -650,11 +675,13 @@ enum Loop {
   LOOP_ONE_SWEEP = 9          // above kThreeTermFusedMaxRows rows on one rank: one walk over the basis per step (run_loop_one_sweep)
 };
 
-Loop choose_loop(lz_handle h, int n) {
+// plan: the Q^T w plan the run will use - the handle's, made by basis_alloc for n rows, unless the caller asks before it allocates
+Loop choose_loop(lz_handle h, int n, const QtwPlan* plan = nullptr) {
   const int f = h->flags;
-  const bool default_kernels = h->qplan.family == 2 && !(f & (LZ_FLAG_QTW_MFMA | LZ_FLAG_QTW_VALU)) && h->tune[1] == 0 && h->tune[8] == 0;
+  const QtwPlan& qp = plan ? *plan : h->qplan;
+  const bool default_kernels = qp.family == 2 && !(f & (LZ_FLAG_QTW_MFMA | LZ_FLAG_QTW_VALU)) && h->tune[1] == 0 && h->tune[8] == 0;
   const bool full_fused = (f & LZ_FLAG_FUSED_NORM) && !(f & LZ_FLAG_REORTH_PARTIAL);
-  if ((f & LZ_FLAG_ONE_REDUCE) && !(f & LZ_FLAG_REORTH_PARTIAL) && h->qplan.family == 2) return LOOP_ONE_REDUCE;
+  if ((f & LZ_FLAG_ONE_REDUCE) && !(f & LZ_FLAG_REORTH_PARTIAL) && qp.family == 2) return LOOP_ONE_REDUCE;
   if ((f & LZ_FLAG_ONE_REDUCE) && (f & LZ_FLAG_REORTH_PARTIAL) && default_kernels && h->tune[18] != 1 && !(f & LZ_FLAG_OVERLAP_HALO))
     return LOOP_PARTIAL_ONE_REDUCE;
   // partial re-orthogonalisation: device-resident decisions with the default kernels (tune[18] == 1: the host-decided loop,
@@ -664,7 +691,7 @@ Loop choose_loop(lz_handle h, int n) {
 #ifdef LZ_KBENCH
   const bool want_steps = h->tune[15] == 5 && n <= kSmallStepMaxN;
   if ((h->tune[15] == 2 || h->tune[15] == 3 || want_steps) && one_rank && full_fused && default_kernels && !(f & LZ_FLAG_SPMV_SCALAR) &&
-      h->qplan.L == 512 && h->rows_pad <= kSmallMaxPadRows && n <= kSmallMaxPadRows && small_engine_applies(h))
+      qp.L == 512 && h->rows_pad <= kSmallMaxPadRows && n <= kSmallMaxPadRows && small_engine_applies(h))
     return want_steps ? LOOP_SMALL_STEP : LOOP_SMALL_ENGINE;
   const bool knob_auto = h->tune[15] == 0 || h->tune[15] == 5;
 #else
@@ -675,7 +702,7 @@ Loop choose_loop(lz_handle h, int n) {
   // (7: never the fused form; 6: never the pair form; 8 / 9: the pair form where it applies, 8 / 16 positions per lane in its walk - A/B)
   if (h->tune[15] >= 6 && h->tune[15] <= 9 && one_sweep_ok) return LOOP_ONE_SWEEP;
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
-  if (one_rank && h->qplan.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)h->qplan.G) return LOOP_FUSED_SMALL;
+  if (one_rank && qp.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)qp.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;
   if (one_sweep_ok) return LOOP_ONE_SWEEP;
   return LOOP_SIX;
@@ -683,94 +710,104 @@ Loop choose_loop(lz_handle h, int n) {
 
 // ---- the plain loop: six launches per step (pass 1, second-stage sums, pass 2, SpMV, alpha sum, three-term), with the
 // opt-in partial re-orthogonalisation (Simon's omega-recurrence on the host) --------------------------------------------
-int run_loop_six(lz_handle h, int n, int* sweeps_out, int j0 = 0) {
-  const bool fused = (h->flags & LZ_FLAG_FUSED_NORM) != 0 && !(h->flags & LZ_FLAG_REORTH_PARTIAL);
+// Simon's omega-recurrence on the host (the host-decided arm, knob 18 = 1): omega_{j,k} estimates v_j . v_k, and a sweep is due when
+// an estimate exceeds sqrt(eps).  Plain arithmetic, no device call: run_loop_six asks due(j) before step j and feeds it the step's two
+// scalars, alpha_j and ||r||^2 = beta_{j+1}^2, afterwards.
+struct HostOmega {
+  static constexpr double eps = 2.220446049250313e-16, thresh = 1.4901161193847656e-08;
+  std::vector<double> w_prev, w_cur, w_new, ha, hb;  // omega_{j-2,:}, omega_{j-1,:}, omega_{j,:}; alpha_k; beta_k (norm forming V[k])
+  double normA = 0.0;
+  bool force_next = false;
+  void start(int n, double nrm2_0) {  // nrm2_0: ||r||^2 of the warm-up
+    for (auto* v : {&w_prev, &w_cur, &w_new, &ha, &hb}) v->assign((size_t)n + 1, 0.0);
+    w_cur[0] = 1.0;  // omega_{0,0} = v_0 . v_0 (until round 4 this row was all zero, which made a spurious sweep due at j = 2)
+    hb[0] = std::sqrt(nrm2_0);
+  }
+  // does step j sweep?  Advances the recurrence to row j.
+  bool due(int j) {
+    bool over = false;
+    if (j >= 1) {
+      // beta_j omega_{j,k} = beta_{k+1} omega_{j-1,k+1} + (alpha_k - alpha_{j-1}) omega_{j-1,k} + beta_k omega_{j-1,k-1}
+      //                      - beta_{j-1} omega_{j-2,k}  (+ rounding of size eps ||A||),   k <= j-2
+      std::fill(w_new.begin(), w_new.end(), 0.0);
+      w_new[(size_t)j] = 1.0;
+      w_new[(size_t)j - 1] = eps;
+      double worst = 0.0;
+      for (int k = 0; k + 2 <= j; ++k) {
+        double t = hb[(size_t)k + 1] * w_cur[(size_t)k + 1] + (ha[(size_t)k] - ha[(size_t)j - 1]) * w_cur[(size_t)k] -
+                   hb[(size_t)j - 1] * w_prev[(size_t)k];
+        if (k > 0) t += hb[(size_t)k] * w_cur[(size_t)k - 1];
+        t += (t < 0 ? -1.0 : 1.0) * 2.0 * eps * normA;
+        w_new[(size_t)k] = t / hb[(size_t)j];
+        worst = std::max(worst, std::fabs(w_new[(size_t)k]));
+      }
+      over = worst > thresh;
+      std::swap(w_prev, w_cur);
+      std::swap(w_cur, w_new);
+    }
+    const bool sweep = (j == 0) || over || force_next;  // a due sweep also covers the next vector (both feed the recurrence)
+    force_next = over;
+    if (sweep)
+      for (int k = 0; k < j; ++k) w_cur[(size_t)k] = eps;
+    return sweep;
+  }
+  void feed(int j, double alpha, double nrm2) {
+    ha[(size_t)j] = alpha;
+    hb[(size_t)j + 1] = std::sqrt(nrm2);
+    normA = std::max(normA, std::fabs(alpha) + hb[(size_t)j] + hb[(size_t)j + 1]);
+  }
+};
+
+// the host-decided arm's read-back: alpha[j] (j >= 0) and ||r||^2 into the pinned pair, one synchronisation
+static int read_back_step(lz_handle h, int j) {
+  if (!h->h_pinned) LZ_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned), 8 * sizeof(double), hipHostMallocDefault));
+  if (j >= 0) LZ_HIP(h, hipMemcpyAsync(&h->h_pinned[0], h->d_alpha + j, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(&h->h_pinned[1], h->d_nrm2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  h->host_syncs += 1;
+  return LZ_OK;
+}
+
+int run_loop_six(lz_handle h, int n, int j0 = 0) {
+  const bool partial = (h->flags & LZ_FLAG_REORTH_PARTIAL) != 0;
+  const bool fused = (h->flags & LZ_FLAG_FUSED_NORM) != 0 && !partial;
   if (j0 == 0) {
-    // warm-up (Lanczos.py:108-110): r = A v0; alpha0 = r.v0; r = r - alpha0 v0
-    LZ_TRY(step_spmv(h, 0));
-    LZ_TRY(step_three_term(h, 0, -1, h->d_alpha, nullptr, !fused));
+    LZ_TRY(warm_up(h, !fused));
   } else if (!fused) {
     // resumed run (lz_run_resume): steps 0 .. j0-1 are in the basis, r is the residual entering step j0; the scale-then-dot order
     // wants ||r||^2 in d_nrm2: r = r - 0 * V[0] leaves r unchanged bit for bit and refreshes it
     LZ_HIP(h, hipMemsetAsync(h->d_c + n, 0, sizeof(double), h->stream));
     LZ_TRY(step_three_term(h, 0, -1, h->d_c + n, nullptr, true));
   }
-  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-  const bool partial = (h->flags & LZ_FLAG_REORTH_PARTIAL) != 0;
-  // Partial re-orthogonalisation (opt-in): Simon's omega-recurrence on the host, fed with alpha_j and beta_{j+1}
-  // (two doubles copied back per step).  omega_{j,k} estimates v_j . v_k; a sweep is due when it exceeds sqrt(eps).
-  const double eps = 2.220446049250313e-16, thresh = 1.4901161193847656e-08;
-  std::vector<double> w_prev, w_cur, w_new, ha, hb;  // omega_{j-2,:}, omega_{j-1,:}, omega_{j,:}; alpha_k; beta_k (norm forming V[k])
+  // Partial re-orthogonalisation (opt-in, never resumed): the sweep decision is the host's, two doubles are copied back per step
+  HostOmega omega;
   if (partial) {
-    if (!h->h_pinned) LZ_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned), 8 * sizeof(double), hipHostMallocDefault));
-    w_prev.assign((size_t)n + 1, 0.0);
-    w_cur.assign((size_t)n + 1, 0.0);
-    w_cur[0] = 1.0;  // omega_{0,0} = v_0 . v_0 (until round 4 this row was all zero, which made a spurious sweep due at j = 2)
-    w_new.assign((size_t)n + 1, 0.0);
-    ha.assign((size_t)n + 1, 0.0);
-    hb.assign((size_t)n + 1, 0.0);
-    double nrm2 = 0.0;
-    LZ_HIP(h, hipMemcpyAsync(&nrm2, h->d_nrm2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    LZ_HIP(h, hipStreamSynchronize(h->stream));
-    h->host_syncs += 1;
-    hb[0] = std::sqrt(nrm2);
+    LZ_TRY(read_back_step(h, -1));
+    omega.start(n, h->h_pinned[1]);
   }
-  bool force_next = false;
-  double normA = 0.0;
   int sweeps = 0;
   for (int j = j0; j < n; ++j) {
-    h->prof_iter = (j % pstride) == pstride / 2;  // centred sample: same mean j as the full run
-    const int bidx = (j + n - 2) % (n - 1);  // beta[j-1] with Python's negative index at j = 0
-    bool sweep = true;
-    if (partial) {
-      bool due = false;
-      if (j >= 1) {
-        // beta_j omega_{j,k} = beta_{k+1} omega_{j-1,k+1} + (alpha_k - alpha_{j-1}) omega_{j-1,k} + beta_k omega_{j-1,k-1}
-        //                      - beta_{j-1} omega_{j-2,k}  (+ rounding of size eps ||A||),   k <= j-2
-        std::fill(w_new.begin(), w_new.end(), 0.0);
-        w_new[(size_t)j] = 1.0;
-        w_new[(size_t)j - 1] = eps;
-        double worst = 0.0;
-        for (int k = 0; k + 2 <= j; ++k) {
-          double t = hb[(size_t)k + 1] * w_cur[(size_t)k + 1] + (ha[(size_t)k] - ha[(size_t)j - 1]) * w_cur[(size_t)k] -
-                     hb[(size_t)j - 1] * w_prev[(size_t)k];
-          if (k > 0) t += hb[(size_t)k] * w_cur[(size_t)k - 1];
-          t += (t < 0 ? -1.0 : 1.0) * 2.0 * eps * normA;
-          w_new[(size_t)k] = t / hb[(size_t)j];
-          worst = std::max(worst, std::fabs(w_new[(size_t)k]));
-        }
-        due = worst > thresh;
-        std::swap(w_prev, w_cur);
-        std::swap(w_cur, w_new);
-      }
-      sweep = (j == 0) || due || force_next;  // a due sweep also covers the next vector (both feed the recurrence)
-      force_next = due;
-      if (sweep)
-        for (int k = 0; k < j; ++k) w_cur[(size_t)k] = eps;
-    }
-    if (sweep) {
+    begin_iter(h, j);
+    const int bidx = beta_index(n, j);
+    double* bslot = h->d_beta + bidx;
+    if (!partial || omega.due(j)) {
       ++sweeps;
       LZ_TRY(step_reorth(h, j, j + 1, true, bidx, true));
     } else {
       Scope sc(h, LZ_K_QTW, 16.0 * (double)h->rows, (double)h->rows);
-      launch_scale_store(h->d_V + (int64_t)j * h->ldv, h->d_r, h->d_nrm2, h->d_beta + bidx, h->rows_pad, h->stream);
+      launch_scale_store(basis_row(h, j), h->d_r, h->d_nrm2, bslot, h->rows_pad, h->stream);
       LZ_TRY(check_launch(h, "scale_store"));
     }
     LZ_TRY(step_spmv(h, j));
     // at j = 0 the reference subtracts beta * V[-1], the still-zero last row: a no-op
-    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, !fused || partial));
+    LZ_TRY(step_three_term(h, j, j > 0 ? j - 1 : -1, h->d_alpha + j, bslot, !fused));
     if (partial) {
-      double* two = h->h_pinned;
-      LZ_HIP(h, hipMemcpyAsync(&two[0], h->d_alpha + j, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      LZ_HIP(h, hipMemcpyAsync(&two[1], h->d_nrm2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      LZ_HIP(h, hipStreamSynchronize(h->stream));
-      h->host_syncs += 1;
-      ha[(size_t)j] = two[0];
-      hb[(size_t)j + 1] = std::sqrt(two[1]);
-      normA = std::max(normA, std::fabs(two[0]) + hb[(size_t)j] + hb[(size_t)j + 1]);
+      LZ_TRY(read_back_step(h, j));
+      omega.feed(j, h->h_pinned[0], h->h_pinned[1]);
     }
   }
-  *sweeps_out = sweeps;
+  h->last_sweeps = sweeps;
+  h->r_state = 1;
   return LZ_OK;
 }
 
@@ -825,12 +862,7 @@ int run_loop_partial_device(lz_handle h, int n, int j0 = 0, const double* state_
   if (j0 == 0) LZ_TRY(step_spmv(h, 0));
   int np = 0;
   auto three_term_and_decide = [&](int j, int jm1, const double* d_alpha, const double* d_beta, double* r, bool decide, int jn) -> int {
-    {
-      Scope sc(h, LZ_K_THREE, (jm1 >= 0 ? 32.0 : 24.0) * M, (jm1 >= 0 ? 6.0 : 4.0) * M);
-      np = launch_three_term(r, h->d_V + (int64_t)j * h->ldv, jm1 >= 0 ? h->d_V + (int64_t)jm1 * h->ldv : nullptr, d_alpha, d_beta, h->rows_pad,
-                             h->d_part, h->stream);
-      LZ_TRY(check_launch(h, "three_term"));
-    }
+    LZ_TRY(step_three_term(h, j, jm1, d_alpha, d_beta, false, &np, r));
     Scope sc(h, LZ_K_FINAL, 0, 0);
     if (one_rank && decide) {
       launch_omega(h->d_part, np, h->d_nrm2, h->d_alpha, jn, n, h->d_om, h->d_omi, h->stream);
@@ -845,21 +877,15 @@ int run_loop_partial_device(lz_handle h, int n, int j0 = 0, const double* state_
     }
     return LZ_OK;
   };
-  if (j0 == 0) {
-    LZ_TRY(three_term_and_decide(0, -1, h->d_alpha, nullptr, h->d_r, true, 0));
-  } else {
-    // resumed: r = r - 0 * V[0] leaves r unchanged bit for bit, refreshes ||r||^2 with the very kernel (and summation) that produced it
-    // in the uninterrupted run, and k_omega takes the decision of step j0 from it
-    LZ_HIP(h, hipMemsetAsync(h->d_c + n, 0, sizeof(double), h->stream));
-    LZ_TRY(three_term_and_decide(0, -1, h->d_c + n, nullptr, h->d_r, true, j0));
-  }
-  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
+  // the warm-up's r = r - alpha0 v0; resumed: r = r - 0 * V[0] leaves r unchanged bit for bit, refreshes ||r||^2 with the very kernel
+  // (and summation) that produced it in the uninterrupted run, and k_omega takes the decision of step j0 from it
+  if (j0 > 0) LZ_HIP(h, hipMemsetAsync(h->d_c + n, 0, sizeof(double), h->stream));
+  LZ_TRY(three_term_and_decide(0, -1, j0 > 0 ? h->d_c + n : h->d_alpha, nullptr, h->d_r, true, j0));
   double* rcur = h->d_r;   // the residual entering the step
   double* rnext = h->d_r2; // where the fused SpMV writes y (it reads r through its gathers: not in place)
   for (int j = j0; j < n; ++j) {
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
-    double* vj = h->d_V + (int64_t)j * h->ldv;
+    begin_iter(h, j);
+    double* bslot = beta_slot(h, n, j);
     // the sweep (gated; bytes are accounted after the run from the device's sweep log: the host does not know which ran)
     {
       QtwFuse fz;
@@ -874,7 +900,7 @@ int run_loop_partial_device(lz_handle h, int n, int j0 = 0, const double* state_
       h->qplan.variant = 0;
       {
         Scope sc(h, LZ_K_QTW, 0, 0);
-        LZ_HIP(h, launch_qtw(h->d_V, h->ldv, h->rows_pad, j + 1, j, rcur, h->d_nrm2, h->d_beta + bidx, h->qplan, h->d_part, 1, h->stream, &fz));
+        LZ_HIP(h, launch_qtw(h->d_V, h->ldv, h->rows_pad, j + 1, j, rcur, h->d_nrm2, bslot, h->qplan, h->d_part, 1, h->stream, &fz));
         LZ_TRY(check_launch(h, "qtw(gated)"));
       }
       if (!fold) {
@@ -885,44 +911,28 @@ int run_loop_partial_device(lz_handle h, int n, int j0 = 0, const double* state_
       LZ_TRY(comm_allreduce(h, h->d_c, j + 1));  // (N > 1: issued every step - the host cannot skip a collective the device may need)
       {
         Scope sc(h, LZ_K_UPDATE, 0, 0);
-        launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, nullptr, h->d_beta + bidx, 0, h->stream, 0, -1, 0, 0, 0, 0, 0, gate);
+        launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, h->d_c, nullptr, bslot, 0, h->stream, 0, -1, 0, 0, 0, 0, 0, gate);
         LZ_TRY(check_launch(h, "update(gated)"));
       }
     }
     if (fuse_scale) {
-      SpmvScale ss;
-      ss.r = rcur;
-      ss.nrm2 = h->d_nrm2;
-      ss.vj = vj;
-      ss.beta_slot = h->d_beta + bidx;
-      ss.gate = gate;
       int npa = 0;
-      {
-        // (the scale pass's 16M bytes ride here: BASELINE.md's accounting of the step is unchanged.  With a row-class coded matrix the
-        // launch moves 25 bytes per row - r once, y, V[j], the class byte - so only V[j]'s 8 are added: counting r twice would be a
-        // third of the total there)
-        Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true) + (h->csr.ell_coded ? 8.0 : 16.0) * M, spmv_flops(h) + M);
-        npa = launch_spmv_ell(h->csr, vj, rnext, vj, h->d_part, h->stream, &ss);
-        LZ_TRY(check_launch(h, "spmv(ell, scale fused)"));
-      }
-      {
-        Scope sc(h, LZ_K_FINAL, 0, 0);
-        launch_final_sum(h->d_part, npa, h->d_alpha + j, h->stream);
-        LZ_TRY(check_launch(h, "final_sum(alpha)"));
-      }
+      LZ_TRY(step_scaling_spmv(h, n, j, rcur, rnext, gate, &npa));  // V[j] = r / beta on read unless the step swept
+      LZ_TRY(step_final_sum(h, npa, h->d_alpha + j, "final_sum(alpha)"));
       std::swap(rcur, rnext);
     } else {
       {
         Scope sc(h, LZ_K_QTW, 16.0 * M, M);
-        launch_scale_store(vj, rcur, h->d_nrm2, h->d_beta + bidx, h->rows_pad, h->stream, gate);
+        launch_scale_store(basis_row(h, j), rcur, h->d_nrm2, bslot, h->rows_pad, h->stream, gate);
         LZ_TRY(check_launch(h, "scale_store(gated)"));
       }
       LZ_TRY(step_spmv(h, j));  // r = A V[j] into h->d_r (== rcur), alpha_j
     }
     // at j = 0 the reference subtracts beta * V[-1], the still-zero last row: a no-op
-    LZ_TRY(three_term_and_decide(j, j > 0 ? j - 1 : -1, h->d_alpha + j, h->d_beta + bidx, rcur, j + 1 < n, j + 1));
+    LZ_TRY(three_term_and_decide(j, j > 0 ? j - 1 : -1, h->d_alpha + j, bslot, rcur, j + 1 < n, j + 1));
   }
   if (rcur != h->d_r) std::swap(h->d_r, h->d_r2);  // the residual entering step n is what lz_get_residual hands out
+  h->r_state = 1;
   return LZ_OK;
 }
 
@@ -958,36 +968,20 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
   LZ_HIP(h, hipMemsetAsync(ticket, 0, sizeof(unsigned), h->stream));
   const bool lean = h->tune[18] != 3;  // (knob 18 = 3: every folded stage as a kernel of its own - the first form of this loop, kept as the A/B arm)
   LZ_TRY(step_spmv(h, 0, h->d_c + onered_slot(0), false));  // warm-up: r'' = A v0 (Lanczos.py:108), alpha0 partial
-  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
-  const size_t self_off = onered_part_off(h);  // the self terms' partials live behind the SpMV's alpha partials in d_part
+  // the self terms' partials (and the lean form's pass 1) live behind the SpMV's alpha partials in d_part
+  double* spart = h->d_part + (lean ? onered_part_off(h) : 0);
   for (int j = 0; j < n; ++j) {
-    h->prof_iter = (j % pstride) == pstride / 2;
-    const int bidx = (j + n - 2) % (n - 1);
+    begin_iter(h, j);
+    double* bslot = beta_slot(h, n, j);
     const int m = j, urow = j > 0 ? j - 1 : 0, ldp = onered_ldp(m);
     const bool last = j == n - 1;
     double* buf = h->d_c + (size_t)(j & 1) * bstride;
     double* bufn = h->d_c + (size_t)((j + 1) & 1) * bstride;
     const int* gate = h->d_omi + (j & 1);
-    double* u = h->d_V + (int64_t)urow * h->ldv;
-    double* vj = h->d_V + (int64_t)j * h->ldv;
-    h->qplan.variant = 0;
-    {
-      QtwFuse fz;
-      fz.gate = gate;
-      if (lean) {  // pass 1's last block adds the blocks' runs itself (k_final_rows_t's order)
-        fz.ticket = ticket;
-        fz.c_out = buf;
-      }
-      Scope sc(h, LZ_K_QTW, 0, 0);  // (bytes of the launches that really ran: accounted after the run from the device's sweep log)
-      LZ_HIP(h, launch_qtw(h->d_V, h->ldv, h->rows_pad, m, urow, h->d_r, nullptr, nullptr, h->qplan, h->d_part + (lean ? self_off : 0), 3, h->stream, &fz));
-      LZ_TRY(check_launch(h, "qtw(two columns, gated)"));
-    }
-    if (!lean) {
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_final_rows_t(h->d_part, h->qplan.G, 2 * ldp, ldp + m + 2, buf, h->stream, gate);
-      LZ_TRY(check_launch(h, "final_rows(gated)"));
-    }
-    LZ_TRY(comm_allreduce(h, buf, onered_slot(m) + 1));  // THE collective of this iteration
+    double* u = basis_row(h, urow);
+    double* vj = basis_row(h, j);
+    // (lean: pass 1's last block adds the blocks' runs itself, in k_final_rows_t's order)
+    LZ_TRY(step_onereduce_head(h, j, urow, spart, buf, gate, lean ? ticket : nullptr));
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
       launch_partial_onered_post(buf, last ? nullptr : bufn, last ? 0 : onered_slot(j + 1) + 1, m, ldp, h->d_alpha + urow, h->d_nrm2, h->d_alpha, j, n,
@@ -997,22 +991,18 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
     if (lean) {
       // ONE launch forms w = (r'' - alpha u) / beta and either sweeps (V[j] = 2 w - sum c_i V_i) or stores V[j] = w
       Scope sc(h, LZ_K_UPDATE, 32.0 * M, 4.0 * M);  // (a sweep's basis rows: accounted after the run)
-      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, buf, h->d_r, h->d_beta + bidx, 0, h->stream, 0, -1, 1, 0, 0, 0, 0, gate, u, h->d_alpha + urow);
+      launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, buf, h->d_r, bslot, 0, h->stream, 0, -1, 1, 0, 0, 0, 0, gate, u, h->d_alpha + urow);
       LZ_TRY(check_launch(h, "update | scale (gated)"));
     } else {
-      {
-        Scope sc(h, LZ_K_THREE, 24.0 * M, 2.0 * M);
-        launch_three_term(h->d_r, u, nullptr, h->d_alpha + urow, nullptr, h->rows_pad, h->d_part, h->stream);  // r = r'' - alpha u
-        LZ_TRY(check_launch(h, "three_term(alpha)"));
-      }
+      LZ_TRY(step_two_term(h, u, h->d_alpha + urow, "three_term(alpha)"));  // r = r'' - alpha u
       {
         Scope sc(h, LZ_K_UPDATE, 0, 0);
-        launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, buf, h->d_r, h->d_beta + bidx, 0, h->stream, 0, -1, 1, 0, 0, 0, 0, gate);
+        launch_update(h->d_V, h->ldv, h->rows_pad, j + 1, j, buf, h->d_r, bslot, 0, h->stream, 0, -1, 1, 0, 0, 0, 0, gate);
         LZ_TRY(check_launch(h, "update(gated)"));
       }
       {
         Scope sc(h, LZ_K_QTW, 16.0 * M, M);
-        launch_scale_store(vj, h->d_r, h->d_nrm2, h->d_beta + bidx, h->rows_pad, h->stream, gate);
+        launch_scale_store(vj, h->d_r, h->d_nrm2, bslot, h->rows_pad, h->stream, gate);
         LZ_TRY(check_launch(h, "scale_store(gated)"));
       }
     }
@@ -1028,10 +1018,9 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
       LZ_TRY(step_spmv(h, j, nullptr, false, &npa));
     else
       LZ_TRY(step_spmv(h, j, bufn + onered_slot(mn), false));
-    double* spart = h->d_part + (lean ? self_off : 0);
     {
       Scope sc(h, LZ_K_THREE, (j > 0 ? 40.0 : 16.0) * M, (j > 0 ? 8.0 : 6.0) * M);
-      G3 = launch_three_term_self(h->d_r, vj, j > 0 ? h->d_V + (int64_t)(j - 1) * h->ldv : nullptr, h->d_beta + bidx, h->rows_pad, spart, h->stream);
+      G3 = launch_three_term_self(h->d_r, vj, j > 0 ? basis_row(h, j - 1) : nullptr, bslot, h->rows_pad, spart, h->stream);
       LZ_TRY(check_launch(h, "three_term(beta) + self terms"));
     }
     FinalMulti fm;
@@ -1050,18 +1039,19 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
   return LZ_OK;
 }
 
-// after the final synchronisation of lz_run: the device's sweep log -> lz_last_sweeps and the byte / flop accounting of the
-// gated launches (pass 1: 8 j M + 16 M bytes, pass 2 the same; in a swept step the scale kernel / fused scale did no work)
-void account_partial_device(lz_handle h, int n, const std::vector<int>& log, int* sweeps_out, size_t log0 = 2) {
+// after the final synchronisation of a device-decided partial run: the device's sweep log (its per-step words start at log0) ->
+// lz_last_sweeps, lz_last_sweep_log and the byte / flop accounting of the gated launches (pass 1: 8 j M + 16 M bytes, pass 2 the same;
+// in a swept step the scale kernel / fused scale did no work).  A resumed run's log holds zeros for the steps of the first leg.
+void account_partial_device(lz_handle h, int n, const std::vector<int>& log, size_t log0) {
   const double M = (double)h->rows;
-  const int pstride = h->tune[7] > 1 ? h->tune[7] : 1;
   int sweeps = 0;
   for (int j = 0; j < n; ++j) {
+    h->sweep_log[(size_t)j] = log[log0 + j] != 0;
     if (!log[log0 + j]) continue;
     ++sweeps;
     // (pass 1's read of r and write of V[j], 16 M bytes, are on the books already: the scale pass is accounted in every step)
     const double flops = 2.0 * (j + 1) * M;
-    const bool timed = (h->flags & LZ_FLAG_PROFILE) != 0 && (j % pstride) == pstride / 2;
+    const bool timed = (h->flags & LZ_FLAG_PROFILE) != 0 && iter_sampled(h, j);
     for (int cls : {LZ_K_QTW, LZ_K_UPDATE}) {
       const double bytes = 8.0 * j * M + (cls == LZ_K_UPDATE ? 16.0 * M : 0.0);
       h->acc.bytes[cls] += bytes;
@@ -1069,7 +1059,7 @@ void account_partial_device(lz_handle h, int n, const std::vector<int>& log, int
       if (timed) h->acc.timed_bytes[cls] += bytes;
     }
   }
-  *sweeps_out = sweeps;
+  h->last_sweeps = sweeps;
 }
 
 // Breakdown report.  The reference divides by beta blindly (Lanczos.py:113): an exhausted Krylov
@@ -1099,6 +1089,146 @@ int breakdown_status(lz_handle h, int n, const double* alpha_out, const double* 
     }
   }
   return LZ_OK;
+}
+
+// ---- the run frame: what lz_run, lz_run_resume and lz_run_resume_partial do around their loop: begin -> the caller's upload ->
+// uploaded -> the loop -> drain -> (the caller looks at its extra words) -> finish -----------------------------------------------
+struct RunExtra {  // device words an entry point wants on the host behind alpha / beta, ahead of the one synchronisation
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+struct RunFrame {
+  lz_handle h;
+  int n;
+  double t0 = 0, t1 = 0, t2 = 0, t3 = 0;  // host clock, ms: entry, basis ready, upload enqueued, loop enqueued (LZ_DEBUG_TIMING)
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+  // the basis for n steps, its first zero_rows rows cleared, and the handle's per-run record as a run that has not started leaves it:
+  // every step swept, no residual.  The loops overwrite what they know better, each at its own end.
+  int begin(int zero_rows) {
+    t0 = now();
+    h->run_timed = false;  // (a pass that was abandoned after its drain books no time)
+    LZ_TRY(basis_alloc(h, n, zero_rows));
+    h->halo_inflight_j = -1;
+    h->y_n = 0;  // the Ritz vectors of an earlier run are not this run's: fetches answer LZ_ERR_STATE until lz_ritz_vectors is called again
+    h->last_engine = LOOP_SIX;
+    h->last_sweeps = n;
+    h->last_misses = 0;
+    h->last_gate_trips = 0;
+    h->last_os_fused = 0;
+    h->last_os_pairs = 0;
+    h->last_pair_abandoned = 0;
+    h->sweep_log.assign((size_t)n, 1);  // which steps ran the sweep (lz_last_sweep_log): all of them unless a partial loop says otherwise
+    h->host_syncs = 0;
+    h->r_state = 0;
+    t1 = now();
+    return LZ_OK;
+  }
+  int uploaded() {
+    t2 = now();
+    LZ_HIP(h, hipEventRecord(h->run_a, h->stream));
+    return LZ_OK;
+  }
+  // behind the loop: alpha, beta and the extras to the host, THE synchronisation of the run
+  int drain(double* alpha_out, double* beta_out, const std::vector<RunExtra>& extras = {}) {
+    h->prof_iter = true;
+    LZ_HIP(h, hipEventRecord(h->run_b, h->stream));
+    t3 = now();
+    h->run_timed = true;  // (an error from here on: drain_events books the run's time)
+    LZ_HIP(h, hipMemcpyAsync(alpha_out, h->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LZ_HIP(h, hipMemcpyAsync(beta_out, h->d_beta, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    for (const RunExtra& e : extras) LZ_HIP(h, hipMemcpyAsync(e.dst, e.src, e.bytes, hipMemcpyDeviceToHost, h->stream));
+    LZ_HIP(h, hipStreamSynchronize(h->stream));
+    return LZ_OK;
+  }
+  // the run's time on the books, the breakdown report as the status
+  int finish(const double* alpha_out, const double* beta_out) {
+    float ms = 0.f;
+    LZ_HIP(h, hipEventElapsedTime(&ms, h->run_a, h->run_b));
+    h->acc.total_ms += ms;
+    h->run_timed = false;
+    return breakdown_status(h, n, alpha_out, beta_out);
+  }
+};
+
+// a checkpoint of j0 completed steps: the basis rows, the residual entering step j0, alpha[0 .. j0), beta[0 .. j0 - 1)
+static int upload_checkpoint(lz_handle h, int j0, const double* V_rows, int64_t ldv_in, const double* r_local, const double* alpha_in,
+                             const double* beta_in) {
+  LZ_TRY(upload2d(h, h->d_V, (size_t)h->ldv * sizeof(double), V_rows, (size_t)ldv_in * sizeof(double), (size_t)h->rows * sizeof(double), (size_t)j0));
+  LZ_TRY(upload(h, h->d_r, r_local, (size_t)h->rows * sizeof(double)));
+  LZ_HIP(h, hipMemcpyAsync(h->d_alpha, alpha_in, (size_t)j0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (j0 > 1) LZ_HIP(h, hipMemcpyAsync(h->d_beta, beta_in, (size_t)(j0 - 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return LZ_OK;
+}
+
+// One pass of lz_run.  *again: the pass's own check says its coefficients do not hold; what makes the next pass take another loop is set
+// (LZ_FLAG_ONE_REDUCE cleared, or h->pair_tripped), nothing is on the books, and lz_run makes that pass.
+static int run_once(lz_handle h, int n, const double* v0_local, double* alpha_out, double* beta_out, bool* again) {
+  *again = false;
+  RunFrame fr{h, n};
+  LZ_TRY(fr.begin(1));
+  LZ_TRY(upload(h, h->d_V, v0_local, (size_t)h->rows * sizeof(double)));
+  LZ_TRY(fr.uploaded());
+  const Loop loop = choose_loop(h, n);
+  const bool one_reduce = loop == LOOP_ONE_REDUCE || loop == LOOP_PARTIAL_ONE_REDUCE;
+  bool tried_pairs = false;
+  h->last_engine = (int)loop;
+  switch (loop) {
+#ifdef LZ_KBENCH
+    case LOOP_SMALL_ENGINE:
+    case LOOP_SMALL_STEP: {
+      bool ran = false;
+      LZ_TRY(run_small_engine(h, n, v0_local, loop == LOOP_SMALL_STEP, &ran));
+      if (!ran) {  // the engine refused (placement / barrier timeout): nothing is lost, the plain loop repeats the run
+        h->last_engine = LOOP_SIX;
+        LZ_TRY(run_loop_six(h, n));
+      }
+      break;
+    }
+#endif
+    case LOOP_FUSED_SMALL: LZ_TRY(run_loop_fused_small(h, n)); break;
+    case LOOP_THREE_TERM_FUSED: LZ_TRY(run_loop_three_term_fused(h, n)); break;
+    case LOOP_ONE_REDUCE: LZ_TRY(run_loop_onereduce(h, n)); break;
+    case LOOP_PARTIAL_DEVICE: LZ_TRY(run_loop_partial_device(h, n)); break;
+    case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
+    case LOOP_ONE_SWEEP:
+      tried_pairs = one_sweep_pair_applies(h, n);
+      LZ_TRY(tried_pairs ? run_loop_one_sweep_pair(h, n) : one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n));
+      break;
+    default: LZ_TRY(run_loop_six(h, n)); break;
+  }
+  double onered_bad = 0.0;
+  int pair_flag = 0;
+  std::vector<int> dev_log(loop == LOOP_PARTIAL_DEVICE ? omega_state_ints(n) : loop == LOOP_PARTIAL_ONE_REDUCE ? omega_onered_ints(n) : 0);
+  std::vector<RunExtra> extras;
+  if (one_reduce) extras.push_back({&onered_bad, h->d_nrm2 + 1, sizeof(double)});
+  if (loop == LOOP_ONE_SWEEP) extras.push_back({&h->last_gate_trips, h->d_osi + 1, sizeof(int)});
+  if (tried_pairs) extras.push_back({&pair_flag, h->d_osi + 3, sizeof(int)});
+  if (!dev_log.empty()) extras.push_back({dev_log.data(), h->d_omi, dev_log.size() * sizeof(int)});
+  LZ_TRY(fr.drain(alpha_out, beta_out, extras));
+  if (loop == LOOP_SIX && (h->flags & LZ_FLAG_REORTH_PARTIAL)) h->sweep_log.clear();  // (the host-decided loop keeps no per-step record)
+  if (!dev_log.empty()) account_partial_device(h, n, dev_log, loop == LOOP_PARTIAL_DEVICE ? 2 : 4);
+  if (loop == LOOP_PARTIAL_ONE_REDUCE) h->last_misses = dev_log[3];
+  if (one_reduce && onered_bad != 0.0) {
+    // cancellation guard of the one-reduce loop (k_onereduce_prepare): |r|^2 = r''.r'' - 2 alpha u.r'' + alpha^2 u.u lost too
+    // many digits at some step (|alpha| >> beta).  Every rank sees the same reduced sums, so every rank takes this branch:
+    // the solve is repeated on the default loop (two all-reduces per iteration), whose coefficients hold the bar.
+    h->flags &= ~LZ_FLAG_ONE_REDUCE;
+    *again = true;
+    return LZ_OK;
+  }
+  if (pair_flag) {
+    // a pair's prediction missed by more than kOneSweepTau (k_os_pair_post): a pair has no correcting sweep, so the whole solve is
+    // repeated on the single fused form, whose gate corrects such steps; remembered until the matrix is set again
+    h->pair_tripped = true;
+    *again = true;
+    return LZ_OK;
+  }
+  if (getenv("LZ_DEBUG_TIMING"))
+    fprintf(stderr, "[lz_run] alloc+memset %.3f ms, v0 upload %.3f ms, enqueue loop %.3f ms, drain+D2H %.3f ms\n", fr.t1 - fr.t0, fr.t2 - fr.t1,
+            fr.t3 - fr.t2, RunFrame::now() - fr.t3);
+  return fr.finish(alpha_out, beta_out);
 }
 
 }  // namespace api
@@ -1159,113 +1289,16 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   if (!v0_local || !alpha_out || !beta_out) return fail(h, LZ_ERR_ARG, "lz_run: NULL buffer");
   if (n < 2) return fail(h, LZ_ERR_ARG, "lz_run: n must be >= 2 (the reference's beta array has n-1 entries)");
   if (n > h->Mg) return fail(h, LZ_ERR_ARG, "lz_run: n cannot be larger than M");
-  const bool dbg = getenv("LZ_DEBUG_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  LZ_TRY(basis_alloc(h, n, 1));
-  h->halo_inflight_j = -1;
-  h->y_n = 0;  // the Ritz vectors of an earlier run are not this run's: fetches answer LZ_ERR_STATE until lz_ritz_vectors is called again
-  const double t1 = now();
-  LZ_TRY(upload(h, h->d_V, v0_local, (size_t)h->rows * sizeof(double)));
-  const double t2 = now();
-  LZ_HIP(h, hipEventRecord(h->run_a, h->stream));
-  h->host_syncs = 0;
-  const Loop loop = choose_loop(h, n);
-  const bool one_reduce = loop == LOOP_ONE_REDUCE || loop == LOOP_PARTIAL_ONE_REDUCE;
-  int sweeps = n;
-  bool tried_pairs = false;
-  h->last_engine = (int)loop;
-  h->last_os_pairs = 0;
-  h->last_pair_abandoned = 0;
-  switch (loop) {
-#ifdef LZ_KBENCH
-    case LOOP_SMALL_ENGINE:
-    case LOOP_SMALL_STEP: {
-      bool ran = false;
-      LZ_TRY(run_small_engine(h, n, v0_local, loop == LOOP_SMALL_STEP, &ran));
-      if (!ran) {  // the engine refused (placement / barrier timeout): nothing is lost, the plain loop repeats the run
-        h->last_engine = LOOP_SIX;
-        LZ_TRY(run_loop_six(h, n, &sweeps));
-      }
-      break;
-    }
-#endif
-    case LOOP_FUSED_SMALL: LZ_TRY(run_loop_fused_small(h, n)); break;
-    case LOOP_THREE_TERM_FUSED: LZ_TRY(run_loop_three_term_fused(h, n)); break;
-    case LOOP_ONE_REDUCE: LZ_TRY(run_loop_onereduce(h, n)); break;
-    case LOOP_PARTIAL_DEVICE: LZ_TRY(run_loop_partial_device(h, n)); break;
-    case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
-    case LOOP_ONE_SWEEP:
-      tried_pairs = one_sweep_pair_applies(h, n);
-      LZ_TRY(tried_pairs ? run_loop_one_sweep_pair(h, n) : one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n));
-      break;
-    default: LZ_TRY(run_loop_six(h, n, &sweeps)); break;
-  }
-  h->last_sweeps = sweeps;
-  h->r_state = (h->last_engine == LOOP_SIX || h->last_engine == LOOP_PARTIAL_DEVICE || h->last_engine == LOOP_ONE_SWEEP) ? 1
-               : (h->last_engine == LOOP_FUSED_SMALL || h->last_engine == LOOP_THREE_TERM_FUSED) ? 2 : 0;
-  h->prof_iter = true;
-  LZ_HIP(h, hipEventRecord(h->run_b, h->stream));
-  const double t3 = now();
-  h->run_timed = true;
-  LZ_HIP(h, hipMemcpyAsync(alpha_out, h->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(beta_out, h->d_beta, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  double onered_bad = 0.0;
-  if (one_reduce) LZ_HIP(h, hipMemcpyAsync(&onered_bad, h->d_nrm2 + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  int gate_trips = 0;
-  int pair_flag = 0;
-  if (loop == LOOP_ONE_SWEEP) LZ_HIP(h, hipMemcpyAsync(&gate_trips, h->d_osi + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (tried_pairs) LZ_HIP(h, hipMemcpyAsync(&pair_flag, h->d_osi + 3, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  std::vector<int> sweep_log;
-  if (loop == LOOP_PARTIAL_DEVICE || loop == LOOP_PARTIAL_ONE_REDUCE) {
-    sweep_log.resize(loop == LOOP_PARTIAL_DEVICE ? omega_state_ints(n) : omega_onered_ints(n));
-    LZ_HIP(h, hipMemcpyAsync(sweep_log.data(), h->d_omi, sweep_log.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  }
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->last_misses = 0;
-  h->last_gate_trips = gate_trips;
-  h->sweep_log.assign((size_t)n, 1);  // which steps ran the sweep (lz_last_sweep_log): all of them unless a partial loop says otherwise
-  if (loop == LOOP_SIX && (h->flags & LZ_FLAG_REORTH_PARTIAL)) h->sweep_log.clear();  // (the host-decided loop keeps no per-step record)
-  if (loop == LOOP_PARTIAL_DEVICE) {
-    account_partial_device(h, n, sweep_log, &h->last_sweeps);
-    for (int j = 0; j < n; ++j) h->sweep_log[(size_t)j] = sweep_log[(size_t)2 + j] != 0;
-  }
-  if (loop == LOOP_PARTIAL_ONE_REDUCE) {
-    account_partial_device(h, n, sweep_log, &h->last_sweeps, 4);
-    h->last_misses = sweep_log[3];
-    for (int j = 0; j < n; ++j) h->sweep_log[(size_t)j] = sweep_log[(size_t)4 + j] != 0;
-  }
-  if (one_reduce && onered_bad != 0.0) {
-    // cancellation guard of the one-reduce loop (k_onereduce_prepare): |r|^2 = r''.r'' - 2 alpha u.r'' + alpha^2 u.u lost too
-    // many digits at some step (|alpha| >> beta).  Every rank sees the same reduced sums, so every rank takes this branch:
-    // the solve is repeated on the default loop (two all-reduces per iteration), whose coefficients hold the bar.
-    h->run_timed = false;
-    const int keep = h->flags;
-    h->flags &= ~LZ_FLAG_ONE_REDUCE;
-    const int rc = lz_run(h, n, v0_local, alpha_out, beta_out);
-    h->flags = keep;
-    h->last_engine = LOOP_ONE_REDUCE_REPEATED;
-    return rc;
-  }
-  if (pair_flag) {
-    // a pair's prediction missed by more than kOneSweepTau (k_os_pair_post): a pair has no correcting sweep, so the whole solve is
-    // repeated on the single fused form, whose gate corrects such steps; remembered until the matrix is set again
-    h->run_timed = false;
-    h->pair_tripped = true;
-    const int rc = lz_run(h, n, v0_local, alpha_out, beta_out);
-    h->last_pair_abandoned = 1;
-    return rc;
-  }
-  if (dbg)
-    fprintf(stderr, "[lz_run] alloc+memset %.3f ms, v0 upload %.3f ms, enqueue loop %.3f ms, drain+D2H %.3f ms\n", t1 - t0, t2 - t1,
-            t3 - t2, now() - t3);
-  {
-    float ms = 0.f;
-    LZ_HIP(h, hipEventElapsedTime(&ms, h->run_a, h->run_b));
-    h->acc.total_ms += ms;
-    h->run_timed = false;
-  }
-  return breakdown_status(h, n, alpha_out, beta_out);
+  const int keep = h->flags;
+  const bool tripped = h->pair_tripped;
+  bool again = false;
+  int rc;
+  do rc = run_once(h, n, v0_local, alpha_out, beta_out, &again);  // a second pass where the first one's own check asks for it
+  while (again);
+  if (h->pair_tripped != tripped) h->last_pair_abandoned = 1;
+  if (h->flags != keep) h->last_engine = LOOP_ONE_REDUCE_REPEATED;
+  h->flags = keep;
+  return rc;
 }
 
 /* ---- checkpoint / resume ("Optional: dump (alpha, beta, j, V[:j])") ---------------------------------- */
@@ -1277,10 +1310,7 @@ int lz_get_residual(lz_handle h, double* r_local) {
   if (h->r_state == 2) {
     // the three- / five-launch loops leave y = A v_{n-1} behind: their three-term recurrence rides in the NEXT step's pass 1.
     // Form r = (y - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2} now, with the same kernel and expression (Lanczos.py:119).
-    Scope sc(h, LZ_K_THREE, 32.0 * (double)h->rows, 6.0 * (double)h->rows);
-    launch_three_term(h->d_r, h->d_V + (int64_t)(n - 1) * h->ldv, n >= 2 ? h->d_V + (int64_t)(n - 2) * h->ldv : nullptr, h->d_alpha + (n - 1),
-                      h->d_beta + (n >= 2 ? n - 2 : 0), h->rows_pad, h->d_part, h->stream);
-    LZ_TRY(check_launch(h, "three_term(residual)"));
+    LZ_TRY(step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), h->d_beta + (n - 2), false, nullptr, nullptr, "three_term(residual)"));
     h->r_state = 1;
   }
   if (h->r_state != 1)
@@ -1310,36 +1340,21 @@ int lz_run_resume_partial(lz_handle h, int n, int j0, const double* V_rows, int6
   if (ldv_in < h->rows) return fail(h, LZ_ERR_ARG, "lz_run_resume_partial: ldv_in < rows_local");
   if (!(h->flags & LZ_FLAG_REORTH_PARTIAL) || (h->flags & LZ_FLAG_ONE_REDUCE))
     return fail(h, LZ_ERR_STATE, "lz_run_resume_partial: needs LZ_FLAG_REORTH_PARTIAL without LZ_FLAG_ONE_REDUCE (the device-decided loop, engine 7)");
-  LZ_TRY(basis_alloc(h, n, j0));  // (all j0 uploaded rows cleared first: see lz_run_resume)
-  if (choose_loop(h, n) != LOOP_PARTIAL_DEVICE)
+  // (a refused call leaves the handle as the last run left it: the check comes before the frame, on the plan basis_alloc will make for
+  // n rows, and that plan is not stored - h->qplan has to match the allocation the single steps launch into)
+  const QtwPlan plan = plan_qtw(h->rows_pad, h->flags, h->tune, n);
+  if (h->kind != 0 && choose_loop(h, n, &plan) != LOOP_PARTIAL_DEVICE)
     return fail(h, LZ_ERR_STATE, "lz_run_resume_partial: these options / knobs do not select the device-decided partial loop");
-  h->halo_inflight_j = -1;
-  h->y_n = 0;
-  LZ_TRY(upload2d(h, h->d_V, (size_t)h->ldv * sizeof(double), V_rows, (size_t)ldv_in * sizeof(double), (size_t)h->rows * sizeof(double), (size_t)j0));
-  LZ_TRY(upload(h, h->d_r, r_local, (size_t)h->rows * sizeof(double)));
-  LZ_HIP(h, hipMemcpyAsync(h->d_alpha, alpha_in, (size_t)j0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(h->d_beta, beta_in, (size_t)(j0 - 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  LZ_HIP(h, hipEventRecord(h->run_a, h->stream));
-  h->host_syncs = 0;
+  RunFrame fr{h, n};
+  LZ_TRY(fr.begin(j0));  // (all j0 uploaded rows cleared first: see lz_run_resume)
+  LZ_TRY(upload_checkpoint(h, j0, V_rows, ldv_in, r_local, alpha_in, beta_in));
+  LZ_TRY(fr.uploaded());
   h->last_engine = LOOP_PARTIAL_DEVICE;
   LZ_TRY(run_loop_partial_device(h, n, j0, omega_state));
-  h->r_state = 1;
-  h->prof_iter = true;
-  LZ_HIP(h, hipEventRecord(h->run_b, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(alpha_out, h->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(beta_out, h->d_beta, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  std::vector<int> sweep_log(omega_state_ints(n));
-  LZ_HIP(h, hipMemcpyAsync(sweep_log.data(), h->d_omi, sweep_log.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  h->last_misses = 0;
-  h->last_gate_trips = 0;
-  h->sweep_log.assign((size_t)n, 0);  // (the steps of the first leg are not on this record)
-  account_partial_device(h, n, sweep_log, &h->last_sweeps);
-  for (int j = j0; j < n; ++j) h->sweep_log[(size_t)j] = sweep_log[(size_t)2 + j] != 0;
-  float ms = 0.f;
-  LZ_HIP(h, hipEventElapsedTime(&ms, h->run_a, h->run_b));
-  h->acc.total_ms += ms;
-  return breakdown_status(h, n, alpha_out, beta_out);
+  std::vector<int> dev_log(omega_state_ints(n));
+  LZ_TRY(fr.drain(alpha_out, beta_out, {{dev_log.data(), h->d_omi, dev_log.size() * sizeof(int)}}));
+  account_partial_device(h, n, dev_log, 2);  // (the steps of the first leg are not on this record)
+  return fr.finish(alpha_out, beta_out);
 }
 
 int lz_run_resume(lz_handle h, int n, int j0, const double* V_rows, int64_t ldv_in, const double* r_local, const double* alpha_in,
@@ -1353,31 +1368,14 @@ int lz_run_resume(lz_handle h, int n, int j0, const double* V_rows, int64_t ldv_
     return fail(h, LZ_ERR_STATE, "lz_run_resume: not with partial re-orthogonalisation (lz_run_resume_partial continues the device-decided loop from its omega state) or the one-reduce loop");
   // The j0 rows about to be uploaded are cleared whole: the upload writes `rows` columns of each, the kernels stream rows_pad of them,
   // and a recycled allocation's padding would enter ||r||^2 (a run's own kernels write the padding of every row they produce: zeros).
-  LZ_TRY(basis_alloc(h, n, j0));
-  h->halo_inflight_j = -1;
-  h->y_n = 0;
-  LZ_TRY(upload2d(h, h->d_V, (size_t)h->ldv * sizeof(double), V_rows, (size_t)ldv_in * sizeof(double), (size_t)h->rows * sizeof(double), (size_t)j0));
-  LZ_TRY(upload(h, h->d_r, r_local, (size_t)h->rows * sizeof(double)));
-  LZ_HIP(h, hipMemcpyAsync(h->d_alpha, alpha_in, (size_t)j0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (j0 > 1) LZ_HIP(h, hipMemcpyAsync(h->d_beta, beta_in, (size_t)(j0 - 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  LZ_HIP(h, hipEventRecord(h->run_a, h->stream));
-  int sweeps = n - j0;
+  RunFrame fr{h, n};
+  LZ_TRY(fr.begin(j0));
+  LZ_TRY(upload_checkpoint(h, j0, V_rows, ldv_in, r_local, alpha_in, beta_in));
+  LZ_TRY(fr.uploaded());
   h->last_engine = LOOP_SIX;  // every loop structure gives the same bits (tests/test_gpu_small.py): the plain one takes a start step
-  LZ_TRY(run_loop_six(h, n, &sweeps, j0));
-  h->last_sweeps = sweeps;
-  h->last_misses = 0;
-  h->last_gate_trips = 0;
-  h->sweep_log.assign((size_t)n, 1);
-  h->r_state = 1;
-  h->prof_iter = true;
-  LZ_HIP(h, hipEventRecord(h->run_b, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(alpha_out, h->d_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipMemcpyAsync(beta_out, h->d_beta, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  LZ_HIP(h, hipEventElapsedTime(&ms, h->run_a, h->run_b));
-  h->acc.total_ms += ms;
-  return breakdown_status(h, n, alpha_out, beta_out);
+  LZ_TRY(run_loop_six(h, n, j0));
+  LZ_TRY(fr.drain(alpha_out, beta_out));
+  return fr.finish(alpha_out, beta_out);
 }
 
 }  // extern "C"

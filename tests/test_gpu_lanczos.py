@@ -930,6 +930,88 @@ def test_checkpoint_and_resume_is_bit_identical(tmp_path, build, n1, n2, fused):
         s.close()
 
 
+def test_a_resume_counts_its_own_host_syncs(hip):
+    """lz_last_host_syncs is the record of the last run, lz_run or a resume: after a host-decided partial run (knob 18 = 1, one read-back
+    per step) a resume on the same handle reports its own count, 0, not the earlier run's."""
+    A = synthetic.laplacian_2d_5pt(20, 17).to_scipy().tocsr()
+    M, n = A.shape[0], 12
+    v0 = synthetic.reference_start_vector(M)
+    v0 /= np.linalg.norm(v0)
+    h = hip.Handle(0)
+    h.set_csr(M, 0, A.indptr, A.indices, A.data)
+    a5, b5 = h.run(5, v0)
+    V5, r5 = h.get_basis(), h.get_residual()
+    whole = h.run(n, v0)
+    h.set_options(hip.FLAG_REORTH_PARTIAL)
+    h.set_tuning(hip.TUNE_PARTIAL_LOOP, 1)
+    h.run(n, v0)
+    assert h.last_engine() == "kernels" and h.last_host_syncs() > n
+    h.set_options(0)
+    a, b = h.run_resume(n, V5, r5, a5, b5)
+    syncs, engine = h.last_host_syncs(), h.last_engine()
+    h.close()
+    assert engine == "kernels" and syncs == 0
+    assert np.array_equal(a, whole[0]) and np.array_equal(b, whole[1])
+
+
+def test_a_resume_clears_the_abandoned_pairs_mark(hip):
+    """lz_last_pair_abandoned speaks of the last run: a resume behind a run that abandoned its pairs reports 0."""
+    # the 40 x 30 periodic 5-point Laplacian plus 1e-9 (P - P^T) on its own off-diagonal pattern: the pair form's prediction assumes
+    # A = A^T and misses by ~1e-9 at every step (the abandoning input of tests/test_gpu_one_sweep_pair.py)
+    L = synthetic.laplacian_2d_5pt(40, 30).to_scipy().tocsr()
+    P = L.copy()
+    P.setdiag(0.0)
+    P.eliminate_zeros()
+    P.data = np.random.default_rng(5).uniform(-1.0, 1.0, size=P.nnz)
+    A = (L + 1e-9 * (P - P.T)).tocsr()
+    A.sort_indices()
+    M, n = A.shape[0], 30
+    v0 = synthetic.reference_start_vector(M)
+    v0 /= np.linalg.norm(v0)
+    h = hip.Handle(0)
+    h.set_options(hip.FLAG_FUSED_NORM)
+    h.set_tuning(hip.TUNE_LOOP, 8)  # the one-sweep loop at any size, with pairs
+    h.set_csr(M, 0, A.indptr, A.indices, A.data)
+    a, b = h.run(n, v0)
+    assert h.last_engine() == "one-sweep" and h.last_pair_abandoned() == 1
+    h.run_resume(n + 2, h.get_basis(), h.get_residual(), a, b)
+    abandoned, engine = h.last_pair_abandoned(), h.last_engine()
+    h.close()
+    assert engine == "kernels" and abandoned == 0
+
+
+def test_a_refused_resume_leaves_the_last_runs_record(hip):
+    """lz_run_resume_partial refuses options that do not select the device-decided loop before it touches anything: the record of the
+    last good run (engine, sweeps, the residual) is still there afterwards, and so is the Q^T w plan that matches its allocation - a
+    single step on the old basis gives the bits it gave before (the refused call came with another slice length: six blocks then, two)."""
+    A = synthetic.laplacian_2d_5pt(64, 48).to_scipy().tocsr()
+    M, n = A.shape[0], 12
+    v0 = synthetic.reference_start_vector(M)
+    v0 /= np.linalg.norm(v0)
+    h = hip.Handle(0)
+    h.set_options(hip.FLAG_REORTH_PARTIAL)
+    h.set_csr(M, 0, A.indptr, A.indices, A.data)
+    a, b = h.run(n, v0)
+    V, r, om, sweeps = h.get_basis(), h.get_residual(), h.get_omega_state(), h.last_sweeps()
+    assert h.last_engine() == "partial-device"
+
+    def reorth_last_row():
+        h.basis_set_row(n - 1, V[n - 1])
+        c = h.step_reorth(n - 1, n)[1]
+        return np.concatenate([c, h.basis_get_row(n - 1)])
+
+    before = reorth_last_row()
+    h.set_tuning(hip.TUNE_PARTIAL_LOOP, 1)  # the host-decided loop: not what lz_run_resume_partial continues
+    h.set_tuning(hip.TUNE_QTW_SLICE, 2048)
+    with pytest.raises(hip.LanczosHipError, match="do not select"):
+        h.run_resume(n + 4, V, r, a, b, omega_state=om)
+    h.set_tuning(hip.TUNE_QTW_SLICE, 0)
+    assert h.last_engine() == "partial-device" and h.last_sweeps() == sweeps
+    assert np.array_equal(h.get_residual(), r)
+    assert np.array_equal(reorth_last_row(), before)
+    h.close()
+
+
 @pytest.mark.parametrize("build,n1,n2", [(lambda: synthetic.laplacian_3d_7pt(40, 30, 20).to_scipy(), 37, 120),       # ELL-fused r / beta; sweeps on both sides of the cut
                                          (lambda: load_golden("deuteron3d_N12_27pt_n100")[1], 50, 100),              # 27-point rows: scale kernel + CSR stream
                                          (lambda: load_golden("box1d_N500_n50")[1], 2, 50),                          # the shortest first leg
