@@ -446,6 +446,15 @@ int lz_trl_probe(lz_handle h, int k, const double* x);
 int lz_trl_get_vectors(lz_handle h, int k, double* Y_out);
 /* out[i] = |A V[i] - theta[i] V[i]| for i < k: one fused SpMV-and-norm launch (CSR, the assembled stencil included); dense: the GEMV */
 int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out);
+/* The same for complex eigenvalues re[i] + i im[i] of a real non-symmetric matrix (lanczos_amd.eigs: Krylov-Schur on the calls above -
+ * on such a matrix lz_trl_extend is an Arnoldi step and lz_trl_restart takes any m x kk matrix, orthonormal or not).  Rows 0 .. k-1 hold
+ * the eigenvectors in real form.  im[i] == 0: row i is x and out[i] is lz_trl_residuals' value, bit for bit.  im[i] > 0: rows i and
+ * i + 1 are x_r and x_i of x = x_r + i x_i, which needs i + 1 < k, re[i + 1] == re[i] and im[i + 1] == -im[i], and
+ *   out[i] = out[i + 1] = sqrt(|A x_r - re x_r + im x_i|^2 + |A x_i - im x_r - re x_i|^2) = |A x - lambda x|.
+ * Anything else - a lone positive im at k - 1, mismatched re, a negative im without its partner in front, a NaN - is LZ_ERR_ARG before
+ * anything is launched.  CSR (the assembled stencil included): one fused launch, the pair's block walks each matrix row once for both
+ * products.  Dense: two GEMVs per pair.  Partial sums are added in a fixed order: same input, same bits.  1 <= k <= m. */
+int lz_trl_residuals_cplx(lz_handle h, int k, const double* re, const double* im, double* out);
 /* Chebyshev filter (lanczos_amd.eigsh(filter_degree=...); Zhou & Saad's filtered Lanczos): with degree > 0 every later lz_trl_extend
  * forms w = p(A) V[j] instead of w = A V[j], p the polynomial of the scaled three-term recurrence
  *   y_1 = a[0] (A x - c x),   y_i = a[i-1] (A y_{i-1} - c y_{i-1}) - b[i-1] y_{i-2}   (i = 2 .. degree, y_0 = x; b[0] is ignored as 0 x).

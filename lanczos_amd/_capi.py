@@ -171,6 +171,7 @@ SIGNATURES = {
     "lz_trl_probe": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_get_vectors": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_trl_residuals_cplx": (C.c_int, [_P, C.c_int, _D, _D, _D]),
     "lz_trl_set_filter": (C.c_int, [_P, C.c_int, _D, _D, C.c_double]),
     "lz_trl_set_series": (C.c_int, [_P, C.c_int, _D, C.c_double, C.c_double]),
     "lz_trl_filter_apply": (C.c_int, [_P, _D, _D]),
@@ -848,6 +849,14 @@ class Handle:
         th = f64(theta)[: int(k)]
         out = np.empty(int(k))
         self.check(self.lib.lz_trl_residuals(self._h, int(k), dptr(th), dptr(out)))
+        return out
+
+    def trl_residuals_cplx(self, k, re, im):
+        """|A x - (re + i im) x| for eigenvectors in real form in rows 0 .. k-1 (a pair: rows i, i + 1 = Re x, Im x; both get its norm)"""
+        re, im = f64(re)[: int(k)], f64(im)[: int(k)]
+        assert re.shape == (int(k),) and im.shape == (int(k),)
+        out = np.empty(int(k))
+        self.check(self.lib.lz_trl_residuals_cplx(self._h, int(k), dptr(re), dptr(im), dptr(out)))
         return out
 
     def trl_set_filter(self, coefficients, c=0.0):

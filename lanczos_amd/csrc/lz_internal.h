@@ -374,6 +374,13 @@ void launch_trl_band_proj(const double* C1, const double* C2, int r0, int b, int
 // squares of A y_i - theta_i y_i, block partials at part[i * G + b]; return G
 int launch_trl_resid_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* theta, double* part, hipStream_t s);
 int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s);
+// the same for complex eigenvalues re + i im of a real matrix, eigenvectors in real form (im[i] == 0: row i; im[i] > 0: rows i, i + 1
+// are the real and imaginary part, (re, im)[i + 1] the conjugate - the caller checks that): squares of |A x - lambda x|, the pair's at
+// part[i * G + b] and zeros at part[(i + 1) * G + b]; return G.  diff: one pair of a dense matrix, yr = A x_r, yi = A x_i.
+int launch_trl_resid_cplx_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* re, const double* im, double* part,
+                              hipStream_t s);
+int launch_trl_resid_cplx_diff(const double* yr, const double* yi, const double* xr, const double* xi, int64_t rows, const double* re,
+                               const double* im, int i, double* part, hipStream_t s);
 void launch_trl_rownorm(const double* part, int G, int k, double* out, hipStream_t s);
 // one step of the scaled Chebyshev recurrence, in place on wz (which holds w = A y): wz[r] = a (w[r] - c y[r]) - b x[r] for r < rows and
 // 0 for rows <= r < len; a = coef[i], b = coef[degree + i] are read on the device.  x may alias y (degree 1: b = 0).

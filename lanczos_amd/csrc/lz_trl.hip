@@ -1,6 +1,6 @@
 // Kernels of the thick-restart Lanczos solver (lz_trl_api.hip, lanczos_amd/eigsh.py): the in-place restart V[0..kk) <- S^T V[0..m),
 // the classical Gram-Schmidt update of r, the band form's block Gram-Schmidt (dots and update of b work vectors per walk over the
-// basis), the one-block bookkeeping between the passes, and the fused residual norms.
+// basis), the one-block bookkeeping between the passes, and the fused residual norms (real and, for eigs, complex eigenvalues).
 #include "lz_device.h"
 
 namespace lz {
@@ -529,6 +529,81 @@ __global__ __launch_bounds__(kTPB) void k_trl_resid_diff(const double* __restric
 int launch_trl_resid_diff(const double* y, const double* x, int64_t rows, const double* theta, int i, double* part, hipStream_t s) {
   const int G = (int)((rows + kTPB - 1) / kTPB);
   hipLaunchKernelGGL(k_trl_resid_diff, dim3(G), dim3(kTPB), 0, s, y, x, rows, theta, i, part);
+  return G;
+}
+// ------------------------------------------------------------------ true residuals |A x - lambda x| for complex lambda (Krylov-Schur, eigs)
+// Rows 0 .. k-1 of Y hold eigenvectors of a real matrix in real form.  im[i] == 0: row i is x and the value is k_trl_resid_csr's, the
+// same expressions in the same order: same bits.  im[i] > 0: rows i and i + 1 are x_r and x_i of x = x_r + i x_i (the caller has
+// checked that i + 1 < k and that (re, im)[i + 1] is the conjugate); the real and imaginary parts of A x - lambda x are
+//   t_r = A x_r - re x_r + im x_i,   t_i = A x_i - im x_r - re x_i,
+// and the block of row i adds t_r^2 + t_i^2: it walks each matrix row once and gathers x_r and x_i at every column, so one pass over
+// the matrix serves both products.  The block of row i + 1 (im < 0) reads nothing and writes a zero partial.  part[i * G + b], summed
+// by k_trl_rownorm in a fixed order: no atomics.
+__global__ __launch_bounds__(kTPB) void k_trl_resid_cplx_csr(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                             const double* __restrict__ vals, const double* __restrict__ Y, int64_t ldy,
+                                                             int64_t rows, const double* __restrict__ re, const double* __restrict__ im,
+                                                             double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const int i = blockIdx.y;
+  const double li = im[i];  // block-uniform
+  const int64_t row = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+  double d = 0.0;
+  if (row < rows && !(li < 0.0)) {
+    const double* x = Y + (int64_t)i * ldy;
+    if (li == 0.0) {
+      double sum = 0.0;
+      for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) sum += vals[e] * x[colidx[e]];
+      const double t = sum - re[i] * x[row];
+      d = t * t;
+    } else {
+      const double* xi = x + ldy;
+      double sr = 0.0, si = 0.0;
+      for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) {
+        const double v = vals[e];
+        const int32_t c = colidx[e];
+        sr += v * x[c];
+        si += v * xi[c];
+      }
+      const double lr = re[i], ar = x[row], ai = xi[row];
+      const double tr = (sr - lr * ar) + li * ai;
+      const double ti = (si - li * ar) - lr * ai;
+      d = tr * tr + ti * ti;
+    }
+  }
+  d = block_sum(d, sm);
+  if (threadIdx.x == 0) part[(int64_t)i * gridDim.x + blockIdx.x] = d;
+}
+int launch_trl_resid_cplx_csr(const CsrDev& A, const double* Y, int64_t ldy, int k, const double* re, const double* im, double* part,
+                              hipStream_t s) {
+  const int G = (int)((A.rows + kTPB - 1) / kTPB);
+  hipLaunchKernelGGL(k_trl_resid_cplx_csr, dim3(G, k), dim3(kTPB), 0, s, A.rowptr, A.colidx, A.vals, Y, ldy, A.rows, re, im, part);
+  return G;
+}
+// dense, a pair in rows i and i + 1: yr = A x_r and yi = A x_i come from two GEMVs; this adds t_r^2 + t_i^2 (part[i * G + b]) and
+// writes the zero partials of row i + 1 (part[(i + 1) * G + b])
+__global__ __launch_bounds__(kTPB) void k_trl_resid_cplx_diff(const double* __restrict__ yr, const double* __restrict__ yi,
+                                                              const double* __restrict__ xr, const double* __restrict__ xi, int64_t rows,
+                                                              const double* __restrict__ re, const double* __restrict__ im, int i,
+                                                              double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const int64_t row = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+  double d = 0.0;
+  if (row < rows) {
+    const double lr = re[i], li = im[i], ar = xr[row], ai = xi[row];
+    const double tr = (yr[row] - lr * ar) + li * ai;
+    const double ti = (yi[row] - li * ar) - lr * ai;
+    d = tr * tr + ti * ti;
+  }
+  d = block_sum(d, sm);
+  if (threadIdx.x == 0) {
+    part[(int64_t)i * gridDim.x + blockIdx.x] = d;
+    part[(int64_t)(i + 1) * gridDim.x + blockIdx.x] = 0.0;
+  }
+}
+int launch_trl_resid_cplx_diff(const double* yr, const double* yi, const double* xr, const double* xi, int64_t rows, const double* re,
+                               const double* im, int i, double* part, hipStream_t s) {
+  const int G = (int)((rows + kTPB - 1) / kTPB);
+  hipLaunchKernelGGL(k_trl_resid_cplx_diff, dim3(G), dim3(kTPB), 0, s, yr, yi, xr, xi, rows, re, im, i, part);
   return G;
 }
 // out[i] = sqrt(sum_b part[i * G + b]), one block per vector

@@ -11,10 +11,10 @@ using namespace lz::api;
 namespace {
 
 // trl_wk.sm: the basis layer's head (c of both passes, nrm2), the projected rows (m x m; band: m x (m + b)), beta (m), the restart's
-// S (m x m), theta and the residual norms (m each); band only: the block coefficients of both passes ((m + b) x b each) and the b
+// S (m x m), theta, the residual norms and the imaginary parts of lz_trl_residuals_cplx (m each); band only: the block coefficients of both passes ((m + b) x b each) and the b
 // squared norms of a batch
 struct TrlSmall : OrthSmallHead {
-  int64_t proj, beta, S, theta, res, C1, C2, nrmb, total;
+  int64_t proj, beta, S, theta, res, im, C1, C2, nrmb, total;
   int ldf;  // row length of proj
 };
 TrlSmall trl_small_layout(int m, int b = 1) {
@@ -26,7 +26,8 @@ TrlSmall trl_small_layout(int m, int b = 1) {
   L.S = L.beta + m + 8;
   L.theta = L.S + (int64_t)m * m;
   L.res = L.theta + m;
-  L.C1 = L.res + m + 8;
+  L.im = L.res + m + 8;
+  L.C1 = L.im + m + 8;
   const int64_t cb = b > 1 ? trl_band_run(m + b, b) + 16 : 0;
   L.C2 = L.C1 + cb;
   L.nrmb = L.C2 + cb;
@@ -167,7 +168,8 @@ int trl_alloc(lz_handle h, int m, int b, const char* who) {
   need = std::max<size_t>(need, (size_t)h->rows / 4 + 64);  // dense GEMV / scalar SpMV partials
   need = std::max<size_t>(need, (size_t)h->csr.n_rowblk + 64);
   if (h->csr.pb) need = std::max<size_t>(need, (size_t)pb_num_partials(h->csr.pb) + 64);
-  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64);  // residual norms + a dense product's
+  // residual norms + a dense product's partials + the second product of a conjugate pair (lz_trl_residuals_cplx, dense)
+  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + (size_t)h->rows / 4 + 64 + (size_t)h->rows_pad + 64);
   if (b > 1) {  // the block Gram-Schmidt's coefficient runs and squared-norm partials
     need = std::max<size_t>(need, (size_t)trl_band_dots_blocks(h->rows_pad, b) * (size_t)trl_band_run(m + b, b));
     need = std::max<size_t>(need, (size_t)b * (size_t)trl_band_update_blocks(h->rows_pad));
@@ -324,6 +326,49 @@ int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
   LZ_TRY(check_launch(h, "trl residuals"));
   LZ_HIP(h, hipMemcpyAsync(out, h->trl_wk.sm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
+}
+
+int lz_trl_residuals_cplx(lz_handle h, int k, const double* re, const double* im, double* out) {
+  LZ_TRY(trl_state(h, "lz_trl_residuals_cplx"));
+  if (!re || !im || !out || k < 1 || k > h->trl_m) return fail(h, LZ_ERR_ARG, "lz_trl_residuals_cplx: need 1 <= k <= m, re, im and out");
+  for (int i = 0; i < k; ++i) {  // every pair is whole before anything is launched
+    if (im[i] == 0.0) continue;
+    if (!(im[i] > 0.0) || i + 1 >= k || re[i + 1] != re[i] || im[i + 1] != -im[i])
+      return fail(h, LZ_ERR_ARG, "lz_trl_residuals_cplx: im[i] > 0 needs its conjugate at i + 1 (re[i + 1] == re[i], im[i + 1] == -im[i], i + 1 < k)");
+    ++i;
+  }
+  const TrlSmall L = trl_small_layout(h);
+  double* dre = h->trl_wk.sm + L.theta;
+  double* dimg = h->trl_wk.sm + L.im;
+  LZ_TRY(upload(h, dre, re, (size_t)k * sizeof(double)));
+  LZ_TRY(upload(h, dimg, im, (size_t)k * sizeof(double)));
+  int G = 0;
+  if (h->kind == 1) {
+    G = launch_trl_resid_cplx_csr(h->csr, h->trl.B, h->trl.ld, k, dre, dimg, h->trl_wk.part, h->stream);
+  } else {
+    const int Gd = (int)((h->rows + kTPB - 1) / kTPB);
+    double* gpart = h->trl_wk.part + (size_t)k * Gd;           // the products' own partials (not used)
+    double* yi = gpart + (((size_t)h->rows / 4 + 64) & ~(size_t)1);  // A x_i of a pair (trl_alloc sized the partials for it)
+    for (int i = 0; i < k; ++i) {
+      const double* x = h->trl.B + (int64_t)i * h->trl.ld;
+      launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, h->trl.w, gpart, h->stream);
+      if (im[i] == 0.0) {
+        G = launch_trl_resid_diff(h->trl.w, x, h->rows, dre, i, h->trl_wk.part, h->stream);
+      } else {
+        const double* xi = x + h->trl.ld;
+        launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, xi, xi, yi, gpart, h->stream);
+        G = launch_trl_resid_cplx_diff(h->trl.w, yi, x, xi, h->rows, dre, dimg, i, h->trl_wk.part, h->stream);
+        ++i;
+      }
+    }
+  }
+  launch_trl_rownorm(h->trl_wk.part, G, k, h->trl_wk.sm + L.res, h->stream);
+  LZ_TRY(check_launch(h, "trl residuals cplx"));
+  LZ_HIP(h, hipMemcpyAsync(out, h->trl_wk.sm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i + 1 < k; ++i)
+    if (im[i] > 0.0) out[i + 1] = out[i];  // both members of a pair carry the pair's norm
   return LZ_OK;
 }
 

@@ -13,6 +13,10 @@ gate next to the fixed-n loop's step, and one eigsh run on the device-assembled 
                                                 single-vector steps of lz_trl_extend at the same basis size, and block_size
                                                 None / 2 / 4 solves with and without the filter
                                                 (the record is profiles/r10/trl_band_probe.json)
+    python tools/trl_probe.py --eigs [--out FILE]     Krylov-Schur (lanczos_amd.eigs): eigs(k=6, "LR") on a 3-D convection-diffusion
+                                                grid of --eigs-n^3 rows (default 160: 4.1e6) against scipy.sparse.linalg.eigs
+                                                (host ARPACK) with the same k, which, ncv and tol
+                                                (the record is profiles/r17/trl_eigs_probe.json)
 
 Times are host wall clock around calls that end in a stream synchronisation, median of several repetitions: a call's fixed cost
 (~20 us: upload of S, launch, synchronisation) is included."""
@@ -351,6 +355,72 @@ def band_probe(a):
         save()
 
 
+def convdiff3d(N, p=(0.3, 0.2, 0.1)):
+    """7-point convection-diffusion on an N^3 grid, Dirichlet: diagonal 6, off-diagonals -1 -+ p per axis (non-symmetric, real spectrum)"""
+    import scipy.sparse as sp
+
+    def line(q):
+        return sp.diags([np.full(N - 1, -1.0 - q), np.full(N, 2.0), np.full(N - 1, -1.0 + q)], [-1, 0, 1], format="csr")
+
+    I = sp.identity(N, format="csr")
+    A = sp.kron(I, sp.kron(I, line(p[0]))) + sp.kron(I, sp.kron(line(p[1]), I)) + sp.kron(line(p[2]), sp.kron(I, I))
+    A = A.tocsr()
+    A.sort_indices()
+    return A
+
+
+def eigs_probe(a):
+    """lanczos_amd.eigs(k=6, which="LR") against scipy.sparse.linalg.eigs on the same matrix: wall time of the whole call (the device
+    call includes the upload of the matrix), restart cycles, products, and the true residuals of both measured on the host"""
+    import scipy.sparse.linalg as sla
+
+    import lanczos_amd
+
+    N, k, which, tol = a.eigs_n, 6, "LR", a.eigs_tol
+    A = convdiff3d(N)
+    n = A.shape[0]
+    out = {"matrix": f"3-D convection-diffusion {N}^3, p = (0.3, 0.2, 0.1)", "rows": n, "nnz": int(A.nnz), "k": k, "which": which, "tol": tol,
+           "ncv": "default (20)"}
+
+    def save():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+    def residual(w, X):
+        return float((np.linalg.norm(A @ X - X * w, axis=0)).max() / np.abs(w).max())
+
+    h = _capi.Handle(0)
+    for rep in range(2):  # the second call runs on a warm handle (kernels loaded, buffers allocated)
+        info = {}
+        t = time.perf_counter()
+        try:
+            w, X = lanczos_amd.eigs(A, k=k, which=which, tol=tol, maxiter=a.eigs_maxiter, handle=h, info=info)
+        except sla.ArpackNoConvergence as e:
+            out[f"device_run{rep}"] = {"converged": False, "wall_s": time.perf_counter() - t, "note": str(e)}
+            print(json.dumps(out[f"device_run{rep}"]), flush=True)
+            continue
+        wall = time.perf_counter() - t
+        out[f"device_run{rep}"] = {"converged": True, "wall_s": wall, "cycles": info["cycles"], "A_products": info["matvecs"],
+                                   "breakdowns": info["breakdowns"], "w": [[z.real, z.imag] for z in w],
+                                   "max_residual_over_max_w_host": residual(w, X),
+                                   "max_residual_over_anorm_device": float(info["residuals"].max() / info["anorm"])}
+        print(json.dumps(out[f"device_run{rep}"]), flush=True)
+        save()
+    h.close()
+    if not a.no_host:
+        t = time.perf_counter()
+        try:
+            w, X = sla.eigs(A, k=k, which=which, tol=tol, maxiter=a.eigs_maxiter)
+            out["host_arpack"] = {"converged": True, "wall_s": time.perf_counter() - t, "w": [[z.real, z.imag] for z in w],
+                                  "max_residual_over_max_w_host": residual(w, X), "threads": os.environ.get("OMP_NUM_THREADS")}
+        except sla.ArpackNoConvergence as e:
+            out["host_arpack"] = {"converged": False, "wall_s": time.perf_counter() - t, "note": str(e)}
+        print(json.dumps(out["host_arpack"]), flush=True)
+    save()
+
+
 def filter_trace(a):
     """A short run for `rocprofv3 --kernel-trace --stats -- python tools/trl_probe.py --filter-trace`: ten degree-16 filter applications
     on each arm and matrix, so that the trace's per-kernel averages give k_cheb_step, the plain SpMV and the fused SpMV step."""
@@ -383,6 +453,11 @@ def main():
     ap.add_argument("--band-maxiter", type=int, default=3000, help="--band: restart cycles allowed to each solve")
     ap.add_argument("--solve-n", type=int, default=48, help="--series: a second, smaller deuteron grid for the solves")
     ap.add_argument("--solve-maxiter", type=int, default=4000, help="--series: restart cycles allowed to each solve on the smaller grid")
+    ap.add_argument("--eigs", action="store_true", help="probe Krylov-Schur (lanczos_amd.eigs) instead (see the module docstring)")
+    ap.add_argument("--eigs-n", type=int, default=160, help="--eigs: the grid is eigs-n^3")
+    ap.add_argument("--eigs-tol", type=float, default=1e-10, help="--eigs: tol of both solvers")
+    ap.add_argument("--eigs-maxiter", type=int, default=20000, help="--eigs: restart cycles allowed to each solver")
+    ap.add_argument("--no-host", action="store_true", help="--eigs: skip the host ARPACK run")
     ap.add_argument("--filter-trace", action="store_true", help="the short run meant for a kernel trace (see filter_trace)")
     ap.add_argument("--deuteron-n", type=int, default=160)
     ap.add_argument("--maxiter", type=int, default=400, help="--filter: restart cycles allowed to each solve on the 2-D Laplacian; --series: to "
@@ -396,6 +471,8 @@ def main():
         return series_probe(a)
     if a.band:
         return band_probe(a)
+    if a.eigs:
+        return eigs_probe(a)
     out = {}
     M = a.rows
     H = synthetic.laplacian_2d_5pt(4000, M // 4000)  # the headline's matrix family at M = 1e7
