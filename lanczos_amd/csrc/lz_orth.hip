@@ -2,8 +2,11 @@
 // orthogonal to an OrthBasis (lz_context.h) and store it as the basis' next row, the row transfers, and the partials they need.  The
 // kernels are lz_reorth.hip's (launch_qtw, launch_final_rows, launch_scale_store) and lz_trl.hip's (launch_trl_cgs, launch_trl_post).
 // What every sequence relies on:
-//  - the walks stream pad doubles of every row and of w, the products write len: w[len .. pad) is zero (orth_upload_x; the products
-//    clear it; lz_trl_extend_band clears its own work vectors), or a NaN left there would reach every coefficient;
+//  - the walks stream pad doubles of every row and of w, the products write len and never touch w[len .. pad).  That padding is zero
+//    because orth_upload_x zeroes all of w before every begin and every probe, and a Gram-Schmidt update with finite coefficients on
+//    zero-padded rows keeps it zero.  A breakdown (0 / 0 behind a vanished residual) leaves NaN there, which no product would clear: the
+//    probe that follows a breakdown does, through orth_upload_x (lz_trl_extend_band clears its own work vectors itself).  A NaN left
+//    there would reach every coefficient;
 //  - the dots take one row more than they project on: row n of B is the self slot, whose "dot" is w . w (the kernel reads w there);
 //  - launch_trl_post(0) sets gate[0] for pass 2 (pass 1 cancelled more than half of |w|, or force), the gated launches of pass 2
 //    return at once where it is 0, and launch_trl_post(1) takes pass 2's norm and adds its coefficients only where it ran.

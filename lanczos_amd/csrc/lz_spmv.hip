@@ -973,29 +973,19 @@ static int launch_spmv_cls(const CsrDev& A, const double* x, double* y, const do
   code.ncls = A.ell_ncls;
   const size_t lds = (size_t)A.ell_ncls * K * 12 + 8;
   code.diag = A.cls_diag;
-  const SpmvScale none;
-  const SpmvCheb noch;
-  if (A.ell_coded == 3) {
-    if (sc)
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc, noch);
-    else if (ch) {
-      if (ch->acc)
-        hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true, 2>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
-      else
-        hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true, 1>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
-    } else {
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, true>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, noch);
-    }
-  } else if (sc) {
-    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, true, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, *sc, noch);
-  } else if (ch) {
-    if (ch->acc)
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false, 2>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
-    else
-      hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false, 1>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, *ch);
-  } else {
-    hipLaunchKernelGGL((k_spmv_cls<K, RPT, G, false, false>), dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, none, noch);
-  }
+  const bool diag = A.ell_coded == 3;
+  const int chk = sc || !ch ? 0 : (ch->acc ? 2 : 1);
+  // (one signature for every form: the form is chosen first, so that the LDS limit is raised on the kernel that is launched)
+  auto kern = sc ? (diag ? k_spmv_cls<K, RPT, G, true, true> : k_spmv_cls<K, RPT, G, true, false>)
+              : chk == 2 ? (diag ? k_spmv_cls<K, RPT, G, false, true, 2> : k_spmv_cls<K, RPT, G, false, false, 2>)
+              : chk == 1 ? (diag ? k_spmv_cls<K, RPT, G, false, true, 1> : k_spmv_cls<K, RPT, G, false, false, 1>)
+                         : (diag ? k_spmv_cls<K, RPT, G, false, true> : k_spmv_cls<K, RPT, G, false, false>);
+  // 27 entries per row and more than 202 classes: the table passes the 64 KiB a kernel may ask for by default (256 classes: 82,952
+  // bytes).  A refused raise stays the runtime's last error, which the caller's check_launch reports.
+  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return nunits;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kTPB), lds, s, code, x, x_own, y, (int)A.rows, rows_pad, nunits, part, sc ? *sc : SpmvScale(),
+                     chk ? *ch : SpmvCheb());
   return nunits;
 }
 template <int K>

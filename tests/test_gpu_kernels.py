@@ -207,6 +207,118 @@ def test_spmv_row_class_coding_gives_way(hip):
     h.close()
 
 
+def layered_stencil27(nx=6, ny=5, nz=24, symmetric=False):
+    """A periodic 27-point stencil whose coefficients depend on the z layer, the +1 and -1 neighbours weighted differently
+    (non-symmetric; ``symmetric``: the weight of an entry depends on both its layers alike): 9 boundary kinds in x, y times ``nz``
+    layers of classes by offsets and values - 216 of the 256 a class byte can name, a table of 216 x 27 x 12 + 8 = 69,992 bytes of LDS,
+    past the 64 KiB a kernel may ask for without raising its limit.
+    Returns ``(A, A + a random diagonal)``: the second has as many classes with the diagonal streamed."""
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    row = ((z * ny + y) * nx + x).ravel()
+    rows, cols, vals = [], [], []
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                base = 26.0 if (dx, dy, dz) == (0, 0, 0) else -(1.0 + 0.25 * dx + 0.125 * dy + 0.0625 * dz) / (abs(dx) + abs(dy) + abs(dz))
+                rows.append(row)
+                cols.append(((((z + dz) % nz) * ny + (y + dy) % ny) * nx + (x + dx) % nx).ravel())
+                if symmetric:
+                    base = 26.0 if (dx, dy, dz) == (0, 0, 0) else -1.0 / (abs(dx) + abs(dy) + abs(dz))
+                    vals.append(base * (1.0 + (z.ravel() + (z.ravel() + dz) % nz + 2) / 64.0))
+                else:
+                    vals.append(base * (1.0 + (z.ravel() + 1) / 32.0 * (1 + dz)))  # the layer's own weight, another one for each of dz = -1, 0, 1
+    A = scipy.sparse.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(nx * ny * nz,) * 2)
+    A.sort_indices()
+    assert np.all(np.diff(A.indptr) == 27)
+    D = (A + scipy.sparse.diags(np.random.default_rng(27).uniform(-1.0, 1.0, A.shape[0]))).tocsr()
+    D.sort_indices()
+    return A, D
+
+
+@pytest.mark.parametrize("which", ["constant", "random_diagonal"])
+def test_spmv_27_entry_class_table_past_64_kib(hip, which):
+    """216 classes of 27 entries: the fully coded kernel's table (values and offsets, 69,992 bytes) needs the kernel's dynamic LDS limit
+    raised (launch_spmv_cls does: no earlier matrix in the suite had 27 entries per row and more than 27 classes).  Held to
+    test_spmv_row_class_coding_bit_exact's standard: y and r equal SciPy's bit for bit, twice, in every layout, and the ELL-order layouts
+    agree on alpha's bits (knob 1 is the CSR-stream kernel for 27 entries, which groups alpha's partials differently)."""
+    H = layered_stencil27()[which == "random_diagonal"]
+    assert abs(H - H.T).max() > 0.1
+    coding = "offsets+values" if which == "constant" else "offsets+values, diagonal streamed"
+    M = H.shape[0]
+    x = np.random.default_rng(1).uniform(-1, 1, M)
+    ref = H * x
+    alphas = {}
+    for knob in (0, 1, 2, 4):
+        h = hip.Handle(0)
+        h.set_tuning(hip.TUNE_FIXED_LAYOUT, knob)
+        h.set_csr(M, 0, H.indptr, H.indices, H.data)
+        want = {0: (coding, 216), 1: ("none", 0), 2: ("none", 0), 4: ("offsets", 27)}[knob]
+        assert h.spmv_coding() == want, (knob, h.spmv_coding())
+        assert h.spmv_plan() == ("csr-stream" if knob == 1 else "fixed-k")
+        for _ in range(2):
+            y = h.spmv_host(x)
+            assert np.array_equal(y, ref), (knob, np.abs(y - ref).max())
+        h.basis_alloc(3)
+        h.basis_set_row(1, x)
+        alphas[knob] = h.step_spmv(1)
+        assert np.array_equal(h.r_get(), ref)
+        assert abs(alphas[knob] - np.dot(x, ref)) <= 1e-13 * np.dot(np.abs(x), np.abs(H) * np.abs(x))
+        h.close()
+    assert alphas[0] == alphas[2] == alphas[4]
+
+
+@pytest.mark.parametrize("which", ["constant", "random_diagonal"])
+def test_filter_steps_fused_into_the_27_entry_class_table(hip, which):
+    """the Chebyshev filter's and the series' step as the coded kernel's epilogue are kernels of their own, each with its own LDS limit
+    to raise: the same bits as the plain coded SpMV followed by the step kernel (LZ_FLAG_TRL_FILTER_UNFUSED)"""
+    from lanczos_amd.eigsh import ChebFilter, SeriesFilter
+
+    H = layered_stencil27()[which == "random_diagonal"]
+    coding = "offsets+values" if which == "constant" else "offsets+values, diagonal streamed"
+    M = H.shape[0]
+    nrm = float(abs(H).sum(axis=1).max())
+    f, s = ChebFilter(-nrm, 0.5 * nrm, 1.5 * nrm, 4), SeriesFilter(-nrm, nrm, 0.1 * nrm, 5)
+    x = np.random.default_rng(2).uniform(-1, 1, M)
+    out = []
+    for flags in (0, hip.FLAG_TRL_FILTER_UNFUSED):
+        h = hip.Handle(0)
+        h.set_options(flags)
+        h.set_csr(M, 0, H.indptr, H.indices, H.data)
+        assert h.spmv_coding() == (coding, 216)
+        h.trl_begin(8, x)
+        h.trl_set_filter(f.coefficients(), f.c)
+        yf = h.trl_filter_apply(x)
+        h.trl_set_series(s.coefficients(), s.c, s.e)
+        out.append((yf, h.trl_filter_apply(x)))
+        h.close()
+    for fused, unfused in zip(*out):
+        assert np.isfinite(fused).all() and np.abs(fused).max() > 0
+        assert np.array_equal(fused, unfused)
+
+
+def test_partial_loop_fused_scale_on_the_27_entry_class_table(hip):
+    """the device-resident partial re-orthogonalisation loop forms r / beta inside the coded SpMV (one more kernel form with its own LDS
+    limit): same sweeps, coefficients and basis, bit for bit, as the loop with the plain coded SpMV and a scale pass (knob 18 = 2)"""
+    from lanczos_amd import Lanczos
+
+    H = layered_stencil27(symmetric=True)[0]
+    assert abs(H - H.T).max() == 0.0
+    Lanczos.verbose = False
+    runs = []
+    for knob in (0, 2):
+        s = Lanczos(H)
+        s.reorth = "partial"
+        s._get_handle().set_tuning(hip.TUNE_PARTIAL_LOOP, knob)
+        s.execute_Lanczos(40)
+        h = s._get_handle()
+        assert h.spmv_coding() == ("offsets+values", 216) and h.last_engine() == "partial-device"
+        runs.append((np.array(s.H_eff), np.array(s.V), s.sweeps))
+        s.close()
+    assert runs[0][2] == runs[1][2]
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+    assert np.all(np.isfinite(runs[0][1])) and np.abs(runs[0][1].T @ runs[0][1] - np.eye(40)).max() < 1e-6  # semi-orthogonal
+
+
 def _two_phase_matrices():
     rng = np.random.default_rng(11)
     big = synthetic.random_graph_laplacian(60000, 210000, seed=8).to_scipy()  # several row blocks x 118 column blocks
