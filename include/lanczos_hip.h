@@ -162,6 +162,8 @@ int lz_set_options(lz_handle h, int flags);
  *   21  Gram matrix: number of K slices (workgroups per unit) of the symmetric kernel; 0 auto (whole residency rounds of 256)
  *   20  one-reduce partial loop (LZ_FLAG_REORTH_PARTIAL | LZ_FLAG_ONE_REDUCE): safety factor kappa of the look-ahead sweep
  *       decision (a sweep is due when kappa * max |predicted omega| > sqrt(eps); 0 = the default, 4)
+ * The dense operator of lz_gk_set_dense reads three of these at that call, each in the sense it already has: 14 (the SpMV plan) forces
+ * its product forms, 4 (entries per segment of a long row) is its segment length, 2 (rows per block) its slab height - see there.
  * The product library returns LZ_ERR_ARG for everything that lives only in the kernel-bench build (make KBENCH=1 ->
  * liblanczos_kbench.so, loaded by tools/ and by the tests of those arms; sources: lz_small.hip, lz_*_kbench.h): the A/B arms
  * retired in round 3 because they measured slower - the one-kernel and one-launch-per-step engines
@@ -514,6 +516,28 @@ int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
  * call keeps every long row in one workgroup (the A/B arm of the segment path).  Drops a basis of an earlier matrix. */
 int lz_gk_set_csr(lz_handle h, int64_t p, int64_t q, int64_t nnz, const int32_t* rowptr, const int32_t* colidx, const double* vals,
                   const int32_t* rowptrT, const int32_t* colidxT, const double* valsT);
+/* The same operator as ONE dense row-major array: S is p x q (stored_transposed == 0) or q x p (the transpose of the tall operator:
+ * a wide matrix as its caller holds it), p >= q >= 2, host rows ld_host >= the row length apart.  The device keeps one copy with an
+ * even row stride (8 B per entry, nothing is transposed or indexed) and runs both directions on it: along the rows ("rowdot",
+ * out[r] = sum_c S[r, c] x[c]) and down the columns ("colsum", out[c] = sum_r S[r, c] u[r]).  Stored tall, A x is rowdot and A^T u
+ * colsum; stored wide the other way round.  The form of each is chosen here from the shape and the CU count (lz_gk_plan reports it):
+ *   rowdot  1 short rows (row length <= 128): a group of lanes per row, several rows per wave
+ *           2 one wave per row
+ *           3 four adjacent rows per wave, which share the loads of x: medium rows (up to 1024) whole, and fewer than 768 longer
+ *             rows cut into two or more segments of >= 2048 doubles, a wave per segment (tuning knob 4: the segment length in
+ *             doubles, even, clamped to 64 .. 2^22), the partials added in segment order by a fold kernel
+ *   colsum 11 tiles of 128 columns x slabs of rows (knob 2: rows per slab, clamped to 1 .. 2^22), the slabs added in order by a
+ *             fold kernel
+ *          12 the same tiles with one slab that holds every row: no fold kernel (the tiles alone fill the device, or few rows)
+ *          13 rows shorter than 128: a group of lanes per row, many rows per workgroup and trip, slabs as in 11
+ * Knob 14 = r + 4 c forces the rowdot form r (1 / 2 / 3) and the colsum form 10 + c (c = 1 / 2 / 3) at any shape, r or c = 0 leaves
+ * that one to the shape (A/B, tests); the three knobs are read at this call.  No atomics: the same input gives the same bits; the sums use fma and another order than a
+ * CSR copy's.  Values are not validated (lz_gk_set_csr does not validate its values either).  Errors as lz_gk_set_csr, before any
+ * device work.  Frees the CSR operator of an earlier lz_gk_set_csr, as that call frees a dense one; drops a basis of an earlier matrix. */
+int lz_gk_set_dense(lz_handle h, int64_t p, int64_t q, const double* S, int64_t ld_host, int stored_transposed);
+/* out[0] = the operator's kind (0 CSR, 1 dense), out[1] = 1 when the dense copy is the transpose (q x p), out[2] / out[3] = the form
+ * that A x / A^T u run (the codes above; 0 for CSR).  LZ_ERR_STATE before lz_gk_set_csr / lz_gk_set_dense. */
+int lz_gk_plan(lz_handle h, int* out);
 /* allocate and zero V (m + 1 rows of the padded q) and U (m + 1 rows of the padded p; row m stays zero), 2 <= m <= min(128, q);
  * V[0] = v0 / |v0| (v0: q doubles) */
 int lz_gk_begin(lz_handle h, int m, const double* v0);
@@ -540,7 +564,7 @@ int lz_gk_get_rows(lz_handle h, int side, int j0, int count, double* rows, int64
 int lz_gk_residuals(lz_handle h, int k, const double* sigma, double* out);
 /* one product through the rectangular kernel on host vectors: y = A x (transpose == 0: x q doubles, y lz_padded_rows(p) doubles) or
  * y = A^T x (x p doubles, y lz_padded_rows(q) doubles).  y receives the padding too, which the kernel writes as zeros.  Needs
- * lz_gk_set_csr only; uses the work vectors of lz_gk_extend. */
+ * lz_gk_set_csr or lz_gk_set_dense only; uses the work vectors of lz_gk_extend. */
 int lz_gk_spmv(lz_handle h, int transpose, const double* x, double* y);
 /* *ms_out = the device time (hipEvents) of one such product, the mean of reps launches behind one warm-up launch, on whatever the work
  * vectors hold: the measurements of tools/svds_probe.py */

@@ -179,6 +179,8 @@ SIGNATURES = {
     "lz_trl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_trl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
+    "lz_gk_set_dense": (C.c_int, [_P, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int]),
+    "lz_gk_plan": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_gk_begin": (C.c_int, [_P, C.c_int, _D]),
     "lz_gk_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _D]),
     "lz_gk_restart": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
@@ -906,6 +908,25 @@ class Handle:
         self.check(self.lib.lz_gk_set_csr(self._h, int(p), int(q), int(A.nnz), i32ptr(arrs[0]), i32ptr(arrs[1]), dptr(arrs[2]),
                                           i32ptr(arrs[3]), i32ptr(arrs[4]), dptr(arrs[5])))
         self.gk_shape = (int(p), int(q))
+
+    def gk_set_dense(self, S, stored_transposed=False):
+        """the operator as one dense row-major float64 array: ``S`` is ``p x q`` (``p >= q``), or ``q x p`` with ``stored_transposed``.
+        Rows that are contiguous but further apart than their length (a column slice of a wider array) are passed as they are."""
+        S = np.asarray(S)
+        if S.ndim != 2:
+            raise ValueError(f"expected a matrix (shape={S.shape})")
+        R, Cn = S.shape
+        if S.dtype != np.float64 or S.strides[1] != 8 or S.strides[0] % 8 or S.strides[0] < 8 * Cn:
+            S = f64(S)
+        p, q = (Cn, R) if stored_transposed else (R, Cn)
+        self.check(self.lib.lz_gk_set_dense(self._h, int(p), int(q), dptr(S), S.strides[0] // 8, 1 if stored_transposed else 0))
+        self.gk_shape = (int(p), int(q))
+
+    def gk_plan(self):
+        """(kind: 0 CSR / 1 dense, stored transposed, form of ``A x``, form of ``A^T u``): the codes of include/lanczos_hip.h"""
+        out = (C.c_int * 4)()
+        self.check(self.lib.lz_gk_plan(self._h, out))
+        return tuple(out)
 
     def gk_begin(self, m, v0):
         v0 = f64(v0)

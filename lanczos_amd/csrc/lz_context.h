@@ -81,10 +81,12 @@ inline OrthSmallHead orth_small_head(int nrows) {
 }
 
 // Golub-Kahan-Lanczos bidiagonalisation (lz_gk_api.hip, lanczos_amd.svds): a rectangular operator and two bases of their own, separate
-// from the handle's square operator, its fixed-n run and its thick-restart basis.  A is p x q (p >= q), AT its transpose.
+// from the handle's square operator, its fixed-n run and its thick-restart basis.  A is p x q (p >= q), AT its transpose - or, after
+// lz_gk_set_dense, D.S is the one dense copy of either of them and A, AT are empty: gk_product (lz_gk_api.hip) is the only place that asks.
 struct GkState {
   bool set = false;
   CsrDev A, AT;
+  lz::DenseDev D;    // D.S != nullptr: the operator is dense
   int m = 0;         // 0: no basis (lz_gk_begin)
   int u_ready = -1;  // k: U[k] was made by lz_gk_probe, so lz_gk_extend(k, ..) starts step k at its second half
   OrthBasis U;       // the long side (len p): m + 1 rows (row m stays zero: launch_trl_restart copies it to row kk); w = A V[j]

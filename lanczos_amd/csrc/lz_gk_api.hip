@@ -3,8 +3,9 @@
 // handle's square operator: h->kind, h->rows, a fixed-n run's V / Y and a thick-restart basis on the same handle stay as they are.
 // What is here is the solver's own: the rectangular matrices and their work items, the alternating step with its resumed half, the
 // two-sided restart, the residuals and the product probes.  Orthogonalising against U or V - an OrthBasis each, with one OrthWork
-// between them - and the row transfers are the basis layer's (lz_orth.hip), shared with the thick-restart solver; the products are
-// launch_spmv_rect (lz_gk.hip) - these matrices never reach launch_spmv_csr or any of the square layouts, whose epilogue reads x_own[row].
+// between them - and the row transfers are the basis layer's (lz_orth.hip), shared with the thick-restart solver; the products go
+// through gk_product: launch_spmv_rect (lz_gk.hip) for a CSR operator - these matrices never reach launch_spmv_csr or any of the square
+// layouts, whose epilogue reads x_own[row] - or the rowdot / colsum kernels on the one dense copy of lz_gk_set_dense.
 #include "lz_context.h"
 
 using namespace lz;
@@ -35,7 +36,7 @@ OrthBasis& gk_basis(lz_handle h, int side) { return side == 0 ? h->gk.U : h->gk.
 
 int gk_state(lz_handle h, const char* who, bool need_basis) {
   if (!h) return LZ_ERR_ARG;
-  if (!h->gk.set) return fail(h, LZ_ERR_STATE, std::string(who) + ": no rectangular matrix (lz_gk_set_csr first)");
+  if (!h->gk.set) return fail(h, LZ_ERR_STATE, std::string(who) + ": no rectangular matrix (lz_gk_set_csr or lz_gk_set_dense first)");
   if (need_basis && h->gk.m == 0) return fail(h, LZ_ERR_STATE, std::string(who) + ": no basis (lz_gk_begin first)");
   LZ_HIP(h, hipSetDevice(h->dev));
   return LZ_OK;
@@ -83,6 +84,36 @@ void gk_free_csr(CsrDev& A) {
   A = CsrDev();
 }
 
+void gk_free_dense(DenseDev& D) {
+  big_free(D.S);
+  big_free(D.rd_part);
+  big_free(D.cs_part);
+  D = DenseDev();
+}
+
+// y = Aop x (transpose == 0) or Aop^T x with whichever operator the state holds; y[len .. pad) = 0
+hipError_t gk_product(lz_handle h, int transpose, const double* x, double* y, int64_t pad) {
+  const GkState& g = h->gk;
+  if (!g.D.S) return launch_spmv_rect(transpose ? g.AT : g.A, x, y, pad, h->stream);
+  return (transpose != 0) == g.D.stored_t ? launch_dense_rowdot(g.D, x, y, pad, h->stream) : launch_dense_colsum(g.D, x, y, pad, h->stream);
+}
+
+// the work vectors of both sides, sized for (p, q); the basis of an earlier operator is gone by now
+int gk_alloc_work(lz_handle h, int64_t p, int64_t q) {
+  GkState& g = h->gk;
+  g.U.len = p;
+  g.V.len = q;
+  for (OrthBasis* b : {&g.U, &g.V}) {
+    b->pad = round_up(b->len, kPadDoubles);
+    b->ld = skew_stride(h, b->pad);
+    LZ_TRY(dev_alloc(h, b->w, (size_t)b->ld));
+  }
+  LZ_HIP(h, hipMemsetAsync(g.U.w, 0, (size_t)g.U.ld * sizeof(double), h->stream));
+  LZ_HIP(h, hipMemsetAsync(g.V.w, 0, (size_t)g.V.ld * sizeof(double), h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
+}
+
 int gk_free_basis(lz_handle h) {
   GkState& g = h->gk;
   LZ_TRY(dev_free(h, g.U.B));
@@ -106,6 +137,7 @@ void gk_free(lz_handle h) {
   GkState& g = h->gk;
   gk_free_csr(g.A);
   gk_free_csr(g.AT);
+  gk_free_dense(g.D);
   orth_free(g.U);
   orth_free(g.V);
   orth_free(g.wk);
@@ -131,22 +163,62 @@ int lz_gk_set_csr(lz_handle h, int64_t p, int64_t q, int64_t nnz, const int32_t*
   GkState& g = h->gk;
   g.set = false;
   LZ_TRY(gk_free_basis(h));
+  gk_free_dense(g.D);
   int fixed_k = 0, max_nnz = 0, max_nnzT = 0;
   LZ_TRY(upload_csr(h, g.A, "lz_gk_set_csr", p, q, nnz, rowptr, colidx, vals, &fixed_k, &max_nnz));
   LZ_TRY(gk_fill_meta(h, g.A, rowptr, p, q, nnz, max_nnz));
   LZ_TRY(upload_csr(h, g.AT, "lz_gk_set_csr (transpose)", q, p, nnz, rowptrT, colidxT, valsT, &fixed_k, &max_nnzT));
   LZ_TRY(gk_fill_meta(h, g.AT, rowptrT, q, p, nnz, max_nnzT));
-  g.U.len = p;
-  g.V.len = q;
-  for (OrthBasis* b : {&g.U, &g.V}) {
-    b->pad = round_up(b->len, kPadDoubles);
-    b->ld = skew_stride(h, b->pad);
-    LZ_TRY(dev_alloc(h, b->w, (size_t)b->ld));
-  }
-  LZ_HIP(h, hipMemsetAsync(g.U.w, 0, (size_t)g.U.ld * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(g.V.w, 0, (size_t)g.V.ld * sizeof(double), h->stream));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  LZ_TRY(gk_alloc_work(h, p, q));
   g.set = true;
+  return LZ_OK;
+}
+
+int lz_gk_set_dense(lz_handle h, int64_t p, int64_t q, const double* S, int64_t ld_host, int stored_transposed) {
+  if (!h) return LZ_ERR_ARG;
+  const int64_t R = stored_transposed ? q : p, C = stored_transposed ? p : q;
+  if (q < 2 || p < q || !S || ld_host < C)
+    return fail(h, LZ_ERR_ARG, "lz_gk_set_dense: need p >= q >= 2, S (row-major, p x q, or q x p when stored_transposed) and ld_host >= its row length");
+  if (p >= (int64_t)1 << 31) return fail(h, LZ_ERR_ARG, "lz_gk_set_dense: sizes exceed int32 indexing");
+  if (h->world > 1 || h->comm_kind != 0)
+    return fail(h, LZ_ERR_STATE, "lz_gk_set_dense: the Golub-Kahan-Lanczos solver runs on one rank (this handle has a communicator)");
+  LZ_HIP(h, hipSetDevice(h->dev));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  GkState& g = h->gk;
+  g.set = false;
+  LZ_TRY(gk_free_basis(h));
+  gk_free_csr(g.A);
+  gk_free_csr(g.AT);
+  gk_free_dense(g.D);
+  DenseDev D;
+  D.R = R;
+  D.C = C;
+  D.ld = round_up(C, 2);
+  D.stored_t = stored_transposed != 0;
+  // knob 14 (the SpMV plan): rowdot form + 4 * colsum form, 0 = by shape; knob 4 (entries per segment of a long row): the segment
+  // length; knob 2 (rows per block): the slab height
+  dense_plan(D, h->tune[14] & 3, (h->tune[14] >> 2) & 3, h->tune[4], h->tune[2]);
+  g.D = D;  // (from here on gk_free_dense releases whatever has been allocated)
+  LZ_TRY(dev_alloc(h, g.D.S, (size_t)R * (size_t)D.ld));
+  LZ_TRY(dev_alloc(h, g.D.rd_part, (size_t)D.rd_nseg * (size_t)round_up(R, kPadDoubles)));
+  LZ_TRY(dev_alloc(h, g.D.cs_part, D.cs_form == kCsOne ? 0 : (size_t)D.cs_nslab * (size_t)round_up(C, kPadDoubles)));
+  if (D.ld > C) LZ_HIP(h, hipMemset2D(g.D.S + C, (size_t)D.ld * sizeof(double), 0, sizeof(double), (size_t)R));  // the padding column
+  LZ_HIP(h, hipMemcpy2D(g.D.S, (size_t)D.ld * sizeof(double), S, (size_t)ld_host * sizeof(double), (size_t)C * sizeof(double), (size_t)R,
+                        hipMemcpyHostToDevice));
+  LZ_TRY(gk_alloc_work(h, p, q));
+  g.set = true;
+  return LZ_OK;
+}
+
+int lz_gk_plan(lz_handle h, int* out) {
+  LZ_TRY(gk_state(h, "lz_gk_plan", false));
+  if (!out) return fail(h, LZ_ERR_ARG, "lz_gk_plan: need out (4 ints)");
+  const DenseDev& D = h->gk.D;
+  const bool dense = D.S != nullptr;
+  out[0] = dense ? 1 : 0;
+  out[1] = dense && D.stored_t ? 1 : 0;
+  out[2] = !dense ? 0 : D.stored_t ? D.cs_form : D.rd_form;  // Aop x
+  out[3] = !dense ? 0 : D.stored_t ? D.rd_form : D.cs_form;  // Aop^T u
   return LZ_OK;
 }
 
@@ -191,11 +263,11 @@ int lz_gk_extend(lz_handle h, int k, int m, double* colproj_out, double* alpha_o
     // w = A V[j] against U[0..j): column j of B above the diagonal, alpha_j = |w|, U[j] = w / alpha_j
     // (not when U[j] is the probed direction that replaces a vanished alpha_j: the step resumes at its second half)
     if (j != u_ready) {
-      LZ_HIP(h, launch_spmv_rect(g.A, V.B + (int64_t)j * V.ld, U.w, U.pad, h->stream));
+      LZ_HIP(h, gk_product(h, 0, V.B + (int64_t)j * V.ld, U.w, U.pad));
       LZ_TRY(orth_cgs_step(h, U, g.wk, pu, j, sm + L.proj + (int64_t)j * m, sm + L.alpha + j, pass2));
     }
     // z = A^T U[j] against V[0..j]: beta_j = |z|, V[j + 1] = z / beta_j (the coefficients are alpha_j on V[j] and rounding elsewhere)
-    LZ_HIP(h, launch_spmv_rect(g.AT, U.B + (int64_t)j * U.ld, V.w, V.pad, h->stream));
+    LZ_HIP(h, gk_product(h, 1, U.B + (int64_t)j * U.ld, V.w, V.pad));
     LZ_TRY(orth_cgs_step(h, V, g.wk, pv, j + 1, sm + L.projv, sm + L.beta + j, pass2));
     LZ_TRY(check_launch(h, "gk extend"));
   }
@@ -262,7 +334,7 @@ int lz_gk_residuals(lz_handle h, int k, const double* sigma, double* out) {
     const OrthBasis& o = gk_basis(h, side);
     int G = 0;
     for (int i = 0; i < k; ++i) {
-      LZ_HIP(h, launch_spmv_rect(side == 0 ? g.A : g.AT, in.B + (int64_t)i * in.ld, o.w, o.pad, h->stream));
+      LZ_HIP(h, gk_product(h, side, in.B + (int64_t)i * in.ld, o.w, o.pad));
       G = launch_trl_resid_diff(o.w, o.B + (int64_t)i * o.ld, o.len, dsig, i, g.wk.part, h->stream);
     }
     launch_trl_rownorm(g.wk.part, G, k, g.wk.sm + L.res + (int64_t)side * k, h->stream);
@@ -280,9 +352,13 @@ int lz_gk_spmv(lz_handle h, int transpose, const double* x, double* y) {
   double* dx = transpose ? g.U.w : g.V.w;
   double* dy = transpose ? g.V.w : g.U.w;
   const int64_t nx = transpose ? g.U.len : g.V.len, ny_pad = transpose ? g.V.pad : g.U.pad;
+  const int64_t nx_pad = transpose ? g.U.pad : g.V.pad;
   LZ_TRY(upload(h, dx, x, (size_t)nx * sizeof(double)));
   LZ_HIP(h, hipMemsetAsync(dy, 0xff, (size_t)ny_pad * sizeof(double), h->stream));  // NaN: whatever the kernel leaves unwritten shows
-  LZ_HIP(h, launch_spmv_rect(transpose ? g.AT : g.A, dx, dy, ny_pad, h->stream));
+  // ... and so does a read of x behind its length: NaN in the input's padding during the product, zero again (the walks' contract) after it
+  if (nx_pad > nx) LZ_HIP(h, hipMemsetAsync(dx + nx, 0xff, (size_t)(nx_pad - nx) * sizeof(double), h->stream));
+  LZ_HIP(h, gk_product(h, transpose, dx, dy, ny_pad));
+  if (nx_pad > nx) LZ_HIP(h, hipMemsetAsync(dx + nx, 0, (size_t)(nx_pad - nx) * sizeof(double), h->stream));
   LZ_TRY(check_launch(h, "gk spmv"));
   LZ_HIP(h, hipMemcpyAsync(y, dy, (size_t)ny_pad * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
@@ -299,9 +375,9 @@ int lz_gk_spmv_time(lz_handle h, int transpose, int reps, double* ms_out) {
   hipEvent_t a, b;
   LZ_HIP(h, hipEventCreate(&a));
   LZ_HIP(h, hipEventCreate(&b));
-  hipError_t e = launch_spmv_rect(transpose ? g.AT : g.A, dx, dy, ny_pad, h->stream);  // warm-up
+  hipError_t e = gk_product(h, transpose, dx, dy, ny_pad);  // warm-up
   if (e == hipSuccess) e = hipEventRecord(a, h->stream);
-  for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_spmv_rect(transpose ? g.AT : g.A, dx, dy, ny_pad, h->stream);
+  for (int r = 0; r < reps && e == hipSuccess; ++r) e = gk_product(h, transpose, dx, dy, ny_pad);
   if (e == hipSuccess) e = hipEventRecord(b, h->stream);
   if (e == hipSuccess) e = hipEventSynchronize(b);
   float ms = 0.f;

@@ -94,6 +94,42 @@ void rect_plan(const int32_t* rowptr, int64_t rows, int nnz_cap, bool split, std
                int* nslots);
 hipError_t launch_spmv_rect(const CsrDev& A, const double* x, double* y, int64_t rows_pad, hipStream_t s);
 
+// ---- dense rectangular product (lz_gk.hip; lz_gk_set_dense): ONE row-major copy S (R x C, stride ld: even, >= C, a padding column is
+// zero) of the caller's array, which is the tall operator Aop (stored_t == false) or its transpose.  rowdot: out[r] = sum_c S[r, c] x[c];
+// colsum: out[c] = sum_r S[r, c] u[r].  Stored tall, Aop x is rowdot and Aop^T u colsum; stored wide the other way round.  Both follow
+// launch_spmv_rect's contract: out[len .. pad) = 0, the input read at valid positions only, no atomics, one summation order per plan.
+// The form codes are lz_gk_plan's (include/lanczos_hip.h).
+enum DenseForm {
+  kRdShort = 1,  // rowdot: a lane group of rd_group lanes per row, several rows per wave (rows of up to kDenseShortMax)
+  kRdWave = 2,   // rowdot: one wave per row (gemv_row_wave)
+  kRdSeg = 3,    // rowdot: a row cut into rd_nseg segments of rd_seg doubles, a wave per segment of four rows, partials folded in segment order
+  kCsSlab = 11,  // colsum: 128-column tiles x slabs of cs_slab rows, partials folded in slab order
+  kCsOne = 12,   // colsum: the same tiles, one slab holds every row: written directly, no fold
+  kCsNarrow = 13 // colsum: cs_group lanes cover a row, 256 / cs_group rows per trip, combined through LDS; slabs folded in order
+};
+struct DenseDev {
+  double* S = nullptr;
+  int64_t R = 0, C = 0, ld = 0;
+  bool stored_t = false;
+  int rd_form = 0, rd_group = 0, rd_nseg = 0;
+  int64_t rd_seg = 0;
+  int cs_form = 0, cs_group = 0, cs_nslab = 0;
+  int64_t cs_slab = 0;
+  double* rd_part = nullptr;  // rd_nseg x round_up(R, 32)
+  double* cs_part = nullptr;  // cs_nslab x round_up(C, 32)
+};
+constexpr int kDenseTileCols = 128;  // colsum: at most this many columns per workgroup tile (a wave's 16-byte loads)
+constexpr int kDenseShortMax = 128;  // rowdot: the longest row of the lane-group form
+constexpr int kDenseShortRows = 4;   // ... and the rows a lane group has in flight
+constexpr int kDenseMediumMax = 1024;// rowdot: up to this length a wave takes four whole rows (the segment form with one segment)
+constexpr int kDenseSegRows = 4;     // rowdot segments: adjacent rows per wave (they share the loads of x)
+constexpr int kDenseSegMaxRows = 768;// ... and the row count from which one wave per row fills the device
+constexpr int kDenseFoldSub = 16;    // fold: lanes that share one output, each adding every 16th partial
+// dense_plan (host): the forms and their sizes from R, C and the CU count; force_* / seg_knob / slab_knob: tuning knobs 14, 4 and 2 (0 auto)
+void dense_plan(DenseDev& D, int force_rd, int force_cs, int seg_knob, int slab_knob);
+hipError_t launch_dense_rowdot(const DenseDev& D, const double* x, double* out, int64_t pad, hipStream_t s);
+hipError_t launch_dense_colsum(const DenseDev& D, const double* u, double* out, int64_t pad, hipStream_t s);
+
 // ---- column-blocked two-phase SpMV (lz_spmv_pb.hip): gathers out of LDS only; y bit-identical to the CSR-stream kernel
 hipError_t pb_build(const CsrDev& A, const int32_t* rowptr_host, PbDev** out, hipStream_t s, int cap_knob = 0, int groups = 0);  // *out == nullptr: not applicable; groups > 1: the A/B arm of knob 22
 void pb_free(PbDev*& pb);

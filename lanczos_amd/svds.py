@@ -102,7 +102,7 @@ class NumpyGKBackend:
 
 
 class DeviceGKBackend:
-    """The ``lz_gk_*`` calls on one ``_capi.Handle`` that already holds the rectangular matrix (``gk_set_csr``)."""
+    """The ``lz_gk_*`` calls on one ``_capi.Handle`` that already holds the rectangular matrix (``gk_set_csr`` or ``gk_set_dense``)."""
 
     def __init__(self, handle, force_second_pass=False):
         self.h = handle
@@ -237,9 +237,13 @@ def gkl(backend, shape, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None,
 
 
 def _pack(A):
-    """``A`` (SciPy sparse of any format or a dense ndarray, real) -> ``(Aop, AopT, transposed)``: float64 CSR with sorted indices and
-    summed duplicates, ``Aop`` the tall orientation (``p x q``, ``p >= q``)"""
-    if not scipy.sparse.issparse(A):
+    """``A`` (SciPy sparse of any format or a dense ndarray, real) -> ``(Aop, AopT, transposed)``, ``Aop`` the tall orientation
+    (``p x q``, ``p >= q``).  Sparse input, and a dense array with ``12 nnz < 8 size`` (its CSR stream is the smaller one): float64 CSR
+    with sorted indices and summed duplicates.  Any other dense array stays dense: ``Aop`` is a float64 *view* of the tall orientation
+    and ``AopT = Aop.T``, so one of the two is C-contiguous.  A C- or F-contiguous float64 array is not copied (an F-contiguous
+    ``M x N`` array is the C-contiguous ``N x M`` transpose); any other layout or dtype takes one ``np.ascontiguousarray``."""
+    dense = not scipy.sparse.issparse(A)
+    if dense:
         A = np.asarray(A)
         if A.ndim != 2:
             raise ValueError(f"expected a matrix (shape={A.shape})")
@@ -250,6 +254,14 @@ def _pack(A):
 
         if LanczosBase.verbose:
             print("+++ svds: float32 input is converted to float64 (the device kernels are FP64).")
+    if dense and not 12 * np.count_nonzero(A) < 8 * A.size:
+        if max(A.shape) >= 2**31:
+            raise ValueError("matrix too large for int32 indices")
+        if A.dtype != np.float64 or not (A.flags.c_contiguous or A.flags.f_contiguous):
+            A = np.ascontiguousarray(A, dtype=np.float64)
+        transposed = A.shape[0] < A.shape[1]
+        Aop = A.T if transposed else A
+        return Aop, Aop.T, transposed
     A = scipy.sparse.csr_matrix(A, dtype=np.float64)
     if A.nnz >= 2**31 or max(A.shape) >= 2**31:
         raise ValueError("matrix too large for int32 CSR indices")
@@ -305,8 +317,11 @@ def svds(A, k=6, ncv=None, tol=0, which="LM", v0=None, maxiter=None, return_sing
     with ``u`` of shape ``(M, k)``, ``s`` ascending and ``vh`` of shape ``(k, N)``.
 
     ``A``: any SciPy sparse format or a dense ndarray with ``min(M, N) >= 2``; float32 is converted to float64 with a notice, complex
-    input raises ``NotImplementedError``.  Dense input is packed as the CSR of its entries: a rectangular dense GEMV is out of scope.
-    The loop's short side carries the start vector: for ``M < N`` it runs on ``A^T`` and swaps ``u`` and ``vh`` at the end; ``v0`` has
+    input raises ``NotImplementedError``.  A dense array stays dense on the device - one row-major copy of 8 B per entry, both
+    products by dense GEMV kernels on it - unless ``12 count_nonzero(A) < 8 A.size``: then the CSR of its entries is the smaller
+    stream and it is packed as CSR like sparse input.  A C-contiguous or F-contiguous float64 array is uploaded as it lies in memory,
+    without a host copy or a transpose (an F-ordered ``M x N`` array is the C-ordered ``N x M`` transpose); any other layout or dtype
+    takes one contiguous float64 copy.  The loop's short side carries the start vector: for ``M < N`` it runs on ``A^T`` and swaps ``u`` and ``vh`` at the end; ``v0`` has
     length ``min(M, N)`` and ``ncv`` counts against ``min(M, N)``.
     ``1 <= k <= min(M, N) - 1``; ``ncv`` (default ``min(min(M, N), max(2k + 1, 20))``) must satisfy ``k + 2 <= ncv <= min(min(M, N), 128)``;
     ``which``: ``"LM"`` or ``"SM"``.  ``"SM"`` is the same loop keeping the smallest Ritz values, without harmonic extraction: it is
@@ -319,8 +334,8 @@ def svds(A, k=6, ncv=None, tol=0, which="LM", v0=None, maxiter=None, return_sing
     singular vectors (``(N, nconv)``) in ``.eigenvectors`` and the counts in ``.info``.
     A single-vector method may return fewer copies of a repeated singular value than exist: there is no probe for multiplicities.
     ``handle``: an open ``_capi.Handle`` to run on - its square matrix and thick-restart basis are left alone; ``info``: a dict that
-    receives ``matvecs`` (products with ``A`` or ``A^T``), ``cycles``, ``breakdowns``, ``anorm`` and ``residuals`` (``(2, k)``:
-    ``|A v - sigma u|`` and ``|A^T u - sigma v|``)."""
+    receives ``matvecs`` (products with ``A`` or ``A^T``), ``cycles``, ``breakdowns``, ``anorm``, ``residuals`` (``(2, k)``:
+    ``|A v - sigma u|`` and ``|A^T u - sigma v|``) and ``plan`` (``"dense"`` or ``"csr"``: how the device holds ``A``)."""
     from . import _capi
 
     h = None
@@ -328,11 +343,20 @@ def svds(A, k=6, ncv=None, tol=0, which="LM", v0=None, maxiter=None, return_sing
     def make_backend(Aop, AopT):
         nonlocal h
         h = handle if handle is not None else _capi.Handle(device_id)
-        h.gk_set_csr(Aop, AopT)
+        if isinstance(Aop, np.ndarray):  # one dense copy: whichever of the two views is C-contiguous, as it lies in memory
+            wide = not Aop.flags.c_contiguous
+            h.gk_set_dense(AopT if wide else Aop, stored_transposed=wide)
+        else:
+            h.gk_set_csr(Aop, AopT)
+        plan.append("dense" if isinstance(Aop, np.ndarray) else "csr")
         return DeviceGKBackend(h)
 
+    plan = []
     try:
-        return _svds(make_backend, A, k, ncv, tol, which, v0, maxiter, return_singular_vectors, solver, rng, random_state, options, info)
+        out = _svds(make_backend, A, k, ncv, tol, which, v0, maxiter, return_singular_vectors, solver, rng, random_state, options, info)
+        if info is not None:
+            info["plan"] = plan[0]
+        return out
     finally:
         if handle is None and h is not None:
             h.close()

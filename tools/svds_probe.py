@@ -6,6 +6,11 @@
 3. the per-step time of lz_gk_extend at (1e6, 257), m = 40, beside the byte accounting of DESIGN.md section 8b.
 
     python tools/svds_probe.py [--out profiles/r14/svds_probe.json]
+
+With --dense: the dense operator (lz_gk_set_dense) against the CSR packing of the same matrix at (1e6, 40), (2e5, 257) and
+(30000, 4096), each stored tall and wide, written to profiles/r19/svds_dense_probe.json (dense_probe below).
+
+    python tools/svds_probe.py --dense [--out profiles/r19/svds_dense_probe.json]
 """
 import argparse
 import json
@@ -39,11 +44,70 @@ def stream_ms(h, reps):
     return t["ms"] / max(t["timed_launches"], 1)
 
 
+def dense_probe(args):
+    """--dense: the dense operator (lz_gk_set_dense, arm A) against the same matrix packed as CSR (lz_gk_set_csr, arm B: what svds did
+    with a dense array before), per shape and storage: five interleaved rounds of gk_spmv_time on one handle pair, both directions;
+    then one svds(k=6) wall time on either path and the device memory each operator holds."""
+    import lanczos_amd
+
+    out = {"device": None, "reps": args.reps, "shapes": {}}
+    for p, q in ((1_000_000, 40), (200_000, 257), (30_000, 4096)):
+        A = np.random.default_rng(p + q).standard_normal((p, q))
+        rec = {"entries": p * q, "dense_bytes": 8.0 * p * q}
+        hb = _capi.Handle(0)
+        out["device"] = hb.device_name()
+        free0 = hb.device_memory()[0]
+        t0 = time.perf_counter()
+        Aop, AopT, _ = _pack(scipy.sparse.csr_matrix(A))
+        rec["csr_pack_host_s"] = time.perf_counter() - t0
+        hb.gk_set_csr(Aop, AopT)
+        rec["csr_device_mib"] = (free0 - hb.device_memory()[0]) / 2**20
+        x, u = np.random.default_rng(1).standard_normal(q), np.random.default_rng(2).standard_normal(p)
+        for storage in ("tall", "wide"):
+            ha = _capi.Handle(0)
+            free0 = ha.device_memory()[0]
+            ha.gk_set_dense(np.ascontiguousarray(A.T) if storage == "wide" else A, stored_transposed=storage == "wide")
+            srec = {"plan": list(ha.gk_plan()), "dense_device_mib": (free0 - ha.device_memory()[0]) / 2**20}
+            for name, transpose, vec in (("A_x", False, x), ("AT_u", True, u)):
+                ya, yb = ha.gk_spmv(vec, transpose=transpose), hb.gk_spmv(vec, transpose=transpose)  # (leaves vec in the work vectors)
+                n = len(vec)
+                srec[name + "_dense_vs_csr_max_rel"] = float(np.abs(ya - yb).max() / np.abs(yb).max())
+                a_ms, b_ms = [], []
+                for _ in range(5):
+                    a_ms.append(ha.gk_spmv_time(transpose, args.reps))
+                    b_ms.append(hb.gk_spmv_time(transpose, args.reps))
+                ma, mb = float(np.median(a_ms)), float(np.median(b_ms))
+                srec[name] = {"dense_us": [1e3 * t for t in a_ms], "csr_us": [1e3 * t for t in b_ms], "dense_us_median": 1e3 * ma,
+                              "csr_us_median": 1e3 * mb, "dense_share_of_8_tb_s": 8.0 * p * q / ma / 1e9 / 8.0, "csr_over_dense": mb / ma,
+                              "terms": n}
+            ha.close()
+            rec[storage] = srec
+        hb.close()
+        walls = {}
+        for name, M in (("dense", A), ("csr", None)):
+            info = {}
+            t0 = time.perf_counter()
+            s = lanczos_amd.svds(A if M is not None else scipy.sparse.csr_matrix(A), k=6, return_singular_vectors=False, info=info)
+            walls[name] = {"wall_s": time.perf_counter() - t0, "plan": info["plan"], "cycles": info["cycles"], "s_max": float(s[-1])}
+        rec["svds_k6"] = walls
+        out["shapes"][f"{p}x{q}"] = rec
+        print(json.dumps({f"{p}x{q}": rec}), flush=True)
+        del A, Aop, AopT
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r14", "svds_probe.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--dense", action="store_true", help="the dense operator against its CSR packing -> profiles/r19/svds_dense_probe.json")
     args = ap.parse_args()
+    if args.dense:
+        args.out = args.out or os.path.join("profiles", "r19", "svds_dense_probe.json")
+        return dense_probe(args)
+    args.out = args.out or os.path.join("profiles", "r14", "svds_probe.json")
     out = {"device": None, "reps": args.reps}
 
     # 1. square matrix: the rectangular kernel against the parent's CSR-stream kernel
