@@ -500,6 +500,50 @@ int lz_trl_extend_band(lz_handle h, int k, int m, double* proj_out, double* beta
 int lz_trl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
 int lz_trl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
 
+/* ---- complex Hermitian matrices (lanczos_amd.eigsh on complex input) ------------------------------------------------------------
+ * The complex twin of the thick-restart section above: a complex Hermitian matrix of its own on the handle and a basis of m + 1
+ * complex rows.  Across this ABI every complex vector or matrix is interleaved complex128 as NumPy stores it, passed as const double*
+ * of twice the length.  On the device the matrix stays interleaved (one 16-byte load per entry) and the vectors are planar: complex
+ * basis row j is two real rows of the padded, skewed stride, real part then imaginary part - so the restart is the real MFMA kernel on
+ * the real form [[Sr, Si], [-Si, Sr]] of S, which holds 2 m x 2 kk doubles in LDS and sets the limit m <= 64.
+ * Handle state: one matrix at a time.  A complex setter drops the real matrix (every real entry point - lz_run, lz_trl_*, lz_spmv_host,
+ * ... - then answers LZ_ERR_STATE "no matrix set"); lz_set_csr, lz_set_dense(_block) and lz_build_stencil3d(_block) drop the complex
+ * one.  lz_gk_* state is separate and untouched.  Hermitian-ness is assumed, never checked.  One rank only: a handle with a
+ * communicator gets LZ_ERR_STATE from the setters and from lz_ztrl_begin, which also refuses LZ_FLAG_REORTH_PARTIAL /
+ * LZ_FLAG_ONE_REDUCE.  A polynomial filter (lz_trl_set_filter / lz_trl_set_series) does not apply to the complex basis. */
+/* square n x n CSR, vals: nnz complex128 (2 nnz doubles); n, nnz < 2^31; rowptr and colidx validated as lz_set_csr does.  The product
+ * is a plain CSR kernel: a group of lanes (the widest power of two <= min(64, nnz / n), at least 1) owns a row and walks a longer row in
+ * strides; an empty row gives 0. */
+int lz_set_csr_cplx(lz_handle h, int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* colidx, const double* vals);
+/* dense n x n row-major complex128, uploaded as it lies in memory (a caller with a column-major Hermitian array holds the conjugate:
+ * it must copy).  The product is one GEMV kernel, a wave per row, that reads A once. */
+int lz_set_dense_cplx(lz_handle h, int64_t n, const double* A);
+/* y = A x on host vectors of n complex128 each: the complex twin of lz_spmv_host, and the tests' way to the product kernels */
+int lz_zspmv_host(lz_handle h, const double* x, double* y);
+/* allocate the basis for m (2 <= m <= min(64, n)) complex vectors plus the residual row, zero it, V[0] = v0 / |v0| (v0: n complex) */
+int lz_ztrl_begin(lz_handle h, int m, const double* v0);
+/* steps j = k .. m-1 without a host synchronisation: w = A V[j]; c_i = <V_i, w> = sum conj(V_i) w for i <= j (real and imaginary part
+ * from one read of V_i), w -= sum c_i V_i; a second such pass only when |w|^2 fell below half of what it was (DGKS, decided on the
+ * device; LZ_FLAG_TRL_PASS2_ALWAYS forces it); beta_j = |w|, V[j + 1] = w / beta_j.  proj_out (m x m complex, row-major): row j
+ * receives c_0 .. c_j (both passes' sums) - column j of the Hermitian projected matrix, whose diagonal entry has roundoff only in its
+ * imaginary part -, rows k .. m-1 only; beta_out[m] is real.  Either may be NULL.  Sums are formed in a fixed order: same input, same
+ * bits. */
+int lz_ztrl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out);
+/* in place: V[k] = sum_i S[i, k] V[i] for k < kk (S: m x kk complex, row-major; no conjugate is taken), then V[kk] = V[m]
+ * (1 <= kk < m).  The padding of every row is left as it is. */
+int lz_ztrl_restart(lz_handle h, int m, int kk, const double* S);
+/* V[k] = x (n complex) made orthogonal to V[0..k) by two classical Gram-Schmidt passes and normalised (0 <= k <= m).  Zeroes the whole
+ * work vector first, which also clears what a breakdown (0 / 0) left in its padding. */
+int lz_ztrl_probe(lz_handle h, int k, const double* x);
+/* the first k basis rows as an (n, k) row-major complex array, through the staging ring */
+int lz_ztrl_get_vectors(lz_handle h, int k, double* Y_out);
+/* out[i] = |A V[i] - theta[i] V[i]| for i < k and real theta: the product into the work vector, then one difference-norm kernel */
+int lz_ztrl_residuals(lz_handle h, int k, const double* theta, double* out);
+/* basis rows j0 .. j0 + count - 1 (0 <= j0, j0 + count <= m + 1) as unpadded rows of n complex numbers, host rows ld >= n complex
+ * elements apart; set_rows writes a zero padding.  Tests of the kernels. */
+int lz_ztrl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
+int lz_ztrl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

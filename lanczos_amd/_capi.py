@@ -178,6 +178,17 @@ SIGNATURES = {
     "lz_trl_rayleigh": (C.c_int, [_P, C.c_int, _D]),
     "lz_trl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_trl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_set_csr_cplx": (C.c_int, [_P, C.c_int64, C.c_int64, _I32, _I32, _D]),
+    "lz_set_dense_cplx": (C.c_int, [_P, C.c_int64, _D]),
+    "lz_zspmv_host": (C.c_int, [_P, _D, _D]),
+    "lz_ztrl_begin": (C.c_int, [_P, C.c_int, _D]),
+    "lz_ztrl_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_ztrl_restart": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_ztrl_probe": (C.c_int, [_P, C.c_int, _D]),
+    "lz_ztrl_get_vectors": (C.c_int, [_P, C.c_int, _D]),
+    "lz_ztrl_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_ztrl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_ztrl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
     "lz_gk_set_dense": (C.c_int, [_P, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int]),
     "lz_gk_plan": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -302,6 +313,11 @@ def i64ptr(a):
 
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def c128(a):
+    """C-contiguous complex128: NumPy's interleaved (re, im) doubles, which is what the ``lz_*_cplx`` / ``lz_z*`` calls take"""
+    return np.ascontiguousarray(a, dtype=np.complex128)
 
 
 class Handle:
@@ -896,6 +912,81 @@ class Handle:
     def trl_get_rows(self, j0, count):
         out = np.empty((int(count), self.padded_rows(self.rows)))
         self.check(self.lib.lz_trl_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
+        return out
+
+    # -- complex Hermitian matrices (lanczos_amd.eigsh on complex input): a matrix and a basis of their own; one matrix at a time - a
+    # complex setter drops the real matrix and the other way round
+    def set_csr_cplx(self, n, rowptr, colidx, vals):
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        colidx = np.ascontiguousarray(colidx, dtype=np.int32)
+        vals = c128(vals)
+        assert len(rowptr) == int(n) + 1 and len(colidx) == len(vals) == int(rowptr[-1])
+        self.check(self.lib.lz_set_csr_cplx(self._h, int(n), int(rowptr[-1]), i32ptr(rowptr), i32ptr(colidx), dptr(vals)))
+        self.rows = int(n)
+        self.matrix_uploads += 1
+
+    def set_dense_cplx(self, A):
+        """row-major complex128; an array that is not C-contiguous is copied (the memory of an F-ordered Hermitian array read by
+        rows is the conjugate, not the matrix)"""
+        A = c128(A)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("dense H must be square")
+        self.check(self.lib.lz_set_dense_cplx(self._h, A.shape[0], dptr(A)))
+        self.rows = A.shape[0]
+        self.matrix_uploads += 1
+
+    def zspmv(self, x):
+        """A x through the complex product kernel, host vectors"""
+        x = c128(x)
+        assert x.shape == (self.rows,)
+        y = np.empty(self.rows, dtype=np.complex128)
+        self.check(self.lib.lz_zspmv_host(self._h, dptr(x), dptr(y)))
+        return y
+
+    def ztrl_begin(self, m, v0):
+        v0 = c128(v0)
+        assert v0.shape == (self.rows,)
+        self.ztrl_m = int(m)
+        self.check(self.lib.lz_ztrl_begin(self._h, int(m), dptr(v0)))
+
+    def ztrl_extend(self, k, m):
+        """steps k .. m-1 -> (proj (m, m) complex: row j = <V_i, A V[j]> for i <= j, j >= k; beta (m,) real)"""
+        proj = np.zeros((m, m), dtype=np.complex128)
+        beta = np.zeros(m)
+        self.check(self.lib.lz_ztrl_extend(self._h, int(k), int(m), dptr(proj), dptr(beta)))
+        return proj, beta
+
+    def ztrl_restart(self, m, kk, S):
+        S = c128(S)
+        assert S.shape == (m, kk)
+        self.check(self.lib.lz_ztrl_restart(self._h, int(m), int(kk), dptr(S)))
+
+    def ztrl_probe(self, k, x):
+        x = c128(x)
+        assert x.shape == (self.rows,)
+        self.check(self.lib.lz_ztrl_probe(self._h, int(k), dptr(x)))
+
+    def ztrl_get_vectors(self, k):
+        Y = np.empty((self.rows, int(k)), dtype=np.complex128)
+        self.check(self.lib.lz_ztrl_get_vectors(self._h, int(k), dptr(Y)))
+        return Y
+
+    def ztrl_residuals(self, k, theta):
+        th = f64(theta)[: int(k)]
+        assert th.shape == (int(k),)
+        out = np.empty(int(k))
+        self.check(self.lib.lz_ztrl_residuals(self._h, int(k), dptr(th), dptr(out)))
+        return out
+
+    def ztrl_set_rows(self, j0, rows):
+        """basis rows j0 .. j0 + len(rows) - 1 from ``rows`` (count, n) complex, unpadded"""
+        rows = c128(rows)
+        assert rows.ndim == 2 and rows.shape[1] == self.rows
+        self.check(self.lib.lz_ztrl_set_rows(self._h, int(j0), rows.shape[0], dptr(rows), rows.shape[1]))
+
+    def ztrl_get_rows(self, j0, count):
+        out = np.empty((int(count), self.rows), dtype=np.complex128)
+        self.check(self.lib.lz_ztrl_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
         return out
 
     # -- Golub-Kahan-Lanczos (lanczos_amd.svds): a rectangular operator and two bases of their own; side 0 = U (length p), 1 = V (length q)

@@ -131,7 +131,10 @@ def _native_arrays(H):
 
 def _pack_matrix(H):
     """-> ("csr", rowptr, colidx, vals) or ("dense", A).  Keeps the stored entry
-    order of a CSR input (the per-row summation order then equals SciPy's)."""
+    order of a CSR input (the per-row summation order then equals SciPy's).
+    Complex input raises: a conversion to float64 would drop the imaginary part."""
+    if np.dtype(getattr(H, "dtype", np.float64)).kind == "c" or (not hasattr(H, "dtype") and np.iscomplexobj(H)):
+        raise NotImplementedError("complex input: use lanczos_amd.eigsh")
     if scipy.sparse.issparse(H):
         A = H if H.format == "csr" else H.tocsr()
         if A.dtype != np.float64:

@@ -515,6 +515,7 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_tW);
   orth_free(h->trl_wk);
   gk_free(h);
+  z_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

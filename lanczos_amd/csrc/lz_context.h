@@ -1,5 +1,5 @@
 // Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip,
-// lz_orth.hip, lz_trl_api.hip, lz_gk_api.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// lz_orth.hip, lz_trl_api.hip, lz_gk_api.hip, lz_zspmv.hip, lz_ztrl_api.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -92,6 +92,24 @@ struct GkState {
   OrthBasis U;       // the long side (len p): m + 1 rows (row m stays zero: launch_trl_restart copies it to row kk); w = A V[j]
   OrthBasis V;       // the short side (len q): m + 1 rows; w = z = A^T U[j]
   OrthWork wk;       // small arrays: see gk_small_layout in lz_gk_api.hip
+};
+
+// Complex Hermitian operator and its thick-restart basis (lz_zspmv.hip, lz_ztrl_api.hip; lanczos_amd.eigsh on complex input).  While a
+// complex matrix is set h->kind stays 0, so every real entry point answers "no matrix set"; h->rows / h->rows_pad are the complex
+// matrix' n and its padding.  Layout: planar.  Complex basis row j is the real rows 2 j (real part) and 2 j + 1 (imaginary part) of B,
+// the work vector is w (real part) and w + ld (imaginary part); only the C ABI speaks interleaved complex128.
+struct ZState {
+  int kind = 0;  // 0 none, 1 CSR, 2 dense
+  int64_t n = 0, nnz = 0;
+  int32_t* rowptr = nullptr;
+  int32_t* colidx = nullptr;
+  double* vals = nullptr;   // CSR: 2 nnz doubles (re, im interleaved); dense: 2 n n, row-major
+  int group = 1;            // lanes per row of the CSR product (a power of two <= 64, from the mean row length)
+  double* xtmp = nullptr;   // lz_zspmv_host: x and y in planar form (4 padded vectors)
+  int64_t xtmp_pad = 0;
+  OrthBasis B;              // 2 (m + 1) real rows; w: 2 ld doubles
+  OrthWork wk;              // small arrays: see ztrl_small_layout in lz_ztrl_api.hip
+  int m = 0;
 };
 
 struct lz_context {
@@ -224,6 +242,7 @@ struct lz_context {
   OrthWork trl_wk;             // small arrays: see trl_small_layout in lz_trl_api.hip
   TrlPoly poly;  // none, the Chebyshev filter or the Chebyshev series
   GkState gk;    // Golub-Kahan-Lanczos (lz_gk_*): freed by gk_free
+  ZState z;      // complex Hermitian matrix and its thick-restart basis (lz_set_*_cplx, lz_ztrl_*): freed by z_free
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -330,6 +349,13 @@ int upload_csr(lz_handle h, CsrDev& A, const char* who, int64_t rows, int64_t nc
 
 // Golub-Kahan-Lanczos state (lz_gk_api.hip): releases everything h->gk owns (lz_destroy)
 void gk_free(lz_handle h);
+
+// complex Hermitian state (lz_zspmv.hip).  z_drop_matrix: what every real matrix setter calls - the complex matrix is gone (its basis
+// stays allocated for the next one); z_free: everything h->z owns (lz_destroy)
+int z_drop_matrix(lz_handle h);
+void z_free(lz_handle h);
+// w = A x on the complex matrix, planar vectors (real part at x / y, imaginary part at x + ld / y + ld); writes n entries of each part
+void z_matvec(lz_handle h, const double* x, double* y, int64_t ld);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_* and lz_gk_* both do with an OrthBasis and its OrthWork
 QtwPlan orth_plan(lz_handle h, const OrthBasis& b);

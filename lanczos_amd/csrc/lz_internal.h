@@ -428,6 +428,25 @@ void launch_cheb_step(double* wz, const double* y, const double* x, const double
 void launch_cheb_series_step(double* wz, const double* y, const double* x, const double* acc_in, double* acc_out, const double* mu, int i,
                              int last, double inv_e, double c, int64_t rows, int64_t len, hipStream_t s);
 
+// ---- complex Hermitian operator (lz_zspmv.hip) and its Gram-Schmidt kernels (lz_ztrl.hip); C ABI in lz_ztrl_api.hip ----
+// Vectors are planar: the real part at p, the imaginary part at p + ld.  Matrix values are interleaved complex128 (16 bytes an entry).
+// y = A x, CSR: a group of `group` lanes (a power of two <= 64) owns a row and walks it in strides of the group; empty rows give 0
+void launch_zspmv_csr(const int32_t* rowptr, const int32_t* colidx, const double* vals, int64_t rows, int group, const double* xr,
+                      const double* xi, double* yr, double* yi, hipStream_t s);
+// y = A x, dense row-major n x n: one wave per row, A read once
+void launch_zgemv(const double* A, int64_t n, const double* xr, const double* xi, double* yr, double* yi, hipStream_t s);
+constexpr int kZMaxRows = 65;  // complex rows of a basis (m + 1, m <= 64): the restart's real form holds 2 m x 2 kk doubles in LDS
+// part[(2 i + 0 / 1) * G + b] = block b's share of Re / Im <V_i, w> = sum conj(V_i) w for i < nb, and of w^H w / 0 at i = nb (the self
+// slot); launch_final_rows(part, 2 (nb + 1), G, c) then gives c interleaved.  V: complex row i = real rows 2 i, 2 i + 1 (ldv apart);
+// w: real part, imaginary part at w + ldv.  len: the padded length.  Returns G = zdots_blocks(len).  gate as launch_trl_cgs.
+int zdots_blocks(int64_t len);
+int launch_zdots(const double* V, int64_t ldv, int64_t len, int nb, const double* w, double* part, const int* gate, hipStream_t s);
+// w -= sum_{i < nb} c_i V_i (c interleaved complex), part[b] = block b's share of |w|^2; returns the number of partials (zcgs_blocks(len))
+int zcgs_blocks(int64_t len);
+int launch_zcgs(const double* V, int64_t ldv, int64_t len, int nb, const double* c, double* w, double* part, const int* gate, hipStream_t s);
+// squares of |y - theta[i] x| over n complex entries (planar, parts ld apart), block partials at part[i * G + b]; returns G
+int launch_zresid_diff(const double* y, const double* x, int64_t ld, int64_t n, const double* theta, int i, double* part, hipStream_t s);
+
 // ---- small-problem engine (lz_small.hip): the whole run as one cooperative kernel
 struct SmallArgs {
   int kind;  // 1 CSR, 2 dense

@@ -209,6 +209,7 @@ int lz_set_csr(lz_handle h, int64_t M_global, int64_t row0, int64_t rows_local, 
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   h->kind = 0;
   h->poly.clear();  // a new matrix drops the polynomial of the thick-restart solver
+  LZ_TRY(z_drop_matrix(h));  // ... and a complex matrix (lz_set_csr_cplx / lz_set_dense_cplx)
   LZ_TRY(dev_free(h, h->d_dense));
   LZ_TRY(dev_free(h, h->d_V));  // a new matrix invalidates the basis
   h->n = 0;
@@ -264,6 +265,7 @@ int lz_build_stencil3d_block(lz_handle h, int Nx, int Ny, int Nz, int points, do
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   h->kind = 0;
   h->poly.clear();  // a new matrix drops the polynomial of the thick-restart solver
+  LZ_TRY(z_drop_matrix(h));  // ... and a complex matrix (lz_set_csr_cplx / lz_set_dense_cplx)
   LZ_TRY(dev_free(h, h->d_dense));
   LZ_TRY(dev_free(h, h->d_V));
   h->n = 0;
@@ -354,6 +356,7 @@ int lz_set_dense_block(lz_handle h, int64_t M_global, int64_t row0, int64_t rows
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   h->kind = 0;
   h->poly.clear();  // a new matrix drops the polynomial of the thick-restart solver
+  LZ_TRY(z_drop_matrix(h));  // ... and a complex matrix (lz_set_csr_cplx / lz_set_dense_cplx)
   LZ_TRY(dev_free(h, h->d_V));
   h->n = 0;
   const int64_t lda = (ncols_ext + 1) & ~(int64_t)1;

@@ -20,6 +20,10 @@ Band.  ``block_size=b`` runs the loop in Ruhe's band form (``trl_band``): ``b`` 
 copies of an eigenvalue up to multiplicity ``b`` appear without a probe and the device orthogonalises ``b`` vectors per walk over the
 basis; the bookkeeping stays that of single rows.
 
+Complex.  A complex Hermitian ``A`` runs the same loop (``trl``) on a complex backend (``lz_ztrl_*``): ``T`` is Hermitian, the small
+problem is ``eigh((T + T^H) / 2)``, the restart's arrow ``T[kk, :kk] = beta S[m - 1, keep]`` has its conjugate in the column, and
+start and probe vectors are complex.  For a real backend nothing changes, bit for bit.  ``ncv <= 64`` there.
+
 Breakdown.  When a ``beta`` falls below ``10 eps max|theta|`` the Krylov space is invariant: the loop goes on from a fresh random
 vector orthogonal to the basis with a zero coupling instead of dividing by ``beta``.
 """
@@ -32,6 +36,7 @@ from scipy.sparse.linalg import ArpackNoConvergence
 _WHICH = ("LM", "SM", "LA", "SA", "BE")
 _EPS = np.finfo(np.float64).eps
 _MAX_NCV = 128  # rows of the restart's S held in LDS (lz_trl.hip)
+_MAX_NCV_COMPLEX = 64  # complex A: the restart runs on the real form of S, twice the rows and columns in the same LDS (lz_ztrl_api.hip)
 _SEED = 0x5EED  # the private generator of start and probe vectors: the same call gives the same bits
 
 
@@ -145,6 +150,56 @@ class NumpyBackend:
         return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
 
 
+class ComplexNumpyBackend:
+    """The calls of the complex device backend (``lz_ztrl_*``) in NumPy, for a complex Hermitian ``A``: what the host tests drive the
+    outer loop with.  ``<x, y> = sum conj(x) y`` throughout."""
+
+    is_complex = True
+
+    def __init__(self, A, force_second_pass=False):
+        self.A = A
+        self.n = A.shape[0]
+        self.force = force_second_pass
+
+    def begin(self, m, v0):
+        self.V = np.zeros((m + 1, self.n), dtype=np.complex128)
+        self.V[0] = v0 / np.linalg.norm(v0)
+
+    def _cgs(self, w, j):
+        c = self.V[: j + 1].conj() @ w
+        return w - c @ self.V[: j + 1], c
+
+    def extend(self, k, m):
+        proj = np.zeros((m, m), dtype=np.complex128)
+        beta = np.zeros(m)
+        for j in range(k, m):
+            w = self.A @ self.V[j]
+            w0 = np.vdot(w, w).real
+            w, c = self._cgs(w, j)
+            if self.force or np.vdot(w, w).real < 0.5 * w0:
+                w, c2 = self._cgs(w, j)
+                c = c + c2
+            proj[j, : j + 1] = c
+            beta[j] = np.linalg.norm(w)
+            self.V[j + 1] = w / beta[j]
+        return proj, beta
+
+    def restart(self, m, kk, S):
+        self.V[:kk] = S.T @ self.V[:m]
+        self.V[kk] = self.V[m].copy()
+
+    def probe(self, k, x):
+        for _ in range(2):
+            x = x - (self.V[:k].conj() @ x) @ self.V[:k]
+        self.V[k] = x / np.linalg.norm(x)
+
+    def get_vectors(self, k):
+        return self.V[:k].T.copy()
+
+    def residuals(self, k, theta):
+        return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
+
+
 def _check_problem(n, k, which, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
     """SciPy's argument errors for everything but ``ncv``"""
     if M is not None or sigma is not None or Minv is not None or OPinv is not None:
@@ -161,34 +216,47 @@ def _check_problem(n, k, which, M=None, sigma=None, Minv=None, OPinv=None, mode=
         raise TypeError(f"k >= N for an N x N matrix (k={k}, N={n}): reduce k")
 
 
-def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
-    """SciPy's argument errors, plus this solver's own limits.  Returns ncv."""
+def check_args(n, k, which, ncv, M=None, sigma=None, Minv=None, OPinv=None, mode="normal", complex_A=False):
+    """SciPy's argument errors, plus this solver's own limits.  Returns ncv.  ``complex_A``: the cap of the complex solver."""
     _check_problem(n, k, which, M, sigma, Minv, OPinv, mode)
     if ncv is None:
         ncv = min(n, max(2 * k + 1, 20))
     ncv = min(int(ncv), n)  # (as SciPy does)
+    if complex_A and not k + 3 <= ncv <= min(n, _MAX_NCV_COMPLEX):
+        raise ValueError(f"ncv must be k+3<=ncv<=min(n, {_MAX_NCV_COMPLEX}) for a complex Hermitian matrix, ncv={ncv} (the complex cap: the "
+                         f"restart kernel holds the real form of S, 2 ncv rows, where a real matrix may have {_MAX_NCV}; pass a smaller ncv or k)")
     if not k + 3 <= ncv <= min(n, _MAX_NCV):
         raise ValueError(f"ncv must be k+3<=ncv<=min(n, {_MAX_NCV}), ncv={ncv} (stricter than SciPy's k<ncv<=n: the thick restart keeps "
                          "two spare basis rows and one more for the probe direction)")
     return ncv
 
 
-def _start(n, tol, v0, rng):
-    """``(rng, tol_eff, v0)``: the generator, the effective tolerance and the checked start vector (drawn only when none is given)"""
+def _start(n, tol, v0, rng, cplx=False):
+    """``(rng, tol_eff, v0)``: the generator, the effective tolerance and the checked start vector (drawn only when none is given;
+    ``cplx``: real and imaginary part, in that order, from the same generator)"""
     rng = np.random.default_rng(_SEED) if rng is None else rng
     tol_eff = float(tol) if tol > 0 else _EPS
-    v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
+    if cplx:
+        v0 = rng.uniform(-1.0, 1.0, n) + 1j * rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.complex128).reshape(-1)
+    else:
+        v0 = rng.uniform(-1.0, 1.0, n) if v0 is None else np.asarray(v0, dtype=np.float64).reshape(-1)
     if v0.shape != (n,) or not np.linalg.norm(v0) > 0:
         raise ValueError("v0 must be a non-zero vector of length n")
     return rng, tol_eff, v0
 
 
+def _probe_vector(rng, n, cplx):
+    """the random direction of a probe or of the fresh start behind a breakdown"""
+    return rng.standard_normal(n) + 1j * rng.standard_normal(n) if cplx else rng.standard_normal(n)
+
+
 def _fill(T, proj, beta, j0, j1, couplings=True):
     """columns ``j0 .. j1 - 1`` of the projected matrix ``T`` (and their rows) from what ``extend`` returned; ``couplings``: the
-    ``beta`` beside the diagonal as well"""
+    ``beta`` beside the diagonal as well.  A complex ``T`` is Hermitian: ``proj[j, i] = <V_i, A V_j>`` is column ``j``, the row its conjugate."""
+    cplx = np.iscomplexobj(T)
     for j in range(j0, j1):
         T[: j + 1, j] = proj[j, : j + 1]
-        T[j, : j + 1] = proj[j, : j + 1]
+        T[j, : j + 1] = np.conj(proj[j, : j + 1]) if cplx else proj[j, : j + 1]
         if couplings and j + 1 < len(T):
             T[j + 1, j] = T[j, j + 1] = beta[j]
 
@@ -198,11 +266,13 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
 
     Returns ``(theta, info)``: the ``k`` wanted eigenvalues in ascending order (``backend.V[0..k)`` then holds their vectors) and
     ``{"matvecs", "cycles", "probes", "breakdowns", "anorm"}`` (anorm: max|theta| over the run, the norm estimate).  Raises ``ArpackNoConvergence`` after ``maxiter`` cycles."""
-    m = check_args(n, k, which, ncv)
+    cplx = bool(getattr(backend, "is_complex", False))  # a complex Hermitian backend: T Hermitian, complex start and probe vectors
+    dt = np.complex128 if cplx else np.float64
+    m = check_args(n, k, which, ncv, complex_A=cplx)
     maxiter = n * 10 if maxiter is None else int(maxiter)
-    rng, tol_eff, v0 = _start(n, tol, v0, rng)
+    rng, tol_eff, v0 = _start(n, tol, v0, rng, cplx)
     backend.begin(m, v0)
-    T = np.zeros((m, m))
+    T = np.zeros((m, m), dtype=dt)
     kcur, nw, last = 0, k, None
     anorm = 0.0
     info = {"matvecs": 0, "cycles": 0, "probes": 0, "breakdowns": 0}
@@ -221,11 +291,11 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             T[jb + 1:, :] = 0.0
             T[:, jb + 1:] = 0.0
             _fill(T, proj, beta, j0, jb + 1, couplings=False)
-            backend.probe(jb + 1, rng.standard_normal(n))
+            backend.probe(jb + 1, _probe_vector(rng, n, cplx))
             j0 = jb + 1
         info["cycles"] += 1
         b_last = beta[m - 1]
-        theta, S = np.linalg.eigh((T + T.T) / 2)
+        theta, S = np.linalg.eigh((T + T.conj().T) / 2 if cplx else (T + T.T) / 2)
         anorm = max(np.abs(theta).max(), anorm)
         res = b_last * np.abs(S[m - 1])
         order = _order(theta, which)
@@ -243,7 +313,7 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
                 return theta[sel], info
         if info["cycles"] >= maxiter:
             conv = sorted((i for i in order[:k] if ok[i]), key=lambda i: theta[i])
-            vecs = np.zeros((n, 0))
+            vecs = np.zeros((n, 0), dtype=dt)
             if conv:
                 backend.restart(m, len(conv), np.ascontiguousarray(S[:, conv]))
                 vecs = backend.get_vectors(len(conv))
@@ -254,9 +324,9 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
         if done:
             last = cur
             backend.restart(m, nw, np.ascontiguousarray(S[:, want]))
-            backend.probe(nw, rng.standard_normal(n))
+            backend.probe(nw, _probe_vector(rng, n, cplx))
             info["probes"] += 1
-            T = np.zeros((m, m))
+            T = np.zeros((m, m), dtype=dt)
             T[np.arange(nw), np.arange(nw)] = theta[want]
             kcur, nw = nw, min(nw + 1, m - 3)
         else:
@@ -264,10 +334,13 @@ def trl(backend, n, k, which="LM", ncv=None, maxiter=None, tol=0.0, v0=None, pro
             kk = min(m - 2, nw + max(nconv, (m - nw) // 2))
             keep = order[:kk]
             backend.restart(m, kk, np.ascontiguousarray(S[:, keep]))
-            T = np.zeros((m, m))
+            T = np.zeros((m, m), dtype=dt)
             T[np.arange(kk), np.arange(kk)] = theta[keep]
             if dead:
-                backend.probe(kk, rng.standard_normal(n))
+                backend.probe(kk, _probe_vector(rng, n, cplx))
+            elif cplx:  # A Y_k = theta_k Y_k + beta S[m-1, k] V[m]: the arrow's row, its conjugate in the column
+                T[kk, :kk] = b_last * S[m - 1, keep]
+                T[:kk, kk] = np.conj(T[kk, :kk])
             else:
                 T[:kk, kk] = T[kk, :kk] = b_last * S[m - 1, keep]
             kcur = kk
@@ -847,6 +920,75 @@ class DeviceBackend:
         return self.h.trl_rayleigh(k)
 
 
+class ComplexDeviceBackend:
+    """The ``lz_ztrl_*`` calls on one ``_capi.Handle`` that already holds the complex Hermitian matrix."""
+
+    is_complex = True
+
+    def __init__(self, handle, n, force_second_pass=False):
+        self.h = handle
+        self.n = n
+        if force_second_pass:
+            from ._capi import FLAG_TRL_PASS2_ALWAYS
+
+            handle.set_options(FLAG_TRL_PASS2_ALWAYS)
+
+    def begin(self, m, v0):
+        self.h.ztrl_begin(m, v0)
+
+    def extend(self, k, m):
+        return self.h.ztrl_extend(k, m)
+
+    def restart(self, m, kk, S):
+        self.h.ztrl_restart(m, kk, S)
+
+    def probe(self, k, x):
+        self.h.ztrl_probe(k, x)
+
+    def get_vectors(self, k):
+        return self.h.ztrl_get_vectors(k)
+
+    def residuals(self, k, theta):
+        return self.h.ztrl_residuals(k, theta)
+
+
+def is_complex_matrix(A):
+    """does ``A`` (SciPy sparse or ndarray) have a complex dtype?  That alone sends ``eigsh`` down the complex path."""
+    return np.dtype(getattr(A, "dtype", np.float64)).kind == "c"
+
+
+def upload_complex_matrix(h, A):
+    """complex ``A`` (SciPy sparse of any format or a dense ndarray; complex64 is converted) -> the handle; returns n.  Dense input that
+    is not C-contiguous is copied: the memory of an F-ordered Hermitian array, read by rows, is the conjugate."""
+    if scipy.sparse.issparse(A):
+        A = A.tocsr().astype(np.complex128, copy=False)
+        if A.nnz >= 2**31 or A.shape[0] >= 2**31:
+            raise ValueError("matrix too large for int32 CSR indices")
+        h.set_csr_cplx(A.shape[0], A.indptr, A.indices, A.data)
+    else:
+        h.set_dense_cplx(np.ascontiguousarray(A, dtype=np.complex128))
+    return int(A.shape[0])
+
+
+def _eigsh_complex(A, n, k, which, v0, ncv, maxiter, tol, return_eigenvectors, device_id, handle, info):
+    """``eigsh`` for a complex Hermitian ``A``: the same outer loop on the complex device backend"""
+    from . import _capi
+
+    h = handle if handle is not None else _capi.Handle(device_id)
+    try:
+        upload_complex_matrix(h, A)
+        theta, run = trl(ComplexDeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+        if info is not None:
+            info.update(run)
+            info["residuals"] = h.ztrl_residuals(k, theta)
+        if not return_eigenvectors:
+            return theta
+        return theta, h.ztrl_get_vectors(k)
+    finally:
+        if handle is None:
+            h.close()
+
+
 def upload_matrix(h, A):
     """A (SciPy sparse of any format, dense ndarray, ``synthetic.CSR`` or ``StencilOperator``) -> the handle; returns n."""
     if hasattr(A, "dims") and hasattr(A, "points"):  # StencilOperator: assembled on the device, as LanczosBase._upload_matrix does
@@ -869,8 +1011,13 @@ def upload_matrix(h, A):
 
 def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=None, tol=0, return_eigenvectors=True, Minv=None,
           OPinv=None, mode="normal", device_id=0, handle=None, info=None, filter_degree=None, block_size=None):
-    """Find ``k`` eigenvalues and eigenvectors of the real symmetric matrix ``A`` - ``scipy.sparse.linalg.eigsh``'s signature and
-    defaults, solved by thick-restart Lanczos on the GPU.
+    """Find ``k`` eigenvalues and eigenvectors of the real symmetric or complex Hermitian matrix ``A`` -
+    ``scipy.sparse.linalg.eigsh``'s signature and defaults, solved by thick-restart Lanczos on the GPU.
+
+    Complex ``A`` (a SciPy sparse matrix or a dense ndarray of a complex dtype; complex64 is converted; Hermitian-ness is assumed, not
+    checked, as SciPy does): the same loop on the complex kernels (``lz_ztrl_*``).  Eigenvalues come back ascending as float64,
+    eigenvectors as ``(n, k)`` complex128; ``v0`` may be real or complex; ``k + 3 <= ncv <= min(n, 64)``, and a default ``ncv`` above 64
+    raises ``ValueError``; ``filter_degree``, ``sigma`` and ``block_size`` raise ``NotImplementedError``.  Everything else below holds.
 
     ``which``: ``"LM"``, ``"SM"``, ``"LA"`` or ``"SA"`` (``"BE"``, ``M``, ``Minv``, ``OPinv``, other modes and ``sigma`` without
     ``filter_degree`` raise ``NotImplementedError``).  ``ncv`` (default ``min(n, max(2k + 1, 20))``) must satisfy ``k + 3 <= ncv <= min(n, 128)``.
@@ -897,6 +1044,15 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
     n = int(A.shape[0])
     if len(A.shape) != 2 or A.shape[1] != n:
         raise ValueError(f"expected square matrix (shape={A.shape})")
+    if is_complex_matrix(A):
+        if filter_degree is not None:
+            raise NotImplementedError("filter_degree with a complex matrix: the polynomial filter is built for the real basis only")
+        if sigma is not None:
+            raise NotImplementedError("sigma with a complex matrix: there is no shift-invert and no interior filter on the complex path")
+        if block_size is not None:
+            raise NotImplementedError("block_size with a complex matrix: the band form is built for the real basis only")
+        check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode, complex_A=True)
+        return _eigsh_complex(A, n, k, which, v0, ncv, maxiter, tol, return_eigenvectors, device_id, handle, info)
     if block_size is not None:
         check_block_size(block_size)
         if sigma is not None:

@@ -47,6 +47,8 @@ class IrrLanczos(LanczosBase):
             # passes dtype).
             print("+++ dtype=%s: inputs rounded to %s, recurrence in float64 on the MI355X, results published as %s." % (dtype.name, dtype.name, dtype.name))
         M = self.M
+        if np.iscomplexobj(self.H):  # (the conversions below would drop the imaginary part before _pack_matrix could refuse it)
+            raise NotImplementedError("complex input: use lanczos_amd.eigsh")
         H = scipy.sparse.csr_matrix(scipy.sparse.csr_matrix(self.H, dtype=dtype), dtype=np.float64)  # :91
         HT = scipy.sparse.csr_matrix(H.transpose(), dtype=np.float64)                                # :92
         np.random.seed(seed)

@@ -21,6 +21,7 @@ __all__ = [
     "random_graph_laplacian",
     "dense_symmetric",
     "dense_symmetric_hashed",
+    "hofstadter",
     "deuteron_potential",
     "DeuteronPotential",
     "reference_start_vector",
@@ -122,6 +123,39 @@ def dense_symmetric(M, seed=0):
     """Config C1: ``A = standard_normal((M, M)); (A + A.T) / 2`` with ``default_rng(seed)``."""
     A = np.random.default_rng(seed).standard_normal((M, M))
     return (A + A.T) / 2
+
+
+def hofstadter(Lx, Ly, alpha, periodic=False, disorder=0.0, seed=0):
+    """The Harper-Hofstadter hopping Hamiltonian on an ``Lx x Ly`` lattice as a complex128 SciPy CSR matrix (Hermitian): site
+    ``(x, y)`` has index ``x * Ly + y``, every x-bond carries ``-1`` and the y-bond ``(x, y) -> (x, y + 1)`` the Peierls phase
+    ``-exp(2 pi i alpha x)`` (its conjugate on the way back), ``alpha`` flux quanta per plaquette in the Landau gauge.  ``periodic``
+    wraps both directions (the phases close when ``alpha * Lx`` is an integer).  ``disorder = W``: uniform on-site energies in
+    ``[-W, W]`` from ``default_rng(seed)``."""
+    import scipy.sparse
+
+    Lx, Ly = int(Lx), int(Ly)
+    n = Lx * Ly
+    x, y = np.divmod(np.arange(n, dtype=np.int64), Ly)
+    rows, cols, vals = [], [], []
+    keep = np.ones(n, dtype=bool) if periodic else x + 1 < Lx  # x-bonds
+    i, j = np.flatnonzero(keep), (((x + 1) % Lx) * Ly + y)[keep]
+    rows += [i, j]
+    cols += [j, i]
+    vals += [np.full(len(i), -1.0 + 0.0j), np.full(len(i), -1.0 + 0.0j)]
+    keep = np.ones(n, dtype=bool) if periodic else y + 1 < Ly  # y-bonds: <x, y + 1| H |x, y> = -exp(2 pi i alpha x)
+    i, j = np.flatnonzero(keep), (x * Ly + (y + 1) % Ly)[keep]
+    ph = np.exp(2j * np.pi * alpha * x[keep])
+    rows += [j, i]
+    cols += [i, j]
+    vals += [-ph, -np.conj(ph)]
+    if disorder:
+        d = np.arange(n, dtype=np.int64)
+        rows.append(d)
+        cols.append(d)
+        vals.append(disorder * np.random.default_rng(seed).uniform(-1.0, 1.0, n) + 0.0j)
+    A = scipy.sparse.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n), dtype=np.complex128).tocsr()
+    A.sort_indices()
+    return A
 
 
 def dense_symmetric_hashed(M, rows=None, seed=0):
