@@ -1,5 +1,5 @@
-// Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip,
-// lz_orth.hip, lz_trl_api.hip, lz_gk_api.hip, lz_zspmv.hip, lz_ztrl_api.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip, lz_orth.hip and the
+// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <system_error>
 #include <thread>
@@ -55,14 +56,18 @@ struct TrlPoly {
 };
 
 // The Gram-Schmidt basis layer under the restart solvers (lz_orth.hip).  OrthBasis: one orthonormal row basis and the work vector that is
-// orthogonalised against it and stored as its next row.  h->trl follows the square matrix set last: trl_state (lz_trl_api.hip), which
+// orthogonalised against it and stored as its next row.  planes == 1: real.  planes == 2: planar complex - row j is the real rows 2 j
+// (real part) and 2 j + 1 (imaginary part) of B, w is two rows ld apart; only the C ABI speaks interleaved complex128.  nrows counts
+// rows of the basis' kind (complex rows of a complex basis: B holds planes * nrows real rows), and so does every row index the layer takes.
+// h->trl follows the square matrix set last: trl_state (lz_trl_api.hip), which
 // every lz_trl_* entry point behind lz_trl_begin calls first, sets its len and pad from h->rows / h->rows_pad on every call; code that
 // uses h->trl without going through trl_state or trl_alloc reads the lengths of the last call that did.
 struct OrthBasis {
-  double* B = nullptr;  // nrows rows, ld doubles apart
-  double* w = nullptr;  // ld doubles; [len, ld) is zero whenever a walk reads it: the walks stream pad doubles, the products write len
+  double* B = nullptr;  // planes * nrows real rows, ld doubles apart
+  double* w = nullptr;  // planes * ld doubles; [len, ld) of each is zero whenever a walk reads it: the walks stream pad doubles, the products write len
   int64_t len = 0, pad = 0, ld = 0;  // the vectors' length, padded to kPadDoubles, and the (skewed) row stride
   int nrows = 0;        // sizes the walks' plan (orth_plan) and the head of the small arrays (orth_small_head)
+  int planes = 1;       // 1: real, 2: planar complex
 };
 // What the bases of one solver share: the small arrays (head: OrthSmallHead, the rest the solver's own), the gate and the partials.
 struct OrthWork {
@@ -71,12 +76,13 @@ struct OrthWork {
   double* part = nullptr;  // partials of the passes, the products and the residual norms
   size_t part_cap = 0;
 };
-// c of pass 1 and of pass 2 (row nrows is the self slot), nrm2 + a scratch slot; the solver's own arrays start at end
+// c of pass 1 and of pass 2 (planes doubles per row, interleaved; row nrows is the self slot), nrm2 + a scratch slot; the solver's own
+// arrays start at end
 struct OrthSmallHead {
   int64_t c1, c2, nrm2, end;
 };
-inline OrthSmallHead orth_small_head(int nrows) {
-  const int64_t cl = lz::qtw_ldp(nrows + 1) + 16;
+inline OrthSmallHead orth_small_head(int nrows, int planes = 1) {
+  const int64_t cl = lz::qtw_ldp(planes * (nrows + 1)) + 16;
   return {0, cl, 2 * cl, 2 * cl + 8};
 }
 
@@ -96,8 +102,8 @@ struct GkState {
 
 // Complex Hermitian operator and its thick-restart basis (lz_zspmv.hip, lz_ztrl_api.hip; lanczos_amd.eigsh on complex input).  While a
 // complex matrix is set h->kind stays 0, so every real entry point answers "no matrix set"; h->rows / h->rows_pad are the complex
-// matrix' n and its padding.  Layout: planar.  Complex basis row j is the real rows 2 j (real part) and 2 j + 1 (imaginary part) of B,
-// the work vector is w (real part) and w + ld (imaginary part); only the C ABI speaks interleaved complex128.
+// matrix' n and its padding.  The basis is a two-plane OrthBasis of its own, separate from h->trl: a real and a complex basis coexist
+// on a handle across matrix swaps.
 struct ZState {
   int kind = 0;  // 0 none, 1 CSR, 2 dense
   int64_t n = 0, nnz = 0;
@@ -107,7 +113,7 @@ struct ZState {
   int group = 1;            // lanes per row of the CSR product (a power of two <= 64, from the mean row length)
   double* xtmp = nullptr;   // lz_zspmv_host: x and y in planar form (4 padded vectors)
   int64_t xtmp_pad = 0;
-  OrthBasis B;              // 2 (m + 1) real rows; w: 2 ld doubles
+  OrthBasis B;              // planes == 2, m + 1 complex rows
   OrthWork wk;              // small arrays: see ztrl_small_layout in lz_ztrl_api.hip
   int m = 0;
 };
@@ -357,26 +363,35 @@ void z_free(lz_handle h);
 // w = A x on the complex matrix, planar vectors (real part at x / y, imaginary part at x + ld / y + ld); writes n entries of each part
 void z_matvec(lz_handle h, const double* x, double* y, int64_t ld);
 
-// Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_* and lz_gk_* both do with an OrthBasis and its OrthWork
-QtwPlan orth_plan(lz_handle h, const OrthBasis& b);
-// c[0 .. n) = B[0 .. n) . w, c[n] = w . w (the self slot); gate: the launches return at once where gate[0] == 0
+// Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
+// its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.
+QtwPlan orth_plan(lz_handle h, const OrthBasis& b);  // (a complex basis' walks plan themselves: an empty plan)
+// c[0 .. n) = <B[0 .. n), w>, c[n] = <w, w> (the self slot); gate: the launches return at once where gate[0] == 0
 int orth_dots(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int n, double* c, const int* gate = nullptr);
 // row k = w made orthogonal to rows [0, k) by two CGS passes, normalised; synchronises.  what: the name check_launch reports
 int orth_store(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int k, const char* what);
 // one extension step: w against rows [0, nb) - CGS and a second pass -, its norm to norm_slot, w / norm to row nb.  proj: where the nb
-// measured coefficients go (both passes' sums).  nb == 0: the norm only.  No check_launch, no synchronisation: the caller's.
+// measured coefficients go (both passes' sums).  nb == 0: the norm only (real bases).  No check_launch, no synchronisation: the caller's.
 enum class OrthPass2 {
   kGated,    // the DGKS gate: pass 2's launches return at once unless pass 1 cancelled more than half of |w|^2
   kForced,   // the same gated launches, the gate always set (LZ_FLAG_TRL_PASS2_ALWAYS)
-  kUngated,  // pass 2's launches take no gate at all (the tail of a band batch, on a view of the rows the batch has made)
+  kUngated,  // pass 2's launches take no gate at all (the tail of a band batch, on a view of the rows the batch has made; real bases)
 };
 int orth_cgs_step(lz_handle h, const OrthBasis& b, const OrthWork& wk, const QtwPlan& plan, int nb, double* proj, double* norm_slot,
                   OrthPass2 pass2);
-int orth_upload_x(lz_handle h, const OrthBasis& b, const double* x);                     // w = x, zero beyond len
-int orth_get_vectors(lz_handle h, const OrthBasis& b, int k, double* out);              // out (len x k, row-major) = rows [0, k) transposed
-// raw rows j0 .. j0 + count - 1 with their padding.  who, top: the caller and its name for the last row, for the argument error's text
+// Across the ABI a real basis moves raw doubles, a complex one interleaved complex128 without padding:
+int orth_upload_x(lz_handle h, const OrthBasis& b, const double* x);         // w = x (len elements), zero beyond len
+int orth_get_vectors(lz_handle h, const OrthBasis& b, int k, double* out);  // out (len x k elements, row-major) = rows [0, k) transposed
+// rows j0 .. j0 + count - 1, ld elements apart on the host.  Real: raw rows with their padding, ld >= pad.  Complex: ld >= len, the
+// padding is written as zero on set.  who, top: the caller and its name for the last row, for the argument error's text
 int orth_set_rows(lz_handle h, const OrthBasis& b, const char* who, const char* top, int j0, int count, const double* rows, int64_t ld);
 int orth_get_rows(lz_handle h, const OrthBasis& b, const char* who, const char* top, int j0, int count, double* rows, int64_t ld);
+// n interleaved complex z <-> the planes re and im
+void to_planar(const double* z, int64_t n, double* re, double* im);
+void to_interleaved(const double* re, const double* im, int64_t n, double* z);
+// out[i] (device) = |y_i - theta_i B_i|, i < k, where product(i) leaves y_i in b.w; theta on the device.  No check_launch, no synchronisation.
+int orth_resid_norms(lz_handle h, const OrthBasis& b, const OrthWork& wk, int k, const double* theta, double* out,
+                     const std::function<hipError_t(int)>& product);
 // partials that the sequences above and m residual norms need; the solver adds its own terms and reserves the largest
 size_t orth_part_need(const OrthBasis& b, const QtwPlan& plan, int m);
 int orth_part_reserve(lz_handle h, OrthWork& wk, size_t need);

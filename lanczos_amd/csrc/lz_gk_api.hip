@@ -3,7 +3,7 @@
 // handle's square operator: h->kind, h->rows, a fixed-n run's V / Y and a thick-restart basis on the same handle stay as they are.
 // What is here is the solver's own: the rectangular matrices and their work items, the alternating step with its resumed half, the
 // two-sided restart, the residuals and the product probes.  Orthogonalising against U or V - an OrthBasis each, with one OrthWork
-// between them - and the row transfers are the basis layer's (lz_orth.hip), shared with the thick-restart solver; the products go
+// between them - and the row transfers are the basis layer's (lz_orth.hip), shared with the thick-restart solvers; the products go
 // through gk_product: launch_spmv_rect (lz_gk.hip) for a CSR operator - these matrices never reach launch_spmv_csr or any of the square
 // layouts, whose epilogue reads x_own[row] - or the rowdot / colsum kernels on the one dense copy of lz_gk_set_dense.
 #include "lz_context.h"
@@ -332,12 +332,8 @@ int lz_gk_residuals(lz_handle h, int k, const double* sigma, double* out) {
   for (int side = 0; side < 2; ++side) {  // 0: |A v_i - sigma_i u_i| (length p), 1: |A^T u_i - sigma_i v_i| (length q)
     const OrthBasis& in = gk_basis(h, 1 - side);
     const OrthBasis& o = gk_basis(h, side);
-    int G = 0;
-    for (int i = 0; i < k; ++i) {
-      LZ_HIP(h, gk_product(h, side, in.B + (int64_t)i * in.ld, o.w, o.pad));
-      G = launch_trl_resid_diff(o.w, o.B + (int64_t)i * o.ld, o.len, dsig, i, g.wk.part, h->stream);
-    }
-    launch_trl_rownorm(g.wk.part, G, k, g.wk.sm + L.res + (int64_t)side * k, h->stream);
+    LZ_TRY(orth_resid_norms(h, o, g.wk, k, dsig, g.wk.sm + L.res + (int64_t)side * k,
+                            [&](int i) { return gk_product(h, side, in.B + (int64_t)i * in.ld, o.w, o.pad); }));
   }
   LZ_TRY(check_launch(h, "gk residuals"));
   LZ_HIP(h, hipMemcpyAsync(out, g.wk.sm + L.res, (size_t)2 * k * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -2,7 +2,7 @@
 // The basis is a buffer of its own (h->trl: trl_m + trl_b rows); the fixed-n run's V / Y on the same handle are untouched.
 // What is here is the solver's own: the operator (A or a polynomial of A), the band batch, the restart, the residuals and the Rayleigh
 // quotient.  Orthogonalising a vector against the basis and storing it, the gated two-pass step of an extension and the row transfers
-// are the basis layer's (lz_orth.hip), shared with the Golub-Kahan-Lanczos solver.
+// are the basis layer's (lz_orth.hip), shared with the Golub-Kahan-Lanczos solver and the complex thick-restart solver.
 #include "lz_context.h"
 
 using namespace lz;
@@ -311,18 +311,17 @@ int lz_trl_residuals(lz_handle h, int k, const double* theta, double* out) {
   const TrlSmall L = trl_small_layout(h);
   double* dth = h->trl_wk.sm + L.theta;
   LZ_TRY(upload(h, dth, theta, (size_t)k * sizeof(double)));
-  int G = 0;
   if (h->kind == 1) {
-    G = launch_trl_resid_csr(h->csr, h->trl.B, h->trl.ld, k, dth, h->trl_wk.part, h->stream);
+    const int G = launch_trl_resid_csr(h->csr, h->trl.B, h->trl.ld, k, dth, h->trl_wk.part, h->stream);
+    launch_trl_rownorm(h->trl_wk.part, G, k, h->trl_wk.sm + L.res, h->stream);
   } else {
-    const int Gd = (int)((h->rows + kTPB - 1) / kTPB);
-    for (int i = 0; i < k; ++i) {
+    const int Gd = (int)((h->rows + kTPB - 1) / kTPB);  // the products' own partials lie behind the k rows of the norms'
+    LZ_TRY(orth_resid_norms(h, h->trl, h->trl_wk, k, dth, h->trl_wk.sm + L.res, [&](int i) {
       const double* x = h->trl.B + (int64_t)i * h->trl.ld;
       launch_gemv_dense(h->d_dense, h->rows, h->ncols_ext, h->dense_lda, x, x, h->trl.w, h->trl_wk.part + (size_t)k * Gd, h->stream);
-      G = launch_trl_resid_diff(h->trl.w, x, h->rows, dth, i, h->trl_wk.part, h->stream);
-    }
+      return hipSuccess;
+    }));
   }
-  launch_trl_rownorm(h->trl_wk.part, G, k, h->trl_wk.sm + L.res, h->stream);
   LZ_TRY(check_launch(h, "trl residuals"));
   LZ_HIP(h, hipMemcpyAsync(out, h->trl_wk.sm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));

@@ -235,10 +235,7 @@ int lz_zspmv_host(lz_handle h, const double* x, double* y) {
     z.xtmp_pad = pad;
   }
   std::vector<double> buf(2 * (size_t)pad, 0.0);  // planar x, then planar y
-  for (int64_t i = 0; i < n; ++i) {
-    buf[(size_t)i] = x[2 * i];
-    buf[(size_t)(pad + i)] = x[2 * i + 1];
-  }
+  to_planar(x, n, buf.data(), buf.data() + pad);
   LZ_TRY(upload(h, z.xtmp, buf.data(), 2 * (size_t)pad * sizeof(double)));
   z_matvec(h, z.xtmp, z.xtmp + 2 * pad, pad);
   LZ_TRY(check_launch(h, "zspmv"));
@@ -246,10 +243,7 @@ int lz_zspmv_host(lz_handle h, const double* x, double* y) {
   LZ_HIP(h, hipMemcpy2DAsync(buf.data(), (size_t)pad * sizeof(double), z.xtmp + 2 * pad, (size_t)pad * sizeof(double), (size_t)n * sizeof(double), 2,
                              hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
-  for (int64_t i = 0; i < n; ++i) {
-    y[2 * i] = buf[(size_t)i];
-    y[2 * i + 1] = buf[(size_t)(pad + i)];
-  }
+  to_interleaved(buf.data(), buf.data() + pad, n, y);
   return LZ_OK;
 }
 

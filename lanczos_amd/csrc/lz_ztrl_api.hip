@@ -1,9 +1,9 @@
 // C ABI of the complex thick-restart Lanczos solver (include/lanczos_hip.h, "complex Hermitian matrices"): the device half of
-// lanczos_amd.eigsh on complex Hermitian input.  The twin of lz_trl_api.hip on a complex matrix (lz_zspmv.hip) and a planar basis of
-// its own (h->z.B: 2 (m + 1) real rows, complex row j = rows 2 j and 2 j + 1), so the restart is launch_trl_restart on the real form of
-// S, the vectors come back through orth_get_vectors and the scale-and-store and final sums are the real kernels'.  The inner products
-// and the Gram-Schmidt update are complex kernels (lz_ztrl.hip).  Across the ABI everything complex is interleaved complex128.
-// The padding rule is lz_orth.hip's: the walks stream the padded length, the products write n, a begin or probe zeroes all of w.
+// lanczos_amd.eigsh on complex Hermitian input.  The basis is a two-plane OrthBasis of its own (h->z.B: m + 1 complex rows), and
+// orthogonalising against it, the gated two-pass step, the row transfers and the residual norms are the basis layer's (lz_orth.hip),
+// shared with the real solvers.  What is here is the solver's own: the state and its checks, the product with the complex matrix
+// (lz_zspmv.hip) and the restart, which is launch_trl_restart on the real form of S.  Across the ABI everything complex is interleaved
+// complex128.
 #include "lz_context.h"
 
 using namespace lz;
@@ -13,18 +13,15 @@ namespace {
 
 constexpr int kZMaxM = kZMaxRows - 1;  // 64: the restart's real form has 2 m rows, and launch_trl_restart takes up to 128
 
-// z.wk.sm: c of both passes (interleaved complex, the self slot last), nrm2, the projected rows (m x m complex), beta (m), the
-// restart's S in real form (2 m x 2 m), theta and the residual norms (m each)
-struct ZSmall {
-  int64_t c1, c2, nrm2, proj, beta, S, theta, res, total;
+// z.wk.sm: the basis layer's head (c of both passes, nrm2), the projected rows (m x m complex), beta (m), the restart's S in real
+// form (2 m x 2 m), theta and the residual norms (m each)
+struct ZSmall : OrthSmallHead {
+  int64_t proj, beta, S, theta, res, total;
 };
 ZSmall ztrl_small_layout(int m) {
   ZSmall L;
-  const int64_t cl = 2 * (int64_t)(m + 2) + 16;
-  L.c1 = 0;
-  L.c2 = cl;
-  L.nrm2 = 2 * cl;
-  L.proj = L.nrm2 + 8;
+  static_cast<OrthSmallHead&>(L) = orth_small_head(m + 1, 2);
+  L.proj = L.end;
   L.beta = L.proj + 2 * (int64_t)m * m;
   L.S = L.beta + m + 8;
   L.theta = L.S + 4 * (int64_t)m * m;
@@ -56,7 +53,7 @@ int ztrl_alloc(lz_handle h, int m) {
   LZ_HIP(h, hipSetDevice(h->dev));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   const int64_t ld = skew_stride(h, h->rows_pad);
-  const size_t nrows = 2 * (size_t)(m + 1);
+  const size_t nrows = 2 * (size_t)(m + 1);  // real rows
   const ZSmall L = ztrl_small_layout(m);
   if (!z.B.B || z.m != m || z.B.ld != ld) {
     LZ_TRY(dev_alloc(h, z.B.B, nrows * (size_t)ld));
@@ -65,14 +62,12 @@ int ztrl_alloc(lz_handle h, int m) {
     LZ_TRY(dev_alloc(h, z.wk.gate, 4));
     z.m = m;
     z.B.ld = ld;
-    z.B.nrows = (int)nrows;
+    z.B.nrows = m + 1;
+    z.B.planes = 2;
   }
   z.B.len = h->rows;
   z.B.pad = h->rows_pad;
-  size_t need = 2 * (size_t)(m + 2) * (size_t)zdots_blocks(h->rows_pad);
-  need = std::max<size_t>(need, (size_t)zcgs_blocks(h->rows_pad));
-  need = std::max<size_t>(need, (size_t)m * (size_t)((h->rows + kTPB - 1) / kTPB) + 64);  // residual norms
-  LZ_TRY(orth_part_reserve(h, z.wk, need));
+  LZ_TRY(orth_part_reserve(h, z.wk, orth_part_need(z.B, orth_plan(h, z.B), m)));
   LZ_HIP(h, hipMemsetAsync(z.B.B, 0, nrows * (size_t)ld * sizeof(double), h->stream));
   LZ_HIP(h, hipMemsetAsync(z.B.w, 0, 2 * (size_t)ld * sizeof(double), h->stream));
   LZ_HIP(h, hipMemsetAsync(z.wk.sm, 0, (size_t)L.total * sizeof(double), h->stream));
@@ -80,77 +75,10 @@ int ztrl_alloc(lz_handle h, int m) {
   return LZ_OK;
 }
 
-// c (interleaved, nb + 1 complex: the self slot last) = <V_i, w>, i < nb
-void ztrl_dots(lz_handle h, int nb, double* c, const int* gate) {
-  const OrthBasis& V = h->z.B;
-  const int G = launch_zdots(V.B, V.ld, V.pad, nb, V.w, h->z.wk.part, gate, h->stream);
-  // (the final sums take no gate: behind a closed gate they add stale partials into pass 2's c, which nothing reads)
-  launch_final_rows(h->z.wk.part, 2 * (nb + 1), G, c, h->stream);
-}
-
-// w = x (n interleaved complex), planar, everything beyond n zero
-int ztrl_upload_x(lz_handle h, const double* x) {
-  const OrthBasis& V = h->z.B;
-  const int64_t n = V.len;
-  std::vector<double> buf(2 * (size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    buf[(size_t)i] = x[2 * i];
-    buf[(size_t)(n + i)] = x[2 * i + 1];
-  }
-  LZ_HIP(h, hipMemsetAsync(V.w, 0, 2 * (size_t)V.ld * sizeof(double), h->stream));
-  LZ_TRY(upload2d(h, V.w, (size_t)V.ld * sizeof(double), buf.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), 2));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));  // (buf)
-  return LZ_OK;
-}
-
-// w / |w| to complex row k, |w| to norm_slot
-void ztrl_scale_store(lz_handle h, int k, const double* nrm2, double* norm_slot) {
-  const OrthBasis& V = h->z.B;
-  launch_scale_store(V.B + (int64_t)(2 * k) * V.ld, V.w, nrm2, norm_slot, V.pad, h->stream);
-  launch_scale_store(V.B + (int64_t)(2 * k + 1) * V.ld, V.w + V.ld, nrm2, norm_slot, V.pad, h->stream);
-}
-
-// row k = w made orthogonal to rows [0, k) by two CGS passes, normalised; synchronises (orth_store's sequence)
-int ztrl_store(lz_handle h, int k, const char* what) {
-  const OrthBasis& V = h->z.B;
-  const OrthWork& wk = h->z.wk;
-  const ZSmall L = ztrl_small_layout(h->z.m);
-  double* c = wk.sm + L.c1;
-  double* nrm2 = wk.sm + L.nrm2;
-  int np = 0;
-  for (int pass = 0; pass < (k > 0 ? 2 : 1); ++pass) {
-    if (k > 0) ztrl_dots(h, k, c, nullptr);
-    np = launch_zcgs(V.B, V.ld, V.pad, k, c, V.w, wk.part, nullptr, h->stream);
-  }
-  launch_trl_post(2, wk.part, np, nullptr, 0, nrm2, nullptr, wk.gate, 0, h->stream);
-  ztrl_scale_store(h, k, nrm2, nrm2 + 1);
-  LZ_TRY(check_launch(h, what));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  return LZ_OK;
-}
-
-// one extension step (orth_cgs_step's sequence, nb >= 1): w against rows [0, nb), a second pass behind the DGKS gate (or forced), the
-// nb complex coefficients to proj, |w| to norm_slot, w / |w| to row nb.  launch_trl_post sees the interleaved c as 2 nb doubles
-// followed by the self slot's real part, which is where it looks for |w|^2 before the pass.
-void ztrl_cgs_step(lz_handle h, int nb, double* proj, double* norm_slot, bool forced) {
-  const OrthBasis& V = h->z.B;
-  const OrthWork& wk = h->z.wk;
-  const ZSmall L = ztrl_small_layout(h->z.m);
-  double* nrm2 = wk.sm + L.nrm2;
-  for (int pass = 0; pass < 2; ++pass) {
-    double* c = wk.sm + (pass == 0 ? L.c1 : L.c2);
-    const int* gate = pass == 0 ? nullptr : wk.gate;
-    ztrl_dots(h, nb, c, gate);
-    const int np = launch_zcgs(V.B, V.ld, V.pad, nb, c, V.w, wk.part, gate, h->stream);
-    launch_trl_post(pass, wk.part, np, c, 2 * nb - 1, nrm2, proj, wk.gate, forced ? 1 : 0, h->stream);
-  }
-  ztrl_scale_store(h, nb, nrm2, norm_slot);
-}
-
-int zrows_arg(lz_handle h, const char* who, int j0, int count, const double* rows, int64_t ld) {
-  if (!rows || j0 < 0 || count < 1 || j0 + count > h->z.m + 1 || ld < h->rows)
-    return fail(h, LZ_ERR_ARG, std::string(who) + ": need rows j0 .. j0 + count - 1 <= m and ld >= n (in complex elements)");
-  return LZ_OK;
+// V[k] = x made orthogonal to V[0..k), normalised
+int ztrl_store_x(lz_handle h, int k, const double* x, const char* what) {
+  LZ_TRY(orth_upload_x(h, h->z.B, x));
+  return orth_store(h, h->z.B, h->z.wk, orth_plan(h, h->z.B), k, what);
 }
 
 }  // namespace
@@ -160,8 +88,7 @@ extern "C" {
 int lz_ztrl_begin(lz_handle h, int m, const double* v0) {
   if (!h || !v0) return LZ_ERR_ARG;
   LZ_TRY(ztrl_alloc(h, m));
-  LZ_TRY(ztrl_upload_x(h, v0));
-  return ztrl_store(h, 0, "ztrl begin");
+  return ztrl_store_x(h, 0, v0, "ztrl begin");
 }
 
 int lz_ztrl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out) {
@@ -171,10 +98,11 @@ int lz_ztrl_extend(lz_handle h, int k, int m, double* proj_out, double* beta_out
   const ZSmall L = ztrl_small_layout(m);
   const OrthBasis& V = z.B;
   double* sm = z.wk.sm;
-  const bool forced = (h->flags & LZ_FLAG_TRL_PASS2_ALWAYS) != 0;
+  const QtwPlan plan = orth_plan(h, V);
+  const OrthPass2 pass2 = (h->flags & LZ_FLAG_TRL_PASS2_ALWAYS) ? OrthPass2::kForced : OrthPass2::kGated;
   for (int j = k; j < m; ++j) {
     z_matvec(h, V.B + (int64_t)(2 * j) * V.ld, V.w, V.ld);  // w = A V[j]
-    ztrl_cgs_step(h, j + 1, sm + L.proj + 2 * (int64_t)j * m, sm + L.beta + j, forced);
+    LZ_TRY(orth_cgs_step(h, V, z.wk, plan, j + 1, sm + L.proj + 2 * (int64_t)j * m, sm + L.beta + j, pass2));
     LZ_TRY(check_launch(h, "ztrl extend"));
   }
   if (proj_out) LZ_HIP(h, hipMemcpyAsync(proj_out, sm + L.proj, 2 * (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -213,15 +141,13 @@ int lz_ztrl_restart(lz_handle h, int m, int kk, const double* S) {
 int lz_ztrl_probe(lz_handle h, int k, const double* x) {
   LZ_TRY(ztrl_state(h, "lz_ztrl_probe"));
   if (!x || k < 0 || k > h->z.m) return fail(h, LZ_ERR_ARG, "lz_ztrl_probe: need 0 <= k <= m and x");
-  LZ_TRY(ztrl_upload_x(h, x));
-  return ztrl_store(h, k, "ztrl orthogonalise");
+  return ztrl_store_x(h, k, x, "ztrl orthogonalise");
 }
 
 int lz_ztrl_get_vectors(lz_handle h, int k, double* Y_out) {
   LZ_TRY(ztrl_state(h, "lz_ztrl_get_vectors"));
   if (!Y_out || k < 1 || k > h->z.m) return fail(h, LZ_ERR_ARG, "lz_ztrl_get_vectors: need 1 <= k <= m and Y_out");
-  // the 2 k real rows transposed are n x 2 k doubles with Re, Im of Y[r, i] side by side: n x k interleaved complex
-  return orth_get_vectors(h, h->z.B, 2 * k, Y_out);
+  return orth_get_vectors(h, h->z.B, k, Y_out);
 }
 
 int lz_ztrl_residuals(lz_handle h, int k, const double* theta, double* out) {
@@ -231,13 +157,10 @@ int lz_ztrl_residuals(lz_handle h, int k, const double* theta, double* out) {
   const ZSmall L = ztrl_small_layout(z.m);
   double* dth = z.wk.sm + L.theta;
   LZ_TRY(upload(h, dth, theta, (size_t)k * sizeof(double)));
-  int G = 0;
-  for (int i = 0; i < k; ++i) {
-    const double* x = z.B.B + (int64_t)(2 * i) * z.B.ld;
-    z_matvec(h, x, z.B.w, z.B.ld);
-    G = launch_zresid_diff(z.B.w, x, z.B.ld, h->rows, dth, i, z.wk.part, h->stream);
-  }
-  launch_trl_rownorm(z.wk.part, G, k, z.wk.sm + L.res, h->stream);
+  LZ_TRY(orth_resid_norms(h, z.B, z.wk, k, dth, z.wk.sm + L.res, [&](int i) {
+    z_matvec(h, z.B.B + (int64_t)(2 * i) * z.B.ld, z.B.w, z.B.ld);
+    return hipSuccess;
+  }));
   LZ_TRY(check_launch(h, "ztrl residuals"));
   LZ_HIP(h, hipMemcpyAsync(out, z.wk.sm + L.res, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
@@ -246,44 +169,12 @@ int lz_ztrl_residuals(lz_handle h, int k, const double* theta, double* out) {
 
 int lz_ztrl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld) {
   LZ_TRY(ztrl_state(h, "lz_ztrl_set_rows"));
-  LZ_TRY(zrows_arg(h, "lz_ztrl_set_rows", j0, count, rows, ld));
-  const OrthBasis& V = h->z.B;
-  const int64_t n = V.len, pad = V.pad;
-  std::vector<double> buf(2 * (size_t)count * (size_t)pad, 0.0);  // planar, with a zero padding
-  for (int j = 0; j < count; ++j) {
-    const double* src = rows + 2 * (int64_t)j * ld;
-    double* re = buf.data() + (size_t)(2 * j) * pad;
-    double* im = re + pad;
-    for (int64_t i = 0; i < n; ++i) {
-      re[i] = src[2 * i];
-      im[i] = src[2 * i + 1];
-    }
-  }
-  LZ_TRY(upload2d(h, V.B + (int64_t)(2 * j0) * V.ld, (size_t)V.ld * sizeof(double), buf.data(), (size_t)pad * sizeof(double),
-                  (size_t)pad * sizeof(double), 2 * (size_t)count));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  return LZ_OK;
+  return orth_set_rows(h, h->z.B, "lz_ztrl_set_rows", "m", j0, count, rows, ld);
 }
 
 int lz_ztrl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld) {
   LZ_TRY(ztrl_state(h, "lz_ztrl_get_rows"));
-  LZ_TRY(zrows_arg(h, "lz_ztrl_get_rows", j0, count, rows, ld));
-  const OrthBasis& V = h->z.B;
-  const int64_t n = V.len;
-  std::vector<double> buf(2 * (size_t)count * (size_t)n);
-  LZ_HIP(h, hipMemcpy2DAsync(buf.data(), (size_t)n * sizeof(double), V.B + (int64_t)(2 * j0) * V.ld, (size_t)V.ld * sizeof(double),
-                             (size_t)n * sizeof(double), 2 * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-  LZ_HIP(h, hipStreamSynchronize(h->stream));
-  for (int j = 0; j < count; ++j) {
-    double* dst = rows + 2 * (int64_t)j * ld;
-    const double* re = buf.data() + (size_t)(2 * j) * n;
-    const double* im = re + n;
-    for (int64_t i = 0; i < n; ++i) {
-      dst[2 * i] = re[i];
-      dst[2 * i + 1] = im[i];
-    }
-  }
-  return LZ_OK;
+  return orth_get_rows(h, h->z.B, "lz_ztrl_get_rows", "m", j0, count, rows, ld);
 }
 
 }  // extern "C"

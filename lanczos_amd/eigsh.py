@@ -20,7 +20,7 @@ Band.  ``block_size=b`` runs the loop in Ruhe's band form (``trl_band``): ``b`` 
 copies of an eigenvalue up to multiplicity ``b`` appear without a probe and the device orthogonalises ``b`` vectors per walk over the
 basis; the bookkeeping stays that of single rows.
 
-Complex.  A complex Hermitian ``A`` runs the same loop (``trl``) on a complex backend (``lz_ztrl_*``): ``T`` is Hermitian, the small
+Complex.  A complex Hermitian ``A`` runs the same loop (``trl``) on the same backends, which then call ``lz_ztrl_*``: ``T`` is Hermitian, the small
 problem is ``eigh((T + T^H) / 2)``, the restart's arrow ``T[kk, :kk] = beta S[m - 1, keep]`` has its conjugate in the column, and
 start and probe vectors are complex.  For a real backend nothing changes, bit for bit.  ``ncv <= 64`` there.
 
@@ -52,23 +52,33 @@ def _order(theta, which):
 
 
 class NumpyBackend:
-    """The calls of the device backend (``lz_trl_*``) in NumPy: what the host tests drive the outer loop with."""
+    """The calls of the device backend (``lz_trl_*``; ``lz_ztrl_*`` for a complex Hermitian ``A``) in NumPy: what the host tests drive
+    the outer loop with.  ``<x, y> = sum conj(x) y`` on a complex matrix; the band, the polynomials and ``rayleigh`` are real-only, as
+    on the device."""
 
     def __init__(self, A, force_second_pass=False, block_size=None):
         self.A = A
         self.n = A.shape[0]
+        self.is_complex = is_complex_matrix(A)
+        self.dtype = np.complex128 if self.is_complex else np.float64
         self.force = force_second_pass
         self.block_size = block_size
         self.filter = None
         self.series = None
 
+    def _real_only(self, what):
+        if self.is_complex:
+            raise NotImplementedError(f"{what} with a complex matrix: built for the real basis only")
+
     def set_filter(self, coefficients, c=0.0):
         """``coefficients``: the (a_i, b_i) of ``ChebFilter.coefficients()``; None: ``extend`` multiplies by A itself again"""
+        self._real_only("set_filter")
         self.filter = None if coefficients is None else (np.asarray(coefficients, dtype=np.float64).reshape(-1, 2), float(c))
         self.series = None
 
     def set_series(self, coefficients, c=0.0, e=1.0):
         """``coefficients``: the ``degree + 1`` values of ``SeriesFilter.coefficients()``; None: ``extend`` multiplies by A itself again"""
+        self._real_only("set_series")
         self.series = None if coefficients is None else SeriesFilter.from_coefficients(coefficients, c, e)
         self.filter = None
 
@@ -84,25 +94,33 @@ class NumpyBackend:
         return cur
 
     def rayleigh(self, k):
+        self._real_only("rayleigh")
         Y = self.V[:k]
         return Y @ np.stack([self.A @ Y[i] for i in range(k)]).T
 
     def begin(self, m, v0):
-        self.V = np.zeros((m + 1, self.n))
+        self.V = np.zeros((m + 1, self.n), dtype=self.dtype)
         self.V[0] = v0 / np.linalg.norm(v0)
 
+    def _dots(self, k, x):
+        """``<V_i, x>``, ``i < k``"""
+        return (self.V[:k].conj() if self.is_complex else self.V[:k]) @ x
+
+    def _norm2(self, w):
+        return np.vdot(w, w).real if self.is_complex else np.dot(w, w)
+
     def _cgs(self, w, j):
-        c = self.V[: j + 1] @ w
+        c = self._dots(j + 1, w)
         return w - c @ self.V[: j + 1], c
 
     def extend(self, k, m):
-        proj = np.zeros((m, m))
+        proj = np.zeros((m, m), dtype=self.dtype)
         beta = np.zeros(m)
         for j in range(k, m):
             w = self._op(self.V[j])
-            w0 = np.dot(w, w)
+            w0 = self._norm2(w)
             w, c = self._cgs(w, j)
-            if self.force or np.dot(w, w) < 0.5 * w0:  # DGKS: the second pass only when the first cancelled more than half of |w|
+            if self.force or self._norm2(w) < 0.5 * w0:  # DGKS: the second pass only when the first cancelled more than half of |w|
                 w, c2 = self._cgs(w, j)
                 c = c + c2
             proj[j, : j + 1] = c
@@ -112,6 +130,7 @@ class NumpyBackend:
 
     def begin_band(self, m, X):
         """the band form of ``begin``: ``m + b`` rows, rows ``0..b`` the rows of ``X`` orthonormalised one by one (``probe``)"""
+        self._real_only("begin_band")
         X = np.asarray(X, dtype=np.float64)
         self.V = np.zeros((m + len(X), self.n))
         for i in range(len(X)):
@@ -120,6 +139,7 @@ class NumpyBackend:
     def extend_band(self, k, m):
         """the band form of ``extend``: step ``j`` makes row ``j + b`` from ``Op V[j]``, orthogonalised against every row below it by two
         CGS passes (no gate).  Returns ``proj`` (``m x (m + b)``: row ``j`` holds the coefficients on rows ``0..j+b``) and ``beta`` (``m``)."""
+        self._real_only("extend_band")
         b = len(self.V) - m
         proj = np.zeros((m, m + b))
         beta = np.zeros(m)
@@ -140,7 +160,7 @@ class NumpyBackend:
 
     def probe(self, k, x):
         for _ in range(2):
-            x = x - (self.V[:k] @ x) @ self.V[:k]
+            x = x - self._dots(k, x) @ self.V[:k]
         self.V[k] = x / np.linalg.norm(x)
 
     def get_vectors(self, k):
@@ -150,54 +170,7 @@ class NumpyBackend:
         return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
 
 
-class ComplexNumpyBackend:
-    """The calls of the complex device backend (``lz_ztrl_*``) in NumPy, for a complex Hermitian ``A``: what the host tests drive the
-    outer loop with.  ``<x, y> = sum conj(x) y`` throughout."""
-
-    is_complex = True
-
-    def __init__(self, A, force_second_pass=False):
-        self.A = A
-        self.n = A.shape[0]
-        self.force = force_second_pass
-
-    def begin(self, m, v0):
-        self.V = np.zeros((m + 1, self.n), dtype=np.complex128)
-        self.V[0] = v0 / np.linalg.norm(v0)
-
-    def _cgs(self, w, j):
-        c = self.V[: j + 1].conj() @ w
-        return w - c @ self.V[: j + 1], c
-
-    def extend(self, k, m):
-        proj = np.zeros((m, m), dtype=np.complex128)
-        beta = np.zeros(m)
-        for j in range(k, m):
-            w = self.A @ self.V[j]
-            w0 = np.vdot(w, w).real
-            w, c = self._cgs(w, j)
-            if self.force or np.vdot(w, w).real < 0.5 * w0:
-                w, c2 = self._cgs(w, j)
-                c = c + c2
-            proj[j, : j + 1] = c
-            beta[j] = np.linalg.norm(w)
-            self.V[j + 1] = w / beta[j]
-        return proj, beta
-
-    def restart(self, m, kk, S):
-        self.V[:kk] = S.T @ self.V[:m]
-        self.V[kk] = self.V[m].copy()
-
-    def probe(self, k, x):
-        for _ in range(2):
-            x = x - (self.V[:k].conj() @ x) @ self.V[:k]
-        self.V[k] = x / np.linalg.norm(x)
-
-    def get_vectors(self, k):
-        return self.V[:k].T.copy()
-
-    def residuals(self, k, theta):
-        return np.array([np.linalg.norm(self.A @ self.V[i] - theta[i] * self.V[i]) for i in range(k)])
+ComplexNumpyBackend = NumpyBackend  # the name the complex host twin had while it was a class of its own: callers written for it still import
 
 
 def _check_problem(n, k, which, M=None, sigma=None, Minv=None, OPinv=None, mode="normal"):
@@ -875,22 +848,28 @@ def trl_interior(backend, n, k, sigma, degree, ncv=None, maxiter=None, tol=0.0, 
 
 
 class DeviceBackend:
-    """The ``lz_trl_*`` calls on one ``_capi.Handle`` that already holds the matrix."""
+    """The ``lz_trl_*`` calls - ``lz_ztrl_*`` with ``is_complex`` - on one ``_capi.Handle`` that already holds the matrix.  The band,
+    the polynomials and ``rayleigh`` exist for a real matrix only (on a complex one the handle answers that no matrix is set)."""
 
-    def __init__(self, handle, n, force_second_pass=False, block_size=None):
+    def __init__(self, handle, n, force_second_pass=False, block_size=None, is_complex=False):
         self.h = handle
         self.n = n
         self.block_size = block_size
+        self.is_complex = is_complex
+        self._prefix = "ztrl_" if is_complex else "trl_"  # of begin, extend, restart, probe, get_vectors and residuals
         if force_second_pass:
             from ._capi import FLAG_TRL_PASS2_ALWAYS
 
             handle.set_options(FLAG_TRL_PASS2_ALWAYS)
 
+    def _call(self, name, *args):
+        return getattr(self.h, self._prefix + name)(*args)
+
     def begin(self, m, v0):
-        self.h.trl_begin(m, v0)
+        self._call("begin", m, v0)
 
     def extend(self, k, m):
-        return self.h.trl_extend(k, m)
+        return self._call("extend", k, m)
 
     def begin_band(self, m, X):
         self.h.trl_begin_band(m, X)
@@ -899,16 +878,16 @@ class DeviceBackend:
         return self.h.trl_extend_band(k, m)
 
     def restart(self, m, kk, S):
-        self.h.trl_restart(m, kk, S)
+        self._call("restart", m, kk, S)
 
     def probe(self, k, x):
-        self.h.trl_probe(k, x)
+        self._call("probe", k, x)
 
     def get_vectors(self, k):
-        return self.h.trl_get_vectors(k)
+        return self._call("get_vectors", k)
 
     def residuals(self, k, theta):
-        return self.h.trl_residuals(k, theta)
+        return self._call("residuals", k, theta)
 
     def set_filter(self, coefficients, c=0.0):
         self.h.trl_set_filter(coefficients, c)
@@ -918,38 +897,6 @@ class DeviceBackend:
 
     def rayleigh(self, k):
         return self.h.trl_rayleigh(k)
-
-
-class ComplexDeviceBackend:
-    """The ``lz_ztrl_*`` calls on one ``_capi.Handle`` that already holds the complex Hermitian matrix."""
-
-    is_complex = True
-
-    def __init__(self, handle, n, force_second_pass=False):
-        self.h = handle
-        self.n = n
-        if force_second_pass:
-            from ._capi import FLAG_TRL_PASS2_ALWAYS
-
-            handle.set_options(FLAG_TRL_PASS2_ALWAYS)
-
-    def begin(self, m, v0):
-        self.h.ztrl_begin(m, v0)
-
-    def extend(self, k, m):
-        return self.h.ztrl_extend(k, m)
-
-    def restart(self, m, kk, S):
-        self.h.ztrl_restart(m, kk, S)
-
-    def probe(self, k, x):
-        self.h.ztrl_probe(k, x)
-
-    def get_vectors(self, k):
-        return self.h.ztrl_get_vectors(k)
-
-    def residuals(self, k, theta):
-        return self.h.ztrl_residuals(k, theta)
 
 
 def is_complex_matrix(A):
@@ -968,25 +915,6 @@ def upload_complex_matrix(h, A):
     else:
         h.set_dense_cplx(np.ascontiguousarray(A, dtype=np.complex128))
     return int(A.shape[0])
-
-
-def _eigsh_complex(A, n, k, which, v0, ncv, maxiter, tol, return_eigenvectors, device_id, handle, info):
-    """``eigsh`` for a complex Hermitian ``A``: the same outer loop on the complex device backend"""
-    from . import _capi
-
-    h = handle if handle is not None else _capi.Handle(device_id)
-    try:
-        upload_complex_matrix(h, A)
-        theta, run = trl(ComplexDeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
-        if info is not None:
-            info.update(run)
-            info["residuals"] = h.ztrl_residuals(k, theta)
-        if not return_eigenvectors:
-            return theta
-        return theta, h.ztrl_get_vectors(k)
-    finally:
-        if handle is None:
-            h.close()
 
 
 def upload_matrix(h, A):
@@ -1044,7 +972,9 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
     n = int(A.shape[0])
     if len(A.shape) != 2 or A.shape[1] != n:
         raise ValueError(f"expected square matrix (shape={A.shape})")
-    if is_complex_matrix(A):
+    cplx = is_complex_matrix(A)
+    interior = None
+    if cplx:
         if filter_degree is not None:
             raise NotImplementedError("filter_degree with a complex matrix: the polynomial filter is built for the real basis only")
         if sigma is not None:
@@ -1052,40 +982,40 @@ def eigsh(A, k=6, M=None, sigma=None, which="LM", v0=None, ncv=None, maxiter=Non
         if block_size is not None:
             raise NotImplementedError("block_size with a complex matrix: the band form is built for the real basis only")
         check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode, complex_A=True)
-        return _eigsh_complex(A, n, k, which, v0, ncv, maxiter, tol, return_eigenvectors, device_id, handle, info)
-    if block_size is not None:
-        check_block_size(block_size)
-        if sigma is not None:
-            raise NotImplementedError("block_size with sigma: the interior mode's certificate is defined for the single-vector loop only")
-    interior = check_interior_args(which, sigma, filter_degree) if M is None and Minv is None and OPinv is None else None
-    if interior is not None:
-        check_args(n, k, which, None, M, None, Minv, OPinv, mode)  # (ncv is measured against the k + extra pairs of trl_interior)
     else:
-        if block_size is None:
-            check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+        if block_size is not None:
+            check_block_size(block_size)
+            if sigma is not None:
+                raise NotImplementedError("block_size with sigma: the interior mode's certificate is defined for the single-vector loop only")
+        if M is None and Minv is None and OPinv is None:
+            interior = check_interior_args(which, sigma, filter_degree)
+        if interior is not None:
+            check_args(n, k, which, None, M, None, Minv, OPinv, mode)  # (ncv is measured against the k + extra pairs of trl_interior)
         else:
-            check_band_args(n, k, which, ncv, block_size, M, sigma, Minv, OPinv, mode)
-        if filter_degree is not None:
-            check_filter_args(which, filter_degree)
+            if block_size is None:
+                check_args(n, k, which, ncv, M, sigma, Minv, OPinv, mode)
+            else:
+                check_band_args(n, k, which, ncv, block_size, M, sigma, Minv, OPinv, mode)
+            if filter_degree is not None:
+                check_filter_args(which, filter_degree)
     h = handle if handle is not None else _capi.Handle(device_id)
     try:
-        upload_matrix(h, A)
+        (upload_complex_matrix if cplx else upload_matrix)(h, A)
+        backend = DeviceBackend(h, n, block_size=block_size, is_complex=cplx)
         if interior is not None:
-            theta, run = trl_interior(DeviceBackend(h, n), n, k, interior[0], interior[1], ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+            theta, run = trl_interior(backend, n, k, interior[0], interior[1], ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
         elif filter_degree is None and block_size is None:
-            theta, run = trl(DeviceBackend(h, n), n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
+            theta, run = trl(backend, n, k, which=which, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
         elif filter_degree is None:
-            theta, run = trl_band(DeviceBackend(h, n, block_size=block_size), n, k, which, block_size, ncv=ncv, maxiter=maxiter, tol=tol,
-                                  v0=v0)
+            theta, run = trl_band(backend, n, k, which, block_size, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0)
         else:
-            theta, run = trl_filtered(DeviceBackend(h, n, block_size=block_size), n, k, which, filter_degree, ncv=ncv, maxiter=maxiter,
-                                      tol=tol, v0=v0, block_size=block_size)
+            theta, run = trl_filtered(backend, n, k, which, filter_degree, ncv=ncv, maxiter=maxiter, tol=tol, v0=v0, block_size=block_size)
         if info is not None:
             info.update(run)
-            info["residuals"] = h.trl_residuals(k, theta)
+            info["residuals"] = backend.residuals(k, theta)
         if not return_eigenvectors:
             return theta
-        return theta, h.trl_get_vectors(k)
+        return theta, backend.get_vectors(k)
     finally:
         if handle is None:
             h.close()

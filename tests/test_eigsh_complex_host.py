@@ -24,7 +24,7 @@ from scipy.sparse.linalg import ArpackNoConvergence
 from lanczos_amd import eigsh as eigsh_fn
 from lanczos_amd import synthetic
 from lanczos_amd._solver import _pack_matrix
-from lanczos_amd.eigsh import (_EPS, _SEED, ComplexNumpyBackend, NumpyBackend, _fill, _order, _start, check_args, trl,
+from lanczos_amd.eigsh import (_EPS, _SEED, NumpyBackend, _fill, _order, _start, check_args, trl,
                                upload_complex_matrix)
 
 # ---------------------------------------------------------------- the matrices and the convergence cases
@@ -100,7 +100,7 @@ def test_hofstadter_is_the_harper_hamiltonian():
 @pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: c.name)
 def test_trl_converges_on_the_complex_numpy_backend(case):
     A, _, _ = conv_matrix(case.matrix)
-    be = ComplexNumpyBackend(A)
+    be = NumpyBackend(A)
     theta, info = trl(be, A.shape[0], case.k, case.which, ncv=case.ncv)
     print(info)
     check_pairs(case, theta, be.get_vectors(case.k), case.name)
@@ -111,17 +111,17 @@ def test_real_and_complex_start_vectors():
     case = CONV_CASES[-1]
     rng = np.random.default_rng(3)
     for v0 in (rng.standard_normal(96), rng.standard_normal(96) + 1j * rng.standard_normal(96)):
-        be = ComplexNumpyBackend(A)
+        be = NumpyBackend(A)
         theta, _ = trl(be, 96, case.k, case.which, v0=v0)
         check_pairs(case, theta, be.get_vectors(case.k), f"v0 {v0.dtype}")
     with pytest.raises(ValueError, match="v0"):
-        trl(ComplexNumpyBackend(A), 96, 4, "SA", v0=np.zeros(96))
+        trl(NumpyBackend(A), 96, 4, "SA", v0=np.zeros(96))
 
 
 def test_no_convergence_carries_the_converged_pairs():
     A, _, _ = conv_matrix("hof")
     with pytest.raises(ArpackNoConvergence) as e:
-        trl(ComplexNumpyBackend(A), 408, 6, "SA", maxiter=1)
+        trl(NumpyBackend(A), 408, 6, "SA", maxiter=1)
     assert e.value.eigenvectors.dtype == np.complex128 and e.value.eigenvectors.shape == (408, len(e.value.eigenvalues))
 
 
@@ -388,7 +388,7 @@ def test_step_cases_are_decisive_and_numpy_is_within_the_bounds(case):
     assert ref["e_proj"].max() < 1e-8 * wn and ref["e_beta"] < 1e-8 * wn  # the bounds bind
     if case.kind == "orth":  # <x, A x> is real, and with orthonormal rows so is what pass 2 adds to it
         assert abs((ref["c1"] + ref["c2"])[-1].imag) <= ref["e_proj"][-1]
-    be = ComplexNumpyBackend(A, force_second_pass=case.force)
+    be = NumpyBackend(A, force_second_pass=case.force)
     nb = case.nb
     be.V = np.zeros((nb + 1, case.n), dtype=np.complex128)
     be.V[:nb] = rows
@@ -396,3 +396,56 @@ def test_step_cases_are_decisive_and_numpy_is_within_the_bounds(case):
     assert worst(np.abs(proj[nb - 1, :nb] - (ref["c1"] + ref["c2"])), ref["e_proj"]) <= 1.0
     assert worst(abs(beta[nb - 1] - ref["beta"]), ref["e_beta"]) <= 1.0
     assert worst(np.abs(be.V[nb] - ref["v"]), ref["e_v"]) <= 1.0
+
+
+# ---------------------------------------------------------------- the probe: a row stored at k > 0 behind rows set from the host
+PROBE_M = 17
+PROBE_KS = (0, 1, 5, 17)
+
+
+@functools.lru_cache(maxsize=None)
+def probe_reference(n):
+    """``(A, V, x)``, computed once and never changed: the NumPy backend's ``PROBE_M + 1`` rows after ``extend(0, PROBE_M)`` and the
+    direction that is probed"""
+    A = zmatrix(n)
+    rng = np.random.default_rng([7, n])
+    be = NumpyBackend(A)
+    be.begin(PROBE_M, rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    be.extend(0, PROBE_M)
+    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    for a in (be.V, x):
+        a.setflags(write=False)
+    return A, be.V, x
+
+
+def probe_state(V, k):
+    """``V`` with the rows at and behind ``k`` filled with NaN: a probe of row ``k`` must not read them"""
+    W = V.copy()
+    W[k:] = np.nan
+    return W
+
+
+def check_probed_rows(new, old, ref_row, k, tag):
+    """the bars of tests/test_gpu_svds_edges.py's ``check_probe`` on complex rows: ``new`` after a probe of row ``k`` from the state
+    ``old``, ``ref_row`` what the NumPy backend stored"""
+    assert np.isfinite(new[k].view(np.float64)).all(), tag
+    assert np.linalg.norm(new[k] - ref_row) <= 1e-10, tag
+    assert abs(np.linalg.norm(new[k]) - 1.0) <= 1e-12, tag
+    if k:
+        assert np.abs(new[:k].conj() @ new[k]).max() <= 1e-12, tag
+    keep = np.arange(len(new)) != k
+    assert np.array_equal(new[keep], old[keep], equal_nan=True), tag  # the other rows: bit-unchanged
+
+
+@pytest.mark.parametrize("n", [33, 1000])
+def test_probe_on_the_numpy_backend_holds_the_bars(n):
+    """what tests/test_gpu_eigsh_complex.py asks of ``lz_ztrl_probe``, asked of the reference first; the row from the NaN-filled state
+    is compared with the one from the whole basis"""
+    A, V, x = probe_reference(n)
+    assert np.abs(V.conj() @ V.T - np.eye(PROBE_M + 1)).max() <= 1e-12
+    for k in PROBE_KS:
+        clean, be = NumpyBackend(A), NumpyBackend(A)
+        clean.V, be.V = V.copy(), probe_state(V, k)
+        clean.probe(k, x)
+        be.probe(k, x)
+        check_probed_rows(be.V, probe_state(V, k), clean.V[k], k, f"n {n} k {k}")

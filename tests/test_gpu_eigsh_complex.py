@@ -9,9 +9,11 @@ import pytest
 import scipy.sparse as sp
 from hermitian_reference import matvec, product_bound, worst
 from scipy.sparse.linalg import ArpackNoConvergence
-from test_eigsh_complex_host import CONV_CASES, LONG_N, STEP_CASES, Case, case_id, check_pairs, conv_matrix, step_reference
+from test_eigsh_complex_host import (CONV_CASES, LONG_N, PROBE_KS, PROBE_M, STEP_CASES, Case, case_id, check_pairs, check_probed_rows,
+                                     conv_matrix, probe_reference, probe_state, step_reference)
 
 from lanczos_amd import _capi, eigsh, synthetic
+from lanczos_amd.eigsh import NumpyBackend
 
 pytestmark = pytest.mark.gpu
 
@@ -163,6 +165,43 @@ def test_restart_matches_numpy(m, kk, n):
     assert np.abs(out[:kk] - ref).max() <= 1e-13 * scale
     assert np.array_equal(out[kk], V[m])  # V[m] moved to V[kk], bit for bit
     assert np.array_equal(out[kk + 1:], V[kk + 1:])  # the other rows >= kk untouched
+    h.close()
+
+
+# ---------------------------------------------------------------- the probe
+@pytest.mark.parametrize("n", [33, 1000])
+def test_probe_matches_numpy(n):
+    """Guards lz_orth.hip on a two-plane basis: orth_upload_x's memset of both planes of the work vector, orth_store's two CGS passes
+    over rows [0, k) - row k is the self slot and is not read -, its k == 0 norm-only branch and the scale-and-store of row k's two
+    planes alone; lz_ztrl_probe's bounds on k.  The bars are tests/test_gpu_svds_edges.py's (check_probed_rows)."""
+    A, V, x = probe_reference(n)
+    m = PROBE_M
+    h = _handle(A)
+    h.ztrl_begin(m, np.ones(n))
+    be = NumpyBackend(A)
+    for k in PROBE_KS:
+        state = probe_state(V, k)
+        h.ztrl_set_rows(0, state)
+        be.V = state.copy()
+        h.ztrl_probe(k, x)
+        be.probe(k, x)
+        check_probed_rows(h.ztrl_get_rows(0, m + 1), state, be.V[k], k, f"n {n} k {k}")
+    h.ztrl_set_rows(0, V)
+    for k in (-1, m + 1):
+        with pytest.raises(_capi.LanczosHipError):
+            h.ztrl_probe(k, x)
+    assert np.array_equal(h.ztrl_get_rows(0, m + 1), V)  # a refused call changes nothing
+    if n == 33:  # the padded length is 64: the unpadded getter cannot see the padding of w or of row 5, the steps that stream it can
+        assert h_pad(n) == 64
+        be.V = V.copy()
+        h.ztrl_probe(5, x)
+        be.probe(5, x)
+        proj, beta = h.ztrl_extend(5, m)
+        ref_proj, ref_beta = be.extend(5, m)
+        out = h.ztrl_get_rows(0, m + 1)
+        assert np.isfinite(proj[5:].view(np.float64)).all() and np.isfinite(beta[5:]).all() and np.isfinite(out.view(np.float64)).all()
+        assert np.abs(proj[5:] - ref_proj[5:]).max() <= 1e-10 and np.abs(beta[5:] - ref_beta[5:]).max() <= 1e-10
+        assert np.linalg.norm(out - be.V, axis=1).max() <= 1e-10
     h.close()
 
 
