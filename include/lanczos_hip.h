@@ -139,7 +139,10 @@ int lz_set_options(lz_handle h, int flags);
  *       loop at any size with the separate three-term kernel always (A/B, tests).  Where the fused form applies, n >= 4 and
  *       n <= 1023, the automatic choice takes its PAIR form - one walk over the basis per two steps, lz_last_one_sweep_pairs;
  *       6 and 7 never do; 8 the one-sweep loop at any size with pairs; 9 the same with 16 instead of 8 positions per lane in
- *       the pair walk on long vectors (A/B))
+ *       the pair walk on long vectors (A/B).  Where the pair form applies, n >= 6 and n <= 512, the automatic choice takes the
+ *       GROUP form instead - one walk over the basis per four steps, lz_last_one_sweep_quads; 6, 7, 8 and 9 never do; 10 the
+ *       one-sweep loop at any size with groups; 11 the same with 8 instead of 4 positions per lane in the group walk on long
+ *       vectors (A/B))
  *   16  rows per chunk of the CHUNKED Ritz mode (0 auto: chunked only when Y does not fit beside the basis; > 0 forces it: tests)
  *   11  two-sided Gram-Schmidt links (0 / 1: streaming kernel + fold kernel per link)
  *   17  fixed-K (stencil) SpMV layout: 0 auto (CSR-order kernel with products staged through LDS; the ELL-ordered second copy -
@@ -391,6 +394,16 @@ int lz_last_one_sweep_pairs(lz_handle h, int* pairs);
  * sweep, so the whole run was repeated on the single fused form (what was returned is that run's result, bit for bit).  The handle
  * remembers it until a matrix is set again: later runs take the single form at once and report 0 here. */
 int lz_last_pair_abandoned(lz_handle h, int* abandoned);
+/* One-sweep loop, group form: the number of group walks behind the result the last lz_run returned - from step 2 on, three plain
+ * Lanczos steps run with no walk at all and ONE walk over the basis then finishes four vectors, with coefficients predicted by the
+ * omega-recurrence over the extended set: (n - 2) / 4 groups; a tail of two steps runs as a pair (lz_last_one_sweep_pairs is then 1),
+ * a tail of one or three on the single form.  0 after the pair and single forms, after any other loop, and after a run that abandoned
+ * its groups.  lz_last_one_sweep_fused stays 1. */
+int lz_last_one_sweep_quads(lz_handle h, int* quads);
+/* 1 when the last lz_run tried the group form and a group's prediction missed by more than the gate (1e-14): a group has no correcting
+ * sweep, so the whole run was repeated on the pair form (which may itself fall back to the single form: lz_last_pair_abandoned).  The
+ * handle remembers it until a matrix is set again: later runs take the pair form at once and report 0 here. */
+int lz_last_quad_abandoned(lz_handle h, int* abandoned);
 /* Host evaluation of the one-sweep loop's per-step arithmetic (the device kernels' expressions, summed in index order; the
  * kernels add the same terms lane-strided through a fixed shuffle tree), for checks without a GPU.  G (symmetric) and H are n x n with column i at [i * n].  predict: chat[0..j] of step j + 1 from alpha_j, the
  * norm beta_j that formed v_j and nrm2 = ||w_{j+1}||^2.  post: col[0..j) = G[:j, j] of the v_j formed with chat from the

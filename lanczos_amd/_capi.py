@@ -143,6 +143,8 @@ SIGNATURES = {
     "lz_last_one_sweep_fused": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_last_one_sweep_pairs": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_last_pair_abandoned": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_one_sweep_quads": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_last_quad_abandoned": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_one_sweep_host_predict": (C.c_int, [C.c_int, C.c_int, _D, _D, C.c_double, C.c_double, C.c_double, _D]),
     "lz_one_sweep_host_post": (C.c_int, [C.c_int, C.c_int, _D, _D, _D, C.c_double, _D]),
     "lz_last_host_syncs": (C.c_int, [_P, _I64]),
@@ -717,6 +719,18 @@ class Handle:
         """one-sweep loop: 1 when the last run tried the pair form, a prediction missed the gate and the run was repeated on the single form"""
         k = C.c_int()
         self.check(self.lib.lz_last_pair_abandoned(self._h, C.byref(k)))
+        return k.value
+
+    def last_one_sweep_quads(self):
+        """one-sweep loop: group walks (one walk over the basis per four steps) behind the last run's result; 0 after a run that abandoned them"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_one_sweep_quads(self._h, C.byref(k)))
+        return k.value
+
+    def last_quad_abandoned(self):
+        """one-sweep loop: 1 when the last run tried the group form, a prediction missed the gate and the run was repeated on the pair form"""
+        k = C.c_int()
+        self.check(self.lib.lz_last_quad_abandoned(self._h, C.byref(k)))
         return k.value
 
     def last_host_syncs(self):

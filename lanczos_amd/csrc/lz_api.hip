@@ -565,7 +565,7 @@ int lz_set_tuning(lz_handle h, int index, int value) {
   // Retired A/B arms (built, measured slower, kept bit-identity-tested in the kernel-bench build): the one-kernel /
   // one-launch-per-step engines (15 = 2, 3, 5), the persistent and LDS-staged Ritz GEMMs (9 >= 2), the ticket / deferred-fold
   // two-sided links (11 >= 2), the row-block-group interleaving of the two-phase SpMV (22 >= 2: round 5, 8-110 % slower)
-  if ((index == 15 && value >= 2 && (value < 6 || value > 9)) || (index == 9 && value >= 2) || (index == 11 && value >= 2) || (index == 22 && value >= 2))
+  if ((index == 15 && value >= 2 && (value < 6 || value > 11)) || (index == 9 && value >= 2) || (index == 11 && value >= 2) || (index == 22 && value >= 2))
     return fail(h, LZ_ERR_ARG, "lz_set_tuning: this A/B arm was retired from the product library (build with KBENCH=1)");
 #endif
   if (value < 0) return fail(h, LZ_ERR_ARG, "lz_set_tuning: negative value");
@@ -854,6 +854,18 @@ int lz_last_one_sweep_pairs(lz_handle h, int* pairs) {
 int lz_last_pair_abandoned(lz_handle h, int* abandoned) {
   if (!h || !abandoned) return LZ_ERR_ARG;
   *abandoned = h->last_pair_abandoned;
+  return LZ_OK;
+}
+
+int lz_last_one_sweep_quads(lz_handle h, int* quads) {
+  if (!h || !quads) return LZ_ERR_ARG;
+  *quads = h->last_engine == 9 ? h->last_os_quads : 0;
+  return LZ_OK;
+}
+
+int lz_last_quad_abandoned(lz_handle h, int* abandoned) {
+  if (!h || !abandoned) return LZ_ERR_ARG;
+  *abandoned = h->last_quad_abandoned;
   return LZ_OK;
 }
 

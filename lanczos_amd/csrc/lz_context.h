@@ -211,7 +211,7 @@ struct lz_context {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
   hipEvent_t run_a = nullptr, run_b = nullptr;
   bool run_timed = false;
-  // the per-run record - last_engine, last_sweeps, last_misses, last_gate_trips, last_os_fused, last_os_pairs, last_pair_abandoned, sweep_log,
+  // the per-run record - last_engine, last_sweeps, last_misses, last_gate_trips, last_os_fused, last_os_pairs, last_pair_abandoned, last_os_quads, last_quad_abandoned, sweep_log,
   // host_syncs, r_state: reset in one place, RunFrame::begin (lz_loops.hip), by lz_run and by both resumes
   int last_sweeps = 0;
   std::vector<int> sweep_log;  // per step of the last lz_run: 1 = the re-orthogonalisation sweep ran (lz_last_sweep_log; device-decided loops only, else all 1)
@@ -220,14 +220,17 @@ struct lz_context {
   int r_state = 0;      // what d_r holds after the last run: 0 nothing usable, 1 the residual entering step n, 2 y = A v_{n-1} (three-term pending)
   Xfer* xfer = nullptr;        // staging ring of the large device -> host copies (lz_xfer.hip), created at the first one
   double* h_pinned = nullptr;  // 8 pinned doubles for the per-step scalar read-back of the host-decided partial-reorth loop (tune[18] == 1)
-  double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n); os_n = its n
-  int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run
+  double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n), the group form's predictions (4 (n + 4)); os_n = its n
+  int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run, [3] / [4] a pair's / a group's leftover exceeded tau
   int os_n = 0;
   int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
   int last_os_fused = 0;       // one-sweep loop: 1 = the last lz_run took the fused form (no three-term pass)
   int last_os_pairs = 0;       // one-sweep loop: pair walks (one walk per two steps) behind the last lz_run's result; 0 after a repeat
   int last_pair_abandoned = 0; // 1 = the last run (lz_run or a resume) tried the pair form, a leftover exceeded kOneSweepTau and the run was repeated on the single form
   bool pair_tripped = false;   // remembered until the matrix is set again: the pair form is not tried a second time
+  int last_os_quads = 0;       // one-sweep loop: group walks (one walk per four steps) behind the last lz_run's result; 0 after a repeat
+  int last_quad_abandoned = 0; // 1 = the last run tried the group form, a leftover exceeded kOneSweepTau and the run was repeated on the pair form
+  bool quad_tripped = false;   // remembered until the matrix is set again: the group form is not tried a second time
   double* d_om = nullptr;      // device-resident partial re-orthogonalisation: omega-recurrence state (omega_state_doubles)
   int* d_omi = nullptr;        //   ... gate of the coming step, sweep count, per-step sweep log (omega_state_ints)
   int om_n = 0;

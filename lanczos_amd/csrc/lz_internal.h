@@ -312,6 +312,26 @@ int launch_os_pair_sweep(double* V, int64_t ldv, int64_t len, int j, const doubl
                          const double* nrm2, const double* alpha0, double* part, bool wide16, hipStream_t s);
 void launch_os_pair_post(const double* d, int ldp, const double* chat, const double* kap, const double* p, double* G, double* H, int n, int j,
                          double* nrm2, const double* alpha_j, double tau, int* ist, double* elog, hipStream_t s);
+// Group form (run_loop_one_sweep_quad): one walk per four steps, j >= 2 the first step of the group; the arithmetic is one_sweep_group_lanczos's
+// at m = 4 (tools/one_sweep_group_prototype.py).  The walk parks 4 waves x 4 x os_quad_ldp(j) per-wave dots in LDS; the limit on the run
+// length follows from the LDS a launch may ask for without a raise (os_quad_max_ldp), and longer runs belong to the pair form.
+// predict: nrm2[0] = sum(part[0 .. np)) = ||z||^2 (b_3 = its root); alpha[0..2] = a_t, beta[0..2] = b_t as the chain left them;
+// gout[t * ldg ..] = g_t: [0, j) the predicted dots of x_t against the basis rows, [j, j + t) against x_0 .. x_{t-1}.  sweep: rows j .. j+3
+// of V (in: x_0 .. x_2 and, from z / b_3, x_3; out: v_j .. v_{j+3}), part[b * 4 ldp + t ldp + ..] = [V_i . x_t (i < j), v_{j+s} . x_t (s < t),
+// v_{j+t} . v_{j+t}]; wide8: 8 positions per lane instead of 4 on long vectors (A/B).  post: d = the runs' sums (launch_final_rows_t over
+// 4 ldp columns); G[:, j .. j+3], H[:, j-1 .. j+2], beta[3] = b_3, elog[j .. j+3], and ist[4] = 1 when a leftover exceeds tau (sticky).
+constexpr int kOneSweepQuadLds = 65536;
+inline size_t os_quad_lds_bytes(int ldp) { return (size_t)(kTPB / 64) * 4 * ldp * sizeof(double); }
+inline int os_quad_max_ldp() { return (int)(kOneSweepQuadLds / os_quad_lds_bytes(1)); }
+int os_quad_ldp(int j);
+int os_quad_sweep_blocks(int64_t len, bool wide8);
+void launch_os_quad_predict(const double* part, int np, double* nrm2, const double* chat, const double* G, const double* H, int n, int j,
+                            const double* alpha, const double* beta, double* gout, int ldg, hipStream_t s);
+int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* nrm2, double* part,
+                         bool wide8, hipStream_t s);
+// returns the error of the per-kernel LDS-limit raise (hipFuncSetAttribute), if that was needed and failed
+hipError_t launch_os_quad_post(const double* d, int ldp, const double* g, int ldg, double* G, double* H, int n, int j, const double* nrm2,
+                               const double* alpha, double* beta, double tau, int* ist, double* elog, hipStream_t s);
 // ---- device-resident partial re-orthogonalisation (Simon's omega-recurrence in a one-block kernel) ----
 // State: st[0] = ||A|| estimate, st[1] = force_next, st[2 .. 2 + n + 2) = hb (hb[k] = the norm that formed V[k]), then three
 // rows of n + 1 doubles (omega_{j,:} lives in row j % 3); ist[0] = the gate of the coming step (1: sweep), ist[1] = number of

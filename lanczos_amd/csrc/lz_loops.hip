@@ -466,14 +466,14 @@ int run_small_engine(lz_handle h, int n, const double* v0_local, bool steps, boo
 // One rank, fused-norm mode, full re-orthogonalisation, default kernels; lz_run_resume continues on the two-pass loop.
 // Where the matrix has a scale-on-read SpMV the fused form below runs instead (lz_set_tuning(h, 15, 7): this one always).
 struct OneSweepState {
-  double *G, *H, *chat, *g, *elog;
+  double *G, *H, *chat, *g, *elog, *gq;  // gq: the group form's predictions, 4 runs of n + 4
   int nb;
 };
 static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_blocks = 0) {
-  const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8;
+  const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8 + (size_t)4 * (n + 4);
   if (h->os_n < n) {
     LZ_TRY(dev_alloc(h, h->d_os, os_doubles));
-    LZ_TRY(dev_alloc(h, h->d_osi, 4));
+    LZ_TRY(dev_alloc(h, h->d_osi, 8));
     h->os_n = n;
   }
   st.nb = os_sweep_blocks(h->rows_pad);
@@ -484,8 +484,10 @@ static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_block
   st.chat = st.H + (size_t)n * n;
   st.g = st.chat + n + 1;
   st.elog = st.g + 2 * n + 2;
+  st.gq = st.elog + n + 1;
   LZ_HIP(h, hipMemsetAsync(h->d_os, 0, os_doubles * sizeof(double), h->stream));
-  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 4 * sizeof(int), h->stream));  // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate), [3] a pair's leftover exceeded tau
+  // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate), [3] a pair's leftover exceeded tau, [4] a group's
+  LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 8 * sizeof(int), h->stream));
   return LZ_OK;
 }
 // sweep (mode 0: units of u = w / beta, reads r and ||w||^2; mode 2: the fused form, see run_loop_one_sweep_fused), second-stage sums,
@@ -606,16 +608,51 @@ bool one_sweep_pair_applies(lz_handle h, int n) {
   const int knob = h->tune[15];
   return one_sweep_fused_applies(h, n) && knob != 6 && n >= 4 && qtw_ldp(n + 1) <= kOneSweepPairMaxLdp && !h->pair_tripped;
 }
-int run_loop_one_sweep_pair(lz_handle h, int n) {
+// one pair at steps j, j + 1 (2 <= j, j + 1 < n): three-term, speculative SpMV, predict, the pair walk, post, the closing SpMV
+static int one_sweep_pair_iter(lz_handle h, int n, int j, const OneSweepState& st, int nbp, bool wide16) {
   const double M = (double)h->rows;
+  double* kap = st.g;  // (the correcting sweep's coefficient buffers are free while a pair runs)
+  double* pp = st.g + n + 1;
+  const int* scale = h->d_osi + 2;  // (stays 0: the SpMVs always scale on read)
+  h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1);
+  // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-1} v_{j-2} -> d_r, ||w_j||^2 -> d_nrm2
+  LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
+  int npa = 0;
+  LZ_TRY(step_scaling_spmv(h, n, j, h->d_r, h->d_r2, scale, &npa));  // y° = A (w_j / b); the V[j] it stores is provisional
+  const int ldp = os_pair_ldp(j);
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_os_pair_predict(h->d_part, npa, h->d_alpha + j, h->d_nrm2, st.chat, st.G, st.H, n, j, kap, pp, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep pair predict"));
+  }
+  {
+    Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 40.0 * M, 8.0 * (j + 1) * M);
+    launch_os_pair_sweep(h->d_V, h->ldv, h->rows_pad, j, st.chat, kap, h->d_r, h->d_r2, h->d_nrm2, h->d_alpha + j, h->d_part, wide16, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep pair walk"));
+  }
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_final_rows_t(h->d_part, nbp, 2 * ldp, ldp + j + 2, h->d_c, h->stream);
+    LZ_TRY(check_launch(h, "final_rows(one-sweep pair)"));
+    launch_os_pair_post(h->d_c, ldp, st.chat, kap, pp, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, kOneSweepTau, h->d_osi, st.elog, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep pair post"));
+  }
+  LZ_TRY(step_scaling_spmv(h, n, j + 1, h->d_r2, h->d_r, scale, &npa));  // V[j+1] = u~_{j+1} / beta_{j+1}, y = A V[j+1]
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 1), st.G, st.H, n, j + 1, h->d_alpha + (j + 1), h->d_beta + j, st.chat, true,
+                          j + 2 < n, h->stream);
+    LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+  }
+  h->last_os_pairs += 1;
+  return LZ_OK;
+}
+int run_loop_one_sweep_pair(lz_handle h, int n) {
   const bool wide16 = h->tune[15] == 9;  // (A/B: 16 positions per lane on long vectors)
   OneSweepState st;
   const int nbp = os_pair_sweep_blocks(h->rows_pad, wide16);
   LZ_TRY(one_sweep_setup(h, n, st, nbp));
   h->last_os_fused = 1;
-  double* kap = st.g;  // (the correcting sweep's coefficient buffers are free while a pair runs)
-  double* pp = st.g + n + 1;
-  const int* scale = h->d_osi + 2;  // (stays 0: the SpMVs always scale on read)
   LZ_TRY(warm_up(h, true));
   for (int j = 0; j < n;) {
     if (j < 2 || j + 1 >= n) {
@@ -624,38 +661,101 @@ int run_loop_one_sweep_pair(lz_handle h, int n) {
       j += 1;
       continue;
     }
-    h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1);
-    // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-1} v_{j-2} -> d_r, ||w_j||^2 -> d_nrm2
+    LZ_TRY(one_sweep_pair_iter(h, n, j, st, nbp, wide16));
+    j += 2;
+  }
+  return one_sweep_fused_tail(h, n);
+}
+
+// The group form of the fused loop: ONE walk over the basis per FOUR steps (tools/one_sweep_group_prototype.py, one_sweep_group_lanczos at
+// m = 4; k_os_quad_predict / k_os_quad_sweep / k_os_quad_post, lz_reorth.hip).  A group at step j (2 <= j, j + 4 <= n):
+//   chain    three plain Lanczos steps with no walk - x_0 = w_j / b_0 and, for t < 3, y_t = A x_t, a_t = x_t . y_t,
+//            z = (y_t - a_t x_t) - b_t x_{t-1}, b_{t+1} = ||z||, x_{t+1} = z / b_{t+1} - by the launches of a step that does not sweep: the
+//            scaling SpMV (which stores x_t into row j + t), the alpha sum, k_three_term, the ||.||^2 sum.  alpha_{j+t} = a_t, beta = b_t.
+//   predict  the omega-recurrence over the extended set [V_0 .. V_{j-1}, x_0 .. x_3] with the full H: every dot of x_t against the rows
+//            before it, to O(eps^2), from G, H, chat and the chain's scalars (one block; it also sums the last ||z||^2)
+//   walk     rows 0 .. j-1 once, four running sums and four dots per position; its epilogue finishes v_j .. v_{j+3}
+//   post     the leftovers against the gate, G[:, j .. j+3], H[:, j-1 .. j+2] (one block)
+//   closing  the plain SpMV on the corrected V[j+3]; its alpha sum predicts the next chat as after any step
+// z differs from the two-pass loop's w_{j+t} by a vector of span(V_0 .. V_{j+t-1}) plus O(eps^2), and projecting that span out of either
+// gives the same v_{j+t}: coefficients and basis equal the two-pass loop's to rounding.  8 j M + 64 M bytes of walk per group where two
+// pair walks move 16 j M + 80 M.  Steps 0 and 1 are the single fused form's; a tail of two steps is a pair, a tail of one or three runs
+// on the single fused form.  A group has no correcting sweep: a leftover above kOneSweepTau sets a sticky device flag, and lz_run repeats
+// the run on the pair form (and remembers it until the matrix is set again).
+bool one_sweep_quad_applies(lz_handle h, int n) {
+  const int knob = h->tune[15];
+  return one_sweep_pair_applies(h, n) && knob != 8 && knob != 9 && n >= 6 && os_quad_ldp(n - 4) <= os_quad_max_ldp() && !h->quad_tripped;
+}
+int run_loop_one_sweep_quad(lz_handle h, int n) {
+  const double M = (double)h->rows;
+  const bool wide8 = h->tune[15] == 11;  // (A/B: 8 positions per lane on long vectors)
+  OneSweepState st;
+  const int nbp = os_pair_sweep_blocks(h->rows_pad, false), nbq = os_quad_sweep_blocks(h->rows_pad, wide8);
+  LZ_TRY(one_sweep_setup(h, n, st, std::max(nbp, 2 * nbq)));
+  h->last_os_fused = 1;
+  const int ldg = n + 4;
+  LZ_TRY(warm_up(h, true));
+  for (int j = 0; j < n;) {
+    if (j >= 2 && n - j == 2 && (n - 2) % 4 == 2) {  // (a tail of two steps; the last two of a tail of three are single steps)
+      LZ_TRY(one_sweep_pair_iter(h, n, j, st, nbp, false));
+      j += 2;
+      continue;
+    }
+    if (j < 2 || j + 4 > n) {
+      begin_iter(h, j);
+      LZ_TRY(one_sweep_fused_iter(h, n, j, st));
+      j += 1;
+      continue;
+    }
+    h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1) || iter_sampled(h, j + 2) || iter_sampled(h, j + 3);
+    // the chain: w_j -> d_r; then x_t = src / b_t -> V[j + t], y_t -> the other residual buffer, z in place there
     LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
-    int npa = 0;
-    LZ_TRY(step_scaling_spmv(h, n, j, h->d_r, h->d_r2, scale, &npa));  // y° = A (w_j / b); the V[j] it stores is provisional
-    const int ldp = os_pair_ldp(j);
+    double* src = h->d_r;
+    double* dst = h->d_r2;
+    int npz = 0;
+    for (int t = 0; t < 3; ++t) {
+      int npa = 0;
+      LZ_TRY(step_scaling_spmv(h, n, j + t, src, dst, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
+      LZ_TRY(step_final_sum(h, npa, h->d_alpha + (j + t), "final_sum(alpha)"));
+      // z = (y_t - a_t x_t) - b_t x_{t-1}; the last ||z||^2 is summed by the predict kernel
+      LZ_TRY(step_three_term(h, j + t, j + t - 1, h->d_alpha + (j + t), h->d_beta + (j + t - 1), t < 2, &npz, dst));
+      std::swap(src, dst);
+    }
+    const double* z = src;  // (d_r2: three steps from d_r)
+    const int ldp = os_quad_ldp(j);
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_pair_predict(h->d_part, npa, h->d_alpha + j, h->d_nrm2, st.chat, st.G, st.H, n, j, kap, pp, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep pair predict"));
+      launch_os_quad_predict(h->d_part, npz, h->d_nrm2, st.chat, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + (j - 1), st.gq, ldg, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep group predict"));
     }
     {
-      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 40.0 * M, 8.0 * (j + 1) * M);
-      launch_os_pair_sweep(h->d_V, h->ldv, h->rows_pad, j, st.chat, kap, h->d_r, h->d_r2, h->d_nrm2, h->d_alpha + j, h->d_part, wide16, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep pair walk"));
+      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 64.0 * M, 16.0 * (j + 1) * M);
+      launch_os_quad_sweep(h->d_V, h->ldv, h->rows_pad, j, st.gq, ldg, z, h->d_nrm2, h->d_part, wide8, h->stream);
+      LZ_TRY(check_launch(h, "one-sweep group walk"));
     }
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_final_rows_t(h->d_part, nbp, 2 * ldp, ldp + j + 2, h->d_c, h->stream);
-      LZ_TRY(check_launch(h, "final_rows(one-sweep pair)"));
-      launch_os_pair_post(h->d_c, ldp, st.chat, kap, pp, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, kOneSweepTau, h->d_osi, st.elog, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep pair post"));
+      launch_final_rows_t(h->d_part, nbq, 4 * ldp, 3 * ldp + j + 4, h->d_c, h->stream);
+      LZ_TRY(check_launch(h, "final_rows(one-sweep group)"));
+      LZ_HIP(h, launch_os_quad_post(h->d_c, ldp, st.gq, ldg, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, h->d_beta + (j - 1), kOneSweepTau, h->d_osi,
+                                    st.elog, h->stream));
+      LZ_TRY(check_launch(h, "one-sweep group post"));
     }
-    LZ_TRY(step_scaling_spmv(h, n, j + 1, h->d_r2, h->d_r, scale, &npa));  // V[j+1] = u~_{j+1} / beta_{j+1}, y = A V[j+1]
-    {
+    {  // closing: y = A V[j+3] -> d_r (V[j+3] is in place: the plain ELL product), alpha_{j+3} and the next chat
+      double* vj = basis_row(h, j + 3);
+      int npa = 0;
+      {
+        Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true), spmv_flops(h));
+        npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream);
+        LZ_TRY(check_launch(h, "spmv(ell)"));
+      }
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 1), st.G, st.H, n, j + 1, h->d_alpha + (j + 1), h->d_beta + j, st.chat, true,
-                            j + 2 < n, h->stream);
+      launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true,
+                            j + 4 < n, h->stream);
       LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
     }
-    h->last_os_pairs += 1;
-    j += 2;
+    h->last_os_quads += 1;
+    j += 4;
   }
   return one_sweep_fused_tail(h, n);
 }
@@ -699,8 +799,9 @@ Loop choose_loop(lz_handle h, int n, const QtwPlan* plan = nullptr) {
 #endif
   // one-sweep loop: one rank, full fused-norm re-orthogonalisation, default kernels, no overlap; tune[15] == 6 forces it at any size
   const bool one_sweep_ok = one_rank && full_fused && default_kernels && !(f & LZ_FLAG_OVERLAP_HALO) && n >= 2 && n <= kOneSweepMaxN;
-  // (7: never the fused form; 6: never the pair form; 8 / 9: the pair form where it applies, 8 / 16 positions per lane in its walk - A/B)
-  if (h->tune[15] >= 6 && h->tune[15] <= 9 && one_sweep_ok) return LOOP_ONE_SWEEP;
+  // (7: never the fused form; 6: never the pair form; 8 / 9: the pair form where it applies, 8 / 16 positions per lane in its walk - A/B;
+  // 10 / 11: the group form where it applies, 4 / 8 positions per lane in its walk - A/B)
+  if (h->tune[15] >= 6 && h->tune[15] <= 11 && one_sweep_ok) return LOOP_ONE_SWEEP;
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
   if (one_rank && qp.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)qp.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;
@@ -1119,6 +1220,8 @@ struct RunFrame {
     h->last_os_fused = 0;
     h->last_os_pairs = 0;
     h->last_pair_abandoned = 0;
+    h->last_os_quads = 0;
+    h->last_quad_abandoned = 0;
     h->sweep_log.assign((size_t)n, 1);  // which steps ran the sweep (lz_last_sweep_log): all of them unless a partial loop says otherwise
     h->host_syncs = 0;
     h->r_state = 0;
@@ -1163,7 +1266,7 @@ static int upload_checkpoint(lz_handle h, int j0, const double* V_rows, int64_t 
 }
 
 // One pass of lz_run.  *again: the pass's own check says its coefficients do not hold; what makes the next pass take another loop is set
-// (LZ_FLAG_ONE_REDUCE cleared, or h->pair_tripped), nothing is on the books, and lz_run makes that pass.
+// (LZ_FLAG_ONE_REDUCE cleared, or h->quad_tripped / h->pair_tripped), nothing is on the books, and lz_run makes that pass.
 static int run_once(lz_handle h, int n, const double* v0_local, double* alpha_out, double* beta_out, bool* again) {
   *again = false;
   RunFrame fr{h, n};
@@ -1172,7 +1275,7 @@ static int run_once(lz_handle h, int n, const double* v0_local, double* alpha_ou
   LZ_TRY(fr.uploaded());
   const Loop loop = choose_loop(h, n);
   const bool one_reduce = loop == LOOP_ONE_REDUCE || loop == LOOP_PARTIAL_ONE_REDUCE;
-  bool tried_pairs = false;
+  bool tried_pairs = false, tried_quads = false;
   h->last_engine = (int)loop;
   switch (loop) {
 #ifdef LZ_KBENCH
@@ -1194,17 +1297,22 @@ static int run_once(lz_handle h, int n, const double* v0_local, double* alpha_ou
     case LOOP_PARTIAL_ONE_REDUCE: LZ_TRY(run_loop_partial_onereduce(h, n)); break;
     case LOOP_ONE_SWEEP:
       tried_pairs = one_sweep_pair_applies(h, n);
-      LZ_TRY(tried_pairs ? run_loop_one_sweep_pair(h, n) : one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n) : run_loop_one_sweep(h, n));
+      tried_quads = one_sweep_quad_applies(h, n);  // (its tail of two steps is a pair: both flags are read)
+      LZ_TRY(tried_quads   ? run_loop_one_sweep_quad(h, n)
+             : tried_pairs ? run_loop_one_sweep_pair(h, n)
+             : one_sweep_fused_applies(h, n) ? run_loop_one_sweep_fused(h, n)
+                                             : run_loop_one_sweep(h, n));
       break;
     default: LZ_TRY(run_loop_six(h, n)); break;
   }
   double onered_bad = 0.0;
-  int pair_flag = 0;
+  int pair_flag = 0, quad_flag = 0;
   std::vector<int> dev_log(loop == LOOP_PARTIAL_DEVICE ? omega_state_ints(n) : loop == LOOP_PARTIAL_ONE_REDUCE ? omega_onered_ints(n) : 0);
   std::vector<RunExtra> extras;
   if (one_reduce) extras.push_back({&onered_bad, h->d_nrm2 + 1, sizeof(double)});
   if (loop == LOOP_ONE_SWEEP) extras.push_back({&h->last_gate_trips, h->d_osi + 1, sizeof(int)});
   if (tried_pairs) extras.push_back({&pair_flag, h->d_osi + 3, sizeof(int)});
+  if (tried_quads) extras.push_back({&quad_flag, h->d_osi + 4, sizeof(int)});
   if (!dev_log.empty()) extras.push_back({dev_log.data(), h->d_omi, dev_log.size() * sizeof(int)});
   LZ_TRY(fr.drain(alpha_out, beta_out, extras));
   if (loop == LOOP_SIX && (h->flags & LZ_FLAG_REORTH_PARTIAL)) h->sweep_log.clear();  // (the host-decided loop keeps no per-step record)
@@ -1215,6 +1323,13 @@ static int run_once(lz_handle h, int n, const double* v0_local, double* alpha_ou
     // many digits at some step (|alpha| >> beta).  Every rank sees the same reduced sums, so every rank takes this branch:
     // the solve is repeated on the default loop (two all-reduces per iteration), whose coefficients hold the bar.
     h->flags &= ~LZ_FLAG_ONE_REDUCE;
+    *again = true;
+    return LZ_OK;
+  }
+  if (quad_flag) {
+    // a group's prediction missed by more than kOneSweepTau (k_os_quad_post): a group has no correcting sweep, so the whole solve is
+    // repeated on the pair form (which may itself fall back to the single form); remembered until the matrix is set again
+    h->quad_tripped = true;
     *again = true;
     return LZ_OK;
   }
@@ -1290,12 +1405,13 @@ int lz_run(lz_handle h, int n, const double* v0_local, double* alpha_out, double
   if (n < 2) return fail(h, LZ_ERR_ARG, "lz_run: n must be >= 2 (the reference's beta array has n-1 entries)");
   if (n > h->Mg) return fail(h, LZ_ERR_ARG, "lz_run: n cannot be larger than M");
   const int keep = h->flags;
-  const bool tripped = h->pair_tripped;
+  const bool tripped = h->pair_tripped, qtripped = h->quad_tripped;
   bool again = false;
   int rc;
   do rc = run_once(h, n, v0_local, alpha_out, beta_out, &again);  // a second pass where the first one's own check asks for it
   while (again);
   if (h->pair_tripped != tripped) h->last_pair_abandoned = 1;
+  if (h->quad_tripped != qtripped) h->last_quad_abandoned = 1;
   if (h->flags != keep) h->last_engine = LOOP_ONE_REDUCE_REPEATED;
   h->flags = keep;
   return rc;

@@ -33,6 +33,7 @@ int finish_csr(lz_handle h, const int32_t* rowptr_host, int64_t M_global, int64_
   h->has_T = false;
   h->bi_n = 0;
   h->pair_tripped = false;  // (the one-sweep loop's pair form is tried afresh on a new matrix)
+  h->quad_tripped = false;  // (... and its group form)
   h->Mg = M_global;
   h->row0 = row0;
   h->rows = rows_local;

@@ -2111,4 +2111,432 @@ void launch_os_pair_post(const double* d, int ldp, const double* chat, const dou
   hipLaunchKernelGGL(k_os_pair_post, dim3(1), dim3(kFinalThreads), lds, s, d, ldp, chat, kap, p, G, H, n, j, nrm2, alpha_j, tau, ist, elog);
 }
 
+// ------------------------------------------------------------------ one-sweep loop, group form: one walk per FOUR steps
+// (run_loop_one_sweep_quad, lz_loops.hip; the arithmetic is tools/one_sweep_group_prototype.py's one_sweep_group_lanczos at m = 4, name for
+// name.)  The chain has left x_0 .. x_2 in rows j .. j+2 of the basis, z = b_3 x_3 in a residual buffer, a_t in alpha[j + t], b_0 .. b_2 in
+// their beta slots and the partials of ||z||^2 in part.
+//
+// k_os_quad_predict, one block: nrm2[0] = ||z||^2 (b_3 = its root), then the omega-recurrence over the extended set
+// [V_0 .. V_{j-1}, x_0 .. x_3] with the full H: g_0[:j] = chat / b_0 and for t = 0, 1, 2
+//   g_{t+1}[i] = ((sum_{l<j} H[l, i] g_t[l] (+ b_0 g_t[x_0] at i = j - 1) - a_t g_t[i]) - b_t g_{t-1}[i]) / b_{t+1}     (i < j; g_{-1} = G[:, j-1])
+//   g_{t+1}[x_s] = (((b_{s+1} g_t[x_{s+1}] + a_s g_t[x_s]) + b_s g_t[x_{s-1}]) - a_t g_t[x_s]) - b_t g_{t-1}[x_s]) / b_{t+1}   (s < t)
+//   g_{t+1}[x_t] = -b_t g_t[x_{t-1}] / b_{t+1}
+// (the diagonal is 1, x_{-1} = V_{j-1}).  g_t goes to gout[t * ldg ..]: [0, j) the rows of the basis, j + s the in-group row x_s.
+__global__ __launch_bounds__(kFinalThreads) void k_os_quad_predict(const double* __restrict__ part, int np, double* __restrict__ nrm2,
+                                                                  const double* __restrict__ chat, const double* __restrict__ G,
+                                                                  const double* __restrict__ H, int n, int j, const double* __restrict__ alpha,
+                                                                  const double* __restrict__ beta, double* __restrict__ gout, int ldg) {
+  extern __shared__ double smem[];  // g_0 .. g_3, j + 4 each
+  const int L = j + 4;
+  __shared__ double sm[kFinalThreads / 64];
+  __shared__ double s_n;
+  const double t0 = final_sum_1024(part, np, sm);
+  if (threadIdx.x == 0) {
+    nrm2[0] = t0;
+    s_n = t0;
+  }
+  __syncthreads();
+  const double b[4] = {beta[0], beta[1], beta[2], sqrt(s_n)};
+  const double a[3] = {alpha[0], alpha[1], alpha[2]};
+  for (int i = threadIdx.x; i < 4 * L; i += blockDim.x) smem[i] = i < j ? chat[i] / b[0] : 0.0;
+  __syncthreads();
+  const double* gm = G + (int64_t)(j - 1) * n;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const double* gt = smem + t * L;
+    const double* gp = t ? smem + (t - 1) * L : gm;
+    double* gn = smem + (t + 1) * L;
+    os_wave_dots(
+        j, [&](int i) { return H + (int64_t)i * n; }, [&](int l) { return gt[l]; }, [&](int i) { return min(i + 2, j); },
+        [&](int i, double s) {
+          if (i == j - 1) s = s + b[0] * (t ? gt[j] : 1.0);  // column j - 1 of the extended H has b_0 in row x_0
+          gn[i] = ((s - a[t] * gt[i]) - b[t] * gp[i]) / b[t + 1];
+        });
+    if (threadIdx.x == 0) {
+      for (int s = 0; s < t; ++s) {
+        const double up = s + 1 == t ? 1.0 : gt[j + s + 1];
+        const double lo = s ? gt[j + s - 1] : gt[j - 1];
+        const double pv = s == t - 1 ? 1.0 : gp[j + s];
+        gn[j + s] = ((((b[s + 1] * up + a[s] * gt[j + s]) + b[s] * lo) - a[t] * gt[j + s]) - b[t] * pv) / b[t + 1];
+      }
+      const double lo = t ? gt[j + t - 1] : gt[j - 1];
+      gn[j + t] = -(b[t] * lo) / b[t + 1];
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < 4 * L; i += blockDim.x) gout[(i / L) * ldg + i % L] = smem[i];
+}
+
+void launch_os_quad_predict(const double* part, int np, double* nrm2, const double* chat, const double* G, const double* H, int n, int j,
+                            const double* alpha, const double* beta, double* gout, int ldg, hipStream_t s) {
+  const size_t lds = (size_t)4 * (j + 4) * sizeof(double);
+  hipLaunchKernelGGL(k_os_quad_predict, dim3(1), dim3(kFinalThreads), lds, s, part, np, nrm2, chat, G, H, n, j, alpha, beta, gout, ldg);
+}
+
+// The NV (a power of two, <= 32) lane partials of a trip, added over the wave JOINTLY: a halving butterfly - at every stage a lane keeps
+// one half of its values and hands the other half to the lane `off` away - until one value per lane is left, then a plain butterfly over
+// the lanes that hold the same value.  NV - 1 + log2(64 / NV) shuffle-adds where NV trees take 6 NV; the tree is fixed (reruns are
+// bit-identical).  Returns the sum of value quad_slot(lane), valid in the lanes with quad_writer(lane).
+template <int NV>
+__device__ __forceinline__ double quad_joint_sum(double (&v)[NV], int lane) {
+  int off = 32;
+#pragma unroll
+  for (int cnt = NV; cnt > 1; cnt >>= 1, off >>= 1) {
+    const bool hi = (lane & off) != 0;
+#pragma unroll
+    for (int i = 0; i < cnt / 2; ++i) {
+      const double send = hi ? v[i] : v[i + cnt / 2];
+      const double mine = hi ? v[i + cnt / 2] : v[i];
+      v[i] = mine + __shfl_xor(send, off, 64);
+    }
+  }
+#pragma unroll
+  for (; off > 0; off >>= 1) v[0] = v[0] + __shfl_xor(v[0], off, 64);
+  return v[0];
+}
+template <int NV>
+__device__ __forceinline__ int quad_slot(int lane) {  // which of the NV values this lane ends up with
+  int idx = 0, off = 32;
+#pragma unroll
+  for (int cnt = NV; cnt > 1; cnt >>= 1, off >>= 1)
+    if (lane & off) idx += cnt / 2;
+  return idx;
+}
+template <int NV>
+__device__ __forceinline__ bool quad_writer(int lane) { return (lane & (64 / NV - 1)) == 0; }
+
+// The one walk of a group (j >= 2): k_os_pair_sweep's slice-owner shape with FOUR vectors, x_0 .. x_2 = rows j .. j+2 as the chain left
+// them and x_3 = z / b_3 (zbuf; b_3 = sqrt(nrm2[0])).  Every row 0 .. j-1 is loaded once: four running sums (g_t against the row) and four
+// dots (the row against x_t) per position.  The 4 RU lane partials of a trip are added jointly (quad_joint_sum).  Epilogue:
+// r_t = x_t - sum_i g_t[i] V_i, v_{j+t} = r_t - sum_{s<t} g_t[x_s] v_{j+s} -> rows j .. j+3 (each position is read and written by the same
+// lane), and the dots v_{j+s} . x_t (s < t) and v_{j+t} . v_{j+t}.  Per wave in LDS, one run of 4 ldp doubles per block in part; run t:
+// [V_i . x_t (i < j), v_{j+s} . x_t (s < t), v_{j+t} . v_{j+t}].  Positions are 32-bit (n2 < 2^30); out-of-range positions are clamped to a
+// valid address and zeroed, so they add nothing (what they read may be mid-update: it is discarded).
+template <int P, int RU>
+__global__ __launch_bounds__(kTPB) void k_os_quad_sweep(double* __restrict__ V, int64_t ldv, int n2, int j, const double* __restrict__ g, int ldg,
+                                                       const double* __restrict__ zbuf, const double* __restrict__ nrm2, int ldp,
+                                                       double* __restrict__ part) {
+  extern __shared__ double keep[];  // [kTPB / 64][4 ldp]: this block's per-wave dots
+  constexpr int NV = 4 * RU;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * (kTPB * P) + threadIdx.x;
+  const int64_t ld2 = ldv >> 1;
+  double2* V2 = reinterpret_cast<double2*>(V);
+  double* kw = keep + wv * 4 * ldp;
+  int pos[P];
+  bool ok[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    ok[p] = base + (int64_t)p * kTPB < n2;
+    pos[p] = ok[p] ? (int)(base + (int64_t)p * kTPB) : n2 - 1;  // valid address, result discarded
+  }
+  const double b3 = sqrt(nrm2[0]);
+  double2 x[4][P];
+  double sx[4][P], sy[4][P];
+  {
+    const double2* z2 = reinterpret_cast<const double2*>(zbuf);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) x[t][p] = V2[(int64_t)(j + t) * ld2 + pos[p]];
+      const double2 zz = z2[pos[p]];
+      x[3][p] = make_double2(zz.x / b3, zz.y / b3);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (!ok[p]) x[t][p] = make_double2(0.0, 0.0);  // so the clamped duplicates add nothing to the dots
+        sx[t][p] = 0.0;
+        sy[t][p] = 0.0;
+      }
+    }
+  }
+  const int slot = quad_slot<NV>(lane), su = slot >> 2, st = slot & 3;
+  const bool writer = quad_writer<NV>(lane);
+  for (int k = 0; k < j; k += RU) {
+    double2 q[RU][P];
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (k + u < j) {  // block-uniform
+        const double2* row = V2 + (int64_t)(k + u) * ld2;
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[u][p] = ld_stream<1>(row + pos[p]);
+      }
+    double d[NV];
+#pragma unroll
+    for (int u = 0; u < RU; ++u) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) d[u * 4 + t] = 0.0;
+      if (k + u < j) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const double c = g[t * ldg + k + u];
+          double dd = 0.0;
+#pragma unroll
+          for (int p = 0; p < P; ++p) {
+            sx[t][p] = fma(c, q[u][p].x, sx[t][p]);  // (fused: the walk's arithmetic is a third shorter, the sums a rounding closer)
+            sy[t][p] = fma(c, q[u][p].y, sy[t][p]);
+            dd = fma(q[u][p].x, x[t][p].x, dd);
+            dd = fma(q[u][p].y, x[t][p].y, dd);
+          }
+          d[u * 4 + t] = dd;
+        }
+      }
+    }
+    const double tot = quad_joint_sum<NV>(d, lane);
+    if (writer && k + su < j) kw[st * ldp + k + su] = tot;
+  }
+  double gi[4][4];  // gi[t][s] = g_t[x_s], s < t
+#pragma unroll
+  for (int t = 1; t < 4; ++t)
+#pragma unroll
+    for (int s = 0; s < t; ++s) gi[t][s] = g[t * ldg + j + s];
+  double mm[4][4], vv[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    vv[t] = 0.0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) mm[t][s] = 0.0;
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    double2 v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      v[t] = make_double2(x[t][p].x - sx[t][p], x[t][p].y - sy[t][p]);
+#pragma unroll
+      for (int s = 0; s < t; ++s) {
+        v[t].x = v[t].x - gi[t][s] * v[s].x;
+        v[t].y = v[t].y - gi[t][s] * v[s].y;
+      }
+    }
+    if (ok[p]) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        st_stream<1>(V2 + (int64_t)(j + t) * ld2 + pos[p], v[t]);
+        vv[t] = fma(v[t].x, v[t].x, vv[t]);
+        vv[t] = fma(v[t].y, v[t].y, vv[t]);
+#pragma unroll
+        for (int s = 0; s < t; ++s) {
+          mm[t][s] = fma(v[s].x, x[t][p].x, mm[t][s]);
+          mm[t][s] = fma(v[s].y, x[t][p].y, mm[t][s]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const double a = wave_sum(vv[t]);
+    if (lane == 0) kw[t * ldp + j + t] = a;
+#pragma unroll
+    for (int s = 0; s < t; ++s) {
+      const double m = wave_sum(mm[t][s]);
+      if (lane == 0) kw[t * ldp + j + s] = m;
+    }
+  }
+  __syncthreads();
+  double* mine = part + (int64_t)blockIdx.x * (4 * ldp);
+  for (int i = threadIdx.x; i < 4 * ldp; i += kTPB) {
+    const bool used = i % ldp <= j + i / ldp;  // (the unused slots leave as zeros, not as whatever the LDS held)
+    const double t = used ? ((keep[i] + keep[4 * ldp + i]) + keep[8 * ldp + i]) + keep[12 * ldp + i] : 0.0;
+    __builtin_nontemporal_store(t, mine + i);
+  }
+}
+
+// positions per lane of the group walk: 4 (two waves per SIMD) or 8 (one wave) for long vectors - wide8 chooses -, else os_sweep_p's choice
+static int os_quad_sweep_p(int64_t n2, bool wide8) {
+  const int P = os_sweep_p(n2);
+  return P >= 8 ? (wide8 ? 8 : 4) : P;
+}
+int os_quad_sweep_blocks(int64_t len, bool wide8) {
+  const int64_t n2 = len >> 1;
+  const int P = os_quad_sweep_p(n2, wide8);
+  return (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+}
+int os_quad_ldp(int j) { return qtw_ldp(j + 4); }
+
+int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* nrm2, double* part,
+                         bool wide8, hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  const int P = os_quad_sweep_p(n2, wide8);
+  const int grid = (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
+  const int ldp = os_quad_ldp(j);
+  const size_t lds = os_quad_lds_bytes(ldp);  // <= kOneSweepQuadLds (os_quad_max_ldp): within what a kernel may ask for by default
+#define LZ_OSQ_GO(PP, RR) \
+  hipLaunchKernelGGL((k_os_quad_sweep<PP, RR>), dim3(grid), dim3(kTPB), lds, s, V, ldv, (int)n2, j, g, ldg, z, nrm2, ldp, part)
+  switch (P) {
+    case 8: LZ_OSQ_GO(8, 1); break;
+    case 4: LZ_OSQ_GO(4, 2); break;
+    case 2: LZ_OSQ_GO(2, 4); break;
+    default: LZ_OSQ_GO(1, 4); break;  // (eight rows a trip are 32 partials to add jointly: that instantiation spills)
+  }
+#undef LZ_OSQ_GO
+  return grid;
+}
+
+// k_os_quad_post, one block: d = the second-stage sums of the walk's four runs (run length ldp), gin the predictions.  Leftovers:
+// e_old = max |d_t[i] - g_t[i]| (i < j), e_in = max |v_{j+s} . x_t - g_t[x_s]|.  With C_t = [g_t, 1] the coefficients of x_t in the
+// finished basis, the new columns of G: G[i, j+t] = d_t[i] - sum_{r<j+t} G[i, r] C_t[r] - the sums over the old columns by os_wave_dots, the
+// in-group columns (kept in LDS until all four are done) added one t after the other -, G[j+t, j+t] = v_{j+t} . v_{j+t}; and of H:
+// H[:, j-1] += b_0 C_0, H[:, j+t] = ((b_{t+1} C_{t+1} + a_t C_t) + b_t C_{t-1}) - sum_{r<j+t} C_t[r] H[:, r] for t < 3 (b_0 e_{j-1} in place
+// of b_0 C_{-1}); the sums along the rows of the old columns of H are k_os_pair_predict's mu (chunks added in order).  beta[3] = b_3.
+// A group has no correcting sweep: a leftover above tau (or a NaN) sets the sticky flag ist[4], and lz_run repeats the run on the pair form.
+__global__ __launch_bounds__(kFinalThreads) void k_os_quad_post(const double* __restrict__ d, int ldp, const double* __restrict__ gin, int ldg,
+                                                               double* __restrict__ G, double* __restrict__ H, int n, int j,
+                                                               const double* __restrict__ nrm2, const double* __restrict__ alpha,
+                                                               double* __restrict__ beta, double tau, int* __restrict__ ist,
+                                                               double* __restrict__ elog) {
+  extern __shared__ double smem[];  // C_0 .. C_3, the new columns of G, the new columns of H: 4 x L each; the chunk sums (kFinalThreads)
+  const int L = j + 6;
+  double* C = smem;
+  double* col = C + 4 * L;
+  double* hn = col + 4 * L;  // hn[0]: column j - 1, hn[1 + t]: column j + t (t < 3)
+  double* red = hn + 4 * L;
+  __shared__ double smax[2][kFinalThreads / 64];
+  __shared__ double s_in[6];
+  const double b[4] = {beta[0], beta[1], beta[2], sqrt(nrm2[0])};
+  const double a[3] = {alpha[0], alpha[1], alpha[2]};
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  auto wave_max = [&](double em, double* dst) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) em = fmax(em, __shfl_down(em, off, 64));
+    if (lane == 0) dst[wv] = em;
+  };
+  double e_old = 0.0, e_in = 0.0;
+  for (int i = threadIdx.x; i < 4 * L; i += blockDim.x) {
+    const int t = i / L, r = i % L;
+    double c = 0.0;
+    if (r < j + t) {
+      c = gin[t * ldg + r];
+      const double e = fabs(d[t * ldp + r] - c);
+      if (r < j)
+        e_old = e == e ? fmax(e_old, e) : __builtin_inf();  // (a NaN leftover must trip: fmax would drop it)
+      else
+        e_in = e == e ? fmax(e_in, e) : __builtin_inf();
+    } else if (r == j + t) {
+      c = 1.0;
+    }
+    C[i] = c;
+    col[i] = 0.0;
+    hn[i] = 0.0;
+  }
+  wave_max(e_old, smax[0]);
+  wave_max(e_in, smax[1]);
+  __syncthreads();
+  // ---- G: the sums over the old columns, then the in-group terms
+#pragma unroll 1
+  for (int t = 0; t < 4; ++t) {
+    const double* Ct = C + t * L;
+    double* ct = col + t * L;
+    os_wave_dots(
+        j, [&](int i) { return (const double*)(G + (int64_t)i * n); }, [&](int l) { return Ct[l]; }, [&](int) { return j; },
+        [&](int i, double s) { ct[i] = d[t * ldp + i] - s; });
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int t = 0; t < 4; ++t) {
+    const double* Ct = C + t * L;
+    double* ct = col + t * L;
+    for (int i = threadIdx.x; i < j; i += blockDim.x) {
+      double v = ct[i];
+      for (int s = 0; s < t; ++s) v = v - col[s * L + i] * Ct[j + s];
+      ct[i] = v;
+    }
+    if (wv < t) {  // row j + s of the old columns is column s of this group: sum_{r<j} G[j+s, r] C_t[r], one wave per s
+      const double* cs = col + wv * L;
+      double acc = 0.0;
+      for (int l = lane; l < j; l += 64) acc = fma(cs[l], Ct[l], acc);
+      acc = wave_sum(acc);
+      if (lane == 0) s_in[wv] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int s = 0; s < t; ++s) {
+        double v = d[t * ldp + j + s] - s_in[s];
+        for (int q = 0; q < t; ++q) v = v - col[max(s, q) * L + j + min(s, q)] * Ct[j + q];  // G[j+s, j+q] of the columns already done
+        ct[j + s] = v;
+      }
+      ct[j + t] = d[t * ldp + j + t];
+    }
+    __syncthreads();
+  }
+  // ---- H: hn[1 + t][l] starts as sum_{r<j-1} H[l, r] C_t[r] (l < j)
+  {
+    const int Lp = (j + 63) & ~63, nchunk = kFinalThreads / Lp;  // j <= 512 (os_quad_max_ldp)
+    const int l = threadIdx.x % Lp, ch = threadIdx.x / Lp;
+#pragma unroll 1
+    for (int t = 0; t < 3; ++t) {
+      const double* Ct = C + t * L;
+      if (ch < nchunk) {
+        double acc = 0.0;
+        if (l < j) {
+          int i = ch;  // H[l, i] is 0 for i < l - 1: start at the first column of this chunk that is not
+          if (i < l - 1) i += (l - 1 - i + nchunk - 1) / nchunk * nchunk;
+          for (; i < j - 1; i += nchunk) acc = fma(H[(int64_t)i * n + l], Ct[i], acc);
+        }
+        red[ch * Lp + l] = acc;
+      }
+      __syncthreads();
+      if (threadIdx.x < j) {
+        double m = 0.0;
+        for (int c = 0; c < nchunk; ++c) m += red[c * Lp + threadIdx.x];
+        hn[(1 + t) * L + threadIdx.x] = m;
+      }
+      __syncthreads();
+    }
+  }
+  {
+    const double* hc = H + (int64_t)(j - 1) * n;
+    for (int l = threadIdx.x; l <= j; l += blockDim.x) hn[l] = l < j ? hc[l] + b[0] * C[l] : b[0];
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int t = 0; t < 3; ++t) {
+    const double* Ct = C + t * L;
+    const double* Cn = C + (t + 1) * L;
+    double* ht = hn + (1 + t) * L;
+    for (int l = threadIdx.x; l <= j + t + 1; l += blockDim.x) {
+      double sub = ht[l] + Ct[j - 1] * hn[l];  // (hn[0][l] is 0 behind row j, ht[l] behind row j - 1)
+      for (int s = 0; s < t; ++s) sub = sub + Ct[j + s] * hn[(1 + s) * L + l];
+      const double last = t ? b[t] * C[(t - 1) * L + l] : (l == j - 1 ? b[0] : 0.0);
+      ht[l] = ((b[t + 1] * Cn[l] + a[t] * Ct[l]) + last) - sub;
+    }
+    __syncthreads();
+  }
+  // ---- out
+  for (int i = threadIdx.x; i < 4 * L; i += blockDim.x) {
+    const int t = i / L, r = i % L;
+    if (r <= j + t) {
+      G[(int64_t)(j + t) * n + r] = col[i];
+      G[(int64_t)r * n + j + t] = col[i];
+    }
+  }
+  for (int l = threadIdx.x; l <= j; l += blockDim.x) H[(int64_t)(j - 1) * n + l] = hn[l];
+  for (int i = threadIdx.x; i < 3 * n; i += blockDim.x) {
+    const int t = i / n, l = i % n;
+    H[(int64_t)(j + t) * n + l] = l <= j + t + 1 ? hn[(1 + t) * L + l] : 0.0;
+  }
+  if (threadIdx.x == 0) {
+    double m1 = 0.0, m2 = 0.0;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
+      m1 = fmax(m1, smax[0][k]);
+      m2 = fmax(m2, smax[1][k]);
+    }
+    beta[3] = b[3];
+    const double m = fmax(m1, m2);
+    for (int t = 0; t < 4; ++t) elog[j + t] = m;
+    if (!(m1 <= tau) || !(m2 <= tau) || !(b[3] == b[3])) ist[4] = 1;
+  }
+}
+
+hipError_t launch_os_quad_post(const double* d, int ldp, const double* g, int ldg, double* G, double* H, int n, int j, const double* nrm2,
+                               const double* alpha, double* beta, double tau, int* ist, double* elog, hipStream_t s) {
+  const size_t lds = ((size_t)12 * (j + 6) + kFinalThreads) * sizeof(double);
+  // the kernel's static LDS counts against the same 64 KiB: past it the per-kernel limit has to be raised, as launch_spmv_rect does
+  if (lds + 1024 > 65536) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_os_quad_post), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+  }
+  hipLaunchKernelGGL(k_os_quad_post, dim3(1), dim3(kFinalThreads), lds, s, d, ldp, g, ldg, G, H, n, j, nrm2, alpha, beta, tau, ist, elog);
+  return hipSuccess;
+}
+
 }  // namespace lz
