@@ -659,7 +659,7 @@ def test_retired_ritz_gemm_arms_in_the_kernel_bench_build(kb, variant, dims, n):
 def test_ritz_backtransform_kernels(hip, variant, dims, n):
     """Y = V S (Lanczos.py:153-156) by the FP64-MFMA kernels - 0: automatic choice: S resident in LDS, Y-stationary waves
     without barriers for 32 < n <= 128; the S-stationary kernel (S held in registers, 16-row tiles of V through LDS) for
-    129 <= n <= 200 - every (column tiles, k-steps) instantiation of either is hit by some case here - else (n > 200) the
+    129 <= n <= 200 - every reachable (column tiles, k-steps) instantiation of either runs in tests/test_gpu_ritz_exact.py, not here - else (n > 200) the
     one-workgroup-per-128-rows kernel; 1: the latter always (one wave per SIMD with a 32-row x n tile) - against NumPy on the
     fetched basis, ragged row and column counts included."""
     A = synthetic.laplacian_2d_5pt(*dims)
