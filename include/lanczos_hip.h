@@ -435,6 +435,31 @@ int lz_step_spmv(lz_handle h, int j, double* dot_out);
 int lz_step_reorth(lz_handle h, int j, int nrows, int scale, double* beta_out, double* c_out);
 /* r = r - alpha V[j] - beta V[jm1] (jm1 < 0: term skipped); *norm2_out = ||r||^2 (Lanczos.py:119,112) */
 int lz_step_three_term(lz_handle h, int j, int jm1, double alpha, double beta, double* norm2_out);
+/* One loop body of the one-sweep loop (engine 9) on a state set from the host: the single fused step (form 1), a pair (2) or a group
+ * of four (4) at step j, by the same functions lz_run's loops call.  Before: lz_basis_alloc(n), rows 0 .. j-1 through
+ * lz_basis_set_rows, lz_step_spmv(h, j - 1) for y = A V[j-1].
+ * lz_os_state_set allocates and zeroes the loop's state for the n of the basis (room for every walk of every form) and uploads G = V V^T
+ * and the applied coefficients H (n x n, column i at [i * n]), chat[0..j) = V_i . w_j (not normalised), alpha_{j-1}, the beta that formed
+ * v_{j-1} (beta_prev) and the one before it (beta_prev2; ignored at j = 2).
+ * lz_os_step runs the step; wide: the 16 / 8 positions per lane of knobs 9 / 11 in the pair / group walk.  *blocks_out: the blocks of
+ * the walk it launched.
+ * lz_os_state_get copies back what the step left (any pointer may be NULL): G, H (n x n), chat (n + 1), g (2 n + 2: the single form's
+ * correction coefficients, or kap at [0] and p at [n + 1] of a pair), gq (4 runs of *ldg_out = n + 4: a group's predictions), d (the
+ * second-stage sums, 4 qtw_ldp(n + 2) + 16 doubles, runs *ldp_out apart), elog, alpha, beta (n + 1 each; beta[k] formed v_{k+1}),
+ * nrm2[0], the second residual buffer (the single form's u~; rows_local doubles) and the eight state ints ([0] gate, [1] trips,
+ * [3] / [4] a pair's / a group's leftover exceeded the gate).  Rows come back through lz_basis_get_row, y through lz_r_get.
+ * LZ_ERR_STATE (nothing touched) unless: one rank, fused-norm full re-orthogonalisation, 5 or 7 entries per row, tuning knob 15 not 7,
+ * n <= 1520 (the fused one-sweep form's limit); j >= 2; form 1: j < n; a pair: j + 2 <= n and n + 1 <= 1024; a group: j + 4 <= n and
+ * n <= 512; lz_os_step also when no state was set since the last lz_basis_alloc.  lz_run's records (lz_last_*) are not changed.
+ * lz_os_raw_get: rows j0 .. j0 + count - 1 as they lie on the device, lz_padded_rows(rows_local) doubles each with the padding
+ * (rows == NULL: none), and the first part_count doubles of the partial sums the last lz_os_step's walk wrote (one run of 4 / 2 / 1
+ * times ldp doubles per block; copied aside behind the walk, because later launches of the step reuse that buffer; part == NULL: none). */
+int lz_os_state_set(lz_handle h, int j, const double* G, const double* H, const double* chat, double alpha_prev, double beta_prev,
+                    double beta_prev2);
+int lz_os_step(lz_handle h, int form, int j, int wide, int* blocks_out);
+int lz_os_state_get(lz_handle h, int form, int j, double* G, double* H, double* chat, double* g, double* gq, double* d, double* elog,
+                    double* alpha, double* beta, double* nrm2, double* r2_local, int* ist, int* ldg_out, int* ldp_out);
+int lz_os_raw_get(lz_handle h, int j0, int count, double* rows, double* part, int64_t part_count);
 /* y = A x on host vectors (length rows_local / ncols_ext handled internally; single rank) */
 int lz_spmv_host(lz_handle h, const double* x, double* y);
 

@@ -157,6 +157,10 @@ SIGNATURES = {
     "lz_step_spmv": (C.c_int, [_P, C.c_int, _D]),
     "lz_step_reorth": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D]),
     "lz_step_three_term": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, _D]),
+    "lz_os_state_set": (C.c_int, [_P, C.c_int, _D, _D, _D, C.c_double, C.c_double, C.c_double]),
+    "lz_os_step": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "lz_os_state_get": (C.c_int, [_P, C.c_int, C.c_int] + [_D] * 11 + [C.POINTER(C.c_int)] * 3),
+    "lz_os_raw_get": (C.c_int, [_P, C.c_int, C.c_int, _D, _D, C.c_int64]),
     "lz_spmv_host": (C.c_int, [_P, _D, _D]),
     "lz_set_csr_transpose": (C.c_int, [_P, C.c_int64, _I32, _I32, _D]),
     "lz_run_two_sided": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D]),
@@ -797,6 +801,44 @@ class Handle:
         d = C.c_double()
         self.check(self.lib.lz_step_three_term(self._h, int(j), int(jm1), float(alpha), float(beta), C.byref(d)))
         return d.value
+
+    # -- one loop body of the one-sweep loop on a state set from the host (after basis_alloc, basis_set_rows, step_spmv(j - 1))
+    def os_state_set(self, j, G, H, chat, alpha_prev, beta_prev, beta_prev2=0.0):
+        """``G``, ``H``: ``(n, n)`` arrays indexed ``[row, column]``; ``chat``: the ``j`` un-normalised predictions ``V_i . w_j``"""
+        n = self.n
+        Gd, Hd = f64(np.asarray(G).T), f64(np.asarray(H).T)  # the device keeps column i at [i * n]
+        chat = f64(chat)
+        assert Gd.shape == (n, n) and Hd.shape == (n, n) and chat.shape == (j,)
+        self.check(self.lib.lz_os_state_set(self._h, int(j), dptr(Gd), dptr(Hd), dptr(chat), float(alpha_prev), float(beta_prev),
+                                            float(beta_prev2)))
+
+    def os_step(self, form, j, wide=False):
+        """one single (1), pair (2) or group (4) step at ``j``; returns the block count of the walk it launched"""
+        nb = C.c_int()
+        self.check(self.lib.lz_os_step(self._h, int(form), int(j), int(bool(wide)), C.byref(nb)))
+        return nb.value
+
+    def os_state_get(self, form, j):
+        """everything a step leaves on the device, as a dict (``G``, ``H`` indexed ``[row, column]``)"""
+        n = self.n
+        ldq = (n + 2 + 15) & ~15
+        out = {"G": np.empty((n, n)), "H": np.empty((n, n)), "chat": np.empty(n + 1), "g": np.empty(2 * n + 2), "gq": np.empty((4, n + 4)),
+               "d": np.empty(4 * ldq + 16), "elog": np.empty(n + 1), "alpha": np.empty(n + 1), "beta": np.empty(n + 1), "nrm2": np.empty(1),
+               "r2": np.empty(self.rows)}
+        ist = np.empty(8, dtype=np.int32)
+        ldg, ldp = C.c_int(), C.c_int()
+        iptr = ist.ctypes.data_as(C.POINTER(C.c_int))
+        self.check(self.lib.lz_os_state_get(self._h, int(form), int(j), *[dptr(v) for v in out.values()], iptr, C.byref(ldg), C.byref(ldp)))
+        out["G"], out["H"] = out["G"].T.copy(), out["H"].T.copy()
+        out.update(ist=ist, ldg=ldg.value, ldp=ldp.value)
+        return out
+
+    def os_raw_get(self, j0, count, part_count):
+        """rows ``j0 .. j0 + count - 1`` with their padding, and the first ``part_count`` partial sums the last step's walk wrote"""
+        rows = np.empty((count, self.padded_rows(self.rows)))
+        part = np.empty(part_count)
+        self.check(self.lib.lz_os_raw_get(self._h, int(j0), int(count), dptr(rows), dptr(part), int(part_count)))
+        return rows, part
 
     # ---- two-sided (bi-orthogonal) Lanczos ----
     def set_csr_transpose(self, rowptr=None, colidx=None, vals=None):

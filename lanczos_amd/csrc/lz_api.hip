@@ -3,6 +3,7 @@
 // in lz_loops.hip, matrix setup in lz_matrix.hip, Ritz vectors / Gram / quality in lz_ritz.hip, the two-sided variant in
 // lz_twosided_api.hip.  See include/lanczos_hip.h for the contract and the reference call sites each entry point replaces.
 #include <atomic>
+#include <cstring>
 #include <deque>
 #include <unordered_map>
 
@@ -89,6 +90,8 @@ int64_t skew_stride(lz_handle h, int64_t ld) {
 int check_launch(lz_handle h, const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, LZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  if (h->tap_what && std::strcmp(what, h->tap_what) == 0)  // (lz_os_step only: what the walk left in d_part, before the next launch reuses it)
+    LZ_HIP(h, hipMemcpyAsync(h->d_tap, h->d_part, h->tap_count * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   return LZ_OK;
 }
 
@@ -508,6 +511,7 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_om);
   big_free(h->d_os);
   big_free(h->d_osi);
+  big_free(h->d_tap);
   big_free(h->d_omi);
   big_free(h->res_V);
   big_free(h->res_Y);
@@ -709,6 +713,7 @@ int lz::api::basis_alloc(lz_handle h, int n, int zero_rows) {
                                  (size_t)n, h->stream));
   }
   h->n = n;
+  h->os_step_n = 0;  // (a state set for an earlier basis or matrix does not fit this one: lz_os_step asks for lz_os_state_set again)
   h->qplan = plan_qtw(h->rows_pad, h->flags, h->tune, n);
   size_t need = (size_t)(n + 16) * (size_t)h->qplan.P;
   if (h->flags & LZ_FLAG_ONE_REDUCE) need = (size_t)2 * qtw_ldp(n + 2) * (size_t)h->qplan.P;

@@ -223,6 +223,12 @@ struct lz_context {
   double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n), the group form's predictions (4 (n + 4)); os_n = its n
   int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run, [3] / [4] a pair's / a group's leftover exceeded tau
   int os_n = 0;
+  int os_step_n = 0;           //   ... the n of the state lz_os_state_set left in d_os (0: none; a run lays d_os out for its own n)
+  // lz_os_step's tap: check_launch copies the first tap_count doubles of d_part to d_tap behind the launch named tap_what (the walk of
+  // the step: later launches of the same step reuse the head of d_part).  nullptr outside lz_os_step.
+  const char* tap_what = nullptr;
+  double* d_tap = nullptr;
+  size_t tap_cap = 0, tap_count = 0;
   int last_gate_trips = 0;     // one-sweep loop: steps of the last lz_run whose prediction missed by more than kOneSweepTau
   int last_os_fused = 0;       // one-sweep loop: 1 = the last lz_run took the fused form (no three-term pass)
   int last_os_pairs = 0;       // one-sweep loop: pair walks (one walk per two steps) behind the last lz_run's result; 0 after a repeat

@@ -469,6 +469,16 @@ struct OneSweepState {
   double *G, *H, *chat, *g, *elog, *gq;  // gq: the group form's predictions, 4 runs of n + 4
   int nb;
 };
+// where the state of an n-step run lies in d_os
+static void one_sweep_view(lz_handle h, int n, OneSweepState& st) {
+  st.nb = os_sweep_blocks(h->rows_pad);
+  st.G = h->d_os;
+  st.H = st.G + (size_t)n * n;
+  st.chat = st.H + (size_t)n * n;
+  st.g = st.chat + n + 1;
+  st.elog = st.g + 2 * n + 2;
+  st.gq = st.elog + n + 1;
+}
 static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_blocks = 0) {
   const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8 + (size_t)4 * (n + 4);
   if (h->os_n < n) {
@@ -476,15 +486,10 @@ static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_block
     LZ_TRY(dev_alloc(h, h->d_osi, 8));
     h->os_n = n;
   }
-  st.nb = os_sweep_blocks(h->rows_pad);
+  h->os_step_n = 0;
+  one_sweep_view(h, n, st);
   // (the pair walk leaves two runs per block, and its block count may differ from the single walk's)
   LZ_TRY(ensure_part(h, (size_t)std::max(st.nb, 2 * pair_blocks) * qtw_ldp(n + 1) + 64));
-  st.G = h->d_os;
-  st.H = st.G + (size_t)n * n;
-  st.chat = st.H + (size_t)n * n;
-  st.g = st.chat + n + 1;
-  st.elog = st.g + 2 * n + 2;
-  st.gq = st.elog + n + 1;
   LZ_HIP(h, hipMemsetAsync(h->d_os, 0, os_doubles * sizeof(double), h->stream));
   // [0] gate, [1] trips, [2] stays 0 (the fused SpMV's "scale" gate), [3] a pair's leftover exceeded tau, [4] a group's
   LZ_HIP(h, hipMemsetAsync(h->d_osi, 0, 8 * sizeof(int), h->stream));
@@ -686,14 +691,66 @@ bool one_sweep_quad_applies(lz_handle h, int n) {
   const int knob = h->tune[15];
   return one_sweep_pair_applies(h, n) && knob != 8 && knob != 9 && n >= 6 && os_quad_ldp(n - 4) <= os_quad_max_ldp() && !h->quad_tripped;
 }
-int run_loop_one_sweep_quad(lz_handle h, int n) {
+// one group at steps j .. j + 3 (2 <= j, j + 4 <= n): the chain, predict, the group walk, post, the closing SpMV
+static int one_sweep_quad_iter(lz_handle h, int n, int j, const OneSweepState& st, int nbq, bool wide8) {
   const double M = (double)h->rows;
+  const int ldg = n + 4;
+  h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1) || iter_sampled(h, j + 2) || iter_sampled(h, j + 3);
+  // the chain: w_j -> d_r; then x_t = src / b_t -> V[j + t], y_t -> the other residual buffer, z in place there
+  LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
+  double* src = h->d_r;
+  double* dst = h->d_r2;
+  int npz = 0;
+  for (int t = 0; t < 3; ++t) {
+    int npa = 0;
+    LZ_TRY(step_scaling_spmv(h, n, j + t, src, dst, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
+    LZ_TRY(step_final_sum(h, npa, h->d_alpha + (j + t), "final_sum(alpha)"));
+    // z = (y_t - a_t x_t) - b_t x_{t-1}; the last ||z||^2 is summed by the predict kernel
+    LZ_TRY(step_three_term(h, j + t, j + t - 1, h->d_alpha + (j + t), h->d_beta + (j + t - 1), t < 2, &npz, dst));
+    std::swap(src, dst);
+  }
+  const double* z = src;  // (d_r2: three steps from d_r)
+  const int ldp = os_quad_ldp(j);
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_os_quad_predict(h->d_part, npz, h->d_nrm2, st.chat, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + (j - 1), st.gq, ldg, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep group predict"));
+  }
+  {
+    Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 64.0 * M, 16.0 * (j + 1) * M);
+    launch_os_quad_sweep(h->d_V, h->ldv, h->rows_pad, j, st.gq, ldg, z, h->d_nrm2, h->d_part, wide8, h->stream);
+    LZ_TRY(check_launch(h, "one-sweep group walk"));
+  }
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_final_rows_t(h->d_part, nbq, 4 * ldp, 3 * ldp + j + 4, h->d_c, h->stream);
+    LZ_TRY(check_launch(h, "final_rows(one-sweep group)"));
+    LZ_HIP(h, launch_os_quad_post(h->d_c, ldp, st.gq, ldg, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, h->d_beta + (j - 1), kOneSweepTau, h->d_osi,
+                                  st.elog, h->stream));
+    LZ_TRY(check_launch(h, "one-sweep group post"));
+  }
+  {  // closing: y = A V[j+3] -> d_r (V[j+3] is in place: the plain ELL product), alpha_{j+3} and the next chat
+    double* vj = basis_row(h, j + 3);
+    int npa = 0;
+    {
+      Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true), spmv_flops(h));
+      npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream);
+      LZ_TRY(check_launch(h, "spmv(ell)"));
+    }
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true,
+                          j + 4 < n, h->stream);
+    LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+  }
+  h->last_os_quads += 1;
+  return LZ_OK;
+}
+int run_loop_one_sweep_quad(lz_handle h, int n) {
   const bool wide8 = h->tune[15] == 11;  // (A/B: 8 positions per lane on long vectors)
   OneSweepState st;
   const int nbp = os_pair_sweep_blocks(h->rows_pad, false), nbq = os_quad_sweep_blocks(h->rows_pad, wide8);
   LZ_TRY(one_sweep_setup(h, n, st, std::max(nbp, 2 * nbq)));
   h->last_os_fused = 1;
-  const int ldg = n + 4;
   LZ_TRY(warm_up(h, true));
   for (int j = 0; j < n;) {
     if (j >= 2 && n - j == 2 && (n - 2) % 4 == 2) {  // (a tail of two steps; the last two of a tail of three are single steps)
@@ -707,57 +764,128 @@ int run_loop_one_sweep_quad(lz_handle h, int n) {
       j += 1;
       continue;
     }
-    h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1) || iter_sampled(h, j + 2) || iter_sampled(h, j + 3);
-    // the chain: w_j -> d_r; then x_t = src / b_t -> V[j + t], y_t -> the other residual buffer, z in place there
-    LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
-    double* src = h->d_r;
-    double* dst = h->d_r2;
-    int npz = 0;
-    for (int t = 0; t < 3; ++t) {
-      int npa = 0;
-      LZ_TRY(step_scaling_spmv(h, n, j + t, src, dst, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
-      LZ_TRY(step_final_sum(h, npa, h->d_alpha + (j + t), "final_sum(alpha)"));
-      // z = (y_t - a_t x_t) - b_t x_{t-1}; the last ||z||^2 is summed by the predict kernel
-      LZ_TRY(step_three_term(h, j + t, j + t - 1, h->d_alpha + (j + t), h->d_beta + (j + t - 1), t < 2, &npz, dst));
-      std::swap(src, dst);
-    }
-    const double* z = src;  // (d_r2: three steps from d_r)
-    const int ldp = os_quad_ldp(j);
-    {
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_quad_predict(h->d_part, npz, h->d_nrm2, st.chat, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + (j - 1), st.gq, ldg, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep group predict"));
-    }
-    {
-      Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 64.0 * M, 16.0 * (j + 1) * M);
-      launch_os_quad_sweep(h->d_V, h->ldv, h->rows_pad, j, st.gq, ldg, z, h->d_nrm2, h->d_part, wide8, h->stream);
-      LZ_TRY(check_launch(h, "one-sweep group walk"));
-    }
-    {
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_final_rows_t(h->d_part, nbq, 4 * ldp, 3 * ldp + j + 4, h->d_c, h->stream);
-      LZ_TRY(check_launch(h, "final_rows(one-sweep group)"));
-      LZ_HIP(h, launch_os_quad_post(h->d_c, ldp, st.gq, ldg, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, h->d_beta + (j - 1), kOneSweepTau, h->d_osi,
-                                    st.elog, h->stream));
-      LZ_TRY(check_launch(h, "one-sweep group post"));
-    }
-    {  // closing: y = A V[j+3] -> d_r (V[j+3] is in place: the plain ELL product), alpha_{j+3} and the next chat
-      double* vj = basis_row(h, j + 3);
-      int npa = 0;
-      {
-        Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true), spmv_flops(h));
-        npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream);
-        LZ_TRY(check_launch(h, "spmv(ell)"));
-      }
-      Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true,
-                            j + 4 < n, h->stream);
-      LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
-    }
-    h->last_os_quads += 1;
+    LZ_TRY(one_sweep_quad_iter(h, n, j, st, nbq, wide8));
     j += 4;
   }
   return one_sweep_fused_tail(h, n);
+}
+
+// One loop body on a state set from the host (lz_os_state_set / lz_os_step / lz_os_state_get, tests/test_gpu_one_sweep_step.py): the
+// same static functions the loops call, on the basis lz_basis_alloc made.  *msg: why a step of this form cannot run at (n, j), or nullptr.
+static const char* one_sweep_step_refusal(lz_handle h, int n, int j, int form) {
+  const bool full_fused = (h->flags & LZ_FLAG_FUSED_NORM) && !(h->flags & LZ_FLAG_REORTH_PARTIAL);
+  if (h->tune[15] == 7) return "one-sweep step: tuning knob 15 is 7 (never the fused one-sweep form)";
+  if (n > kOneSweepFusedMaxN) return "one-sweep step: the basis has more rows than the fused one-sweep form takes (1520)";
+  if (!one_sweep_fused_applies(h, n) || !full_fused)
+    return "one-sweep step: needs one rank, fused-norm full re-orthogonalisation and a matrix with 5 or 7 entries per row (the fused one-sweep form)";
+  if (j < 2) return "one-sweep step: need j >= 2";
+  if (form == 1) return j + 1 > n ? "one-sweep step: need j < n" : nullptr;
+  if (form == 2)
+    return j + 2 > n || qtw_ldp(n + 1) > kOneSweepPairMaxLdp ? "one-sweep step: a pair needs j + 2 <= n and n + 1 within the pair walk's run length"
+                                                              : nullptr;
+  if (form == 4)
+    return j + 4 > n || os_quad_ldp(n - 4) > os_quad_max_ldp() ? "one-sweep step: a group needs j + 4 <= n and n within the group walk's run length"
+                                                               : nullptr;
+  return "one-sweep step: form must be 1, 2 or 4";
+}
+static int one_sweep_step_blocks(lz_handle h, int form, bool wide) {
+  return form == 4 ? os_quad_sweep_blocks(h->rows_pad, wide) : form == 2 ? os_pair_sweep_blocks(h->rows_pad, wide) : os_sweep_blocks(h->rows_pad);
+}
+int one_sweep_state_set(lz_handle h, int j, const double* G, const double* H, const double* chat, double alpha_prev, double beta_prev,
+                        double beta_prev2) {
+  const int n = h->n;
+  if (const char* why = one_sweep_step_refusal(h, n, j, 1)) return fail(h, LZ_ERR_STATE, why);
+  OneSweepState st;
+  int blocks = 0;  // room for every walk a step may launch: both widths of the pair's and of the group's (two group runs per pair run)
+  for (int wide = 0; wide < 2; ++wide)
+    blocks = std::max({blocks, os_pair_sweep_blocks(h->rows_pad, wide != 0), 2 * os_quad_sweep_blocks(h->rows_pad, wide != 0)});
+  LZ_TRY(one_sweep_setup(h, n, st, blocks));
+  const size_t nn = (size_t)n * n * sizeof(double);
+  LZ_HIP(h, hipMemcpyAsync(st.G, G, nn, hipMemcpyHostToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(st.H, H, nn, hipMemcpyHostToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(st.chat, chat, (size_t)j * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(h->d_alpha + (j - 1), &alpha_prev, sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LZ_HIP(h, hipMemcpyAsync(h->d_beta + (j - 2), &beta_prev, sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (j >= 3) LZ_HIP(h, hipMemcpyAsync(h->d_beta + (j - 3), &beta_prev2, sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  h->os_step_n = n;
+  return LZ_OK;
+}
+int one_sweep_step_run(lz_handle h, int form, int j, bool wide, int* blocks) {
+  const int n = h->n;
+  if (const char* why = one_sweep_step_refusal(h, n, j, form)) return fail(h, LZ_ERR_STATE, why);
+  if (h->os_step_n != n || !h->d_os) return fail(h, LZ_ERR_STATE, "one-sweep step: no state set for this basis (lz_os_state_set after lz_basis_alloc)");
+  OneSweepState st;
+  one_sweep_view(h, n, st);
+  const int nb = one_sweep_step_blocks(h, form, wide);
+  const int pairs = h->last_os_pairs, quads = h->last_os_quads;  // (lz_run's record stays lz_run's)
+  // what the walk leaves in d_part is copied aside behind its launch: the closing SpMV's partials reuse the head of d_part
+  const size_t tap = (size_t)nb * (form == 4 ? 4 * os_quad_ldp(j) : form == 2 ? 2 * os_pair_ldp(j) : qtw_ldp(j + 2));
+  if (h->tap_cap < tap) {
+    LZ_TRY(dev_alloc(h, h->d_tap, tap));
+    h->tap_cap = tap;
+  }
+  h->tap_count = tap;
+  h->tap_what = form == 4 ? "one-sweep group walk" : form == 2 ? "one-sweep pair walk" : "one-sweep";
+  int rc;
+  if (form == 4) {
+    rc = one_sweep_quad_iter(h, n, j, st, nb, wide);
+  } else if (form == 2) {
+    rc = one_sweep_pair_iter(h, n, j, st, nb, wide);
+  } else {
+    begin_iter(h, j);
+    rc = one_sweep_fused_iter(h, n, j, st);
+  }
+  h->tap_what = nullptr;
+  h->last_os_pairs = pairs;
+  h->last_os_quads = quads;
+  LZ_TRY(rc);
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  if (blocks) *blocks = nb;
+  return LZ_OK;
+}
+int one_sweep_state_get(lz_handle h, int form, int j, double* G, double* H, double* chat, double* g, double* gq, double* d, double* elog,
+                        double* alpha, double* beta, double* nrm2, double* r2, int* ist, int* ldg, int* ldp) {
+  const int n = h->n;
+  if (h->os_step_n != n || !h->d_os) return fail(h, LZ_ERR_STATE, "one-sweep step: no state set for this basis (lz_os_state_set after lz_basis_alloc)");
+  OneSweepState st;
+  one_sweep_view(h, n, st);
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+  };
+  const size_t nn = (size_t)n * n * sizeof(double);
+  LZ_HIP(h, get(G, st.G, nn));
+  LZ_HIP(h, get(H, st.H, nn));
+  LZ_HIP(h, get(chat, st.chat, ((size_t)n + 1) * sizeof(double)));
+  LZ_HIP(h, get(g, st.g, ((size_t)2 * n + 2) * sizeof(double)));
+  LZ_HIP(h, get(gq, st.gq, (size_t)4 * (n + 4) * sizeof(double)));
+  LZ_HIP(h, get(d, h->d_c, ((size_t)4 * qtw_ldp(n + 2) + 16) * sizeof(double)));
+  LZ_HIP(h, get(elog, st.elog, ((size_t)n + 1) * sizeof(double)));
+  LZ_HIP(h, get(alpha, h->d_alpha, ((size_t)n + 1) * sizeof(double)));
+  LZ_HIP(h, get(beta, h->d_beta, ((size_t)n + 1) * sizeof(double)));
+  LZ_HIP(h, get(nrm2, h->d_nrm2, sizeof(double)));
+  LZ_HIP(h, get(r2, h->d_r2, (size_t)h->rows * sizeof(double)));
+  LZ_HIP(h, get(ist, h->d_osi, 8 * sizeof(int)));
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  if (ldg) *ldg = n + 4;
+  if (ldp) *ldp = form == 4 ? os_quad_ldp(j) : form == 2 ? os_pair_ldp(j) : qtw_ldp(j + 2);
+  return LZ_OK;
+}
+
+// raw rows j0 .. j0 + count - 1 with their padding (rows_pad doubles each) and the first part_count doubles the last step's walk left in
+// d_part (its tap)
+int one_sweep_raw_get(lz_handle h, int j0, int count, double* rows, double* part, int64_t part_count) {
+  if (rows) {
+    if (count < 1 || j0 < 0 || j0 + count > h->n) return fail(h, LZ_ERR_ARG, "lz_os_raw_get: rows out of range");
+    LZ_HIP(h, hipMemcpy2DAsync(rows, (size_t)h->rows_pad * sizeof(double), h->d_V + (int64_t)j0 * h->ldv, (size_t)h->ldv * sizeof(double),
+                               (size_t)h->rows_pad * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (part) {
+    if (part_count < 0 || (size_t)part_count > h->tap_count || !h->d_tap) return fail(h, LZ_ERR_STATE, "lz_os_raw_get: the last step's walk left fewer partials");
+    LZ_HIP(h, hipMemcpyAsync(part, h->d_tap, (size_t)part_count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  LZ_HIP(h, hipStreamSynchronize(h->stream));
+  return LZ_OK;
 }
 
 // ---- which loop structure runs the Krylov iteration --------------------------------------------------------------------
@@ -1492,6 +1620,38 @@ int lz_run_resume(lz_handle h, int n, int j0, const double* V_rows, int64_t ldv_
   LZ_TRY(run_loop_six(h, n, j0));
   LZ_TRY(fr.drain(alpha_out, beta_out));
   return fr.finish(alpha_out, beta_out);
+}
+
+/* ---- one loop body of the one-sweep loop on a state set from the host (include/lanczos_hip.h) ------------------------------ */
+int lz_os_state_set(lz_handle h, int j, const double* G, const double* H, const double* chat, double alpha_prev, double beta_prev,
+                    double beta_prev2) {
+  if (!h) return LZ_ERR_ARG;
+  if (!G || !H || !chat) return fail(h, LZ_ERR_ARG, "lz_os_state_set: NULL buffer");
+  LZ_TRY(require_basis(h, 0));
+  LZ_HIP(h, hipSetDevice(h->dev));
+  return one_sweep_state_set(h, j, G, H, chat, alpha_prev, beta_prev, beta_prev2);
+}
+
+int lz_os_step(lz_handle h, int form, int j, int wide, int* blocks_out) {
+  if (!h) return LZ_ERR_ARG;
+  LZ_TRY(require_basis(h, 0));
+  LZ_HIP(h, hipSetDevice(h->dev));
+  return one_sweep_step_run(h, form, j, wide != 0, blocks_out);
+}
+
+int lz_os_state_get(lz_handle h, int form, int j, double* G, double* H, double* chat, double* g, double* gq, double* d, double* elog,
+                    double* alpha, double* beta, double* nrm2, double* r2_local, int* ist, int* ldg_out, int* ldp_out) {
+  if (!h) return LZ_ERR_ARG;
+  LZ_TRY(require_basis(h, 0));
+  LZ_HIP(h, hipSetDevice(h->dev));
+  return one_sweep_state_get(h, form, j, G, H, chat, g, gq, d, elog, alpha, beta, nrm2, r2_local, ist, ldg_out, ldp_out);
+}
+
+int lz_os_raw_get(lz_handle h, int j0, int count, double* rows, double* part, int64_t part_count) {
+  if (!h) return LZ_ERR_ARG;
+  LZ_TRY(require_basis(h, 0));
+  LZ_HIP(h, hipSetDevice(h->dev));
+  return one_sweep_raw_get(h, j0, count, rows, part, part_count);
 }
 
 }  // extern "C"
