@@ -582,6 +582,50 @@ int lz_ztrl_residuals(lz_handle h, int k, const double* theta, double* out);
 int lz_ztrl_set_rows(lz_handle h, int j0, int count, const double* rows, int64_t ld);
 int lz_ztrl_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
 
+/* ---- matrix exponential action (lanczos_amd.expm_multiply; the short-iterative Lanczos propagator) -------------------------------
+ * exp(a t A) b for a real symmetric or complex Hermitian A: m Lanczos steps from the current state, the exponential of the small
+ * projected matrix on the host, the combination of the rows on the device - and again from the new state, which never leaves the
+ * device.  The basis (m + 1 rows) is the propagator's own: the bases of lz_trl_* and lz_ztrl_* on the same handle are untouched, and
+ * no matrix setter drops more than it drops without this section.  Real rows (cplx = 0) or planar complex rows as in the section
+ * above (cplx = 1); across this ABI a complex vector is interleaved complex128.  Three routes: a real matrix and a real basis run the
+ * real product; a complex matrix needs the planar basis and runs lz_zspmv_host's product; a REAL matrix with a PLANAR basis (a real
+ * Hamiltonian in Schroedinger time) runs the mixed product, which takes one of two forms: the two-plane kernel, which reads the
+ * matrix once for both planes (CSR: a group of lanes per row, chosen from the mean row length as lz_set_csr_cplx does; dense: a wave
+ * per row), or two launches of the real product, one per plane.  lz_expm_set_product chooses: 0 auto, 1 two launches, 2 the two-plane
+ * kernel (a call of its own, not an lz_set_tuning index: every index up to 23 is taken and 24 is refused as out of range).  Auto takes the two-plane kernel for every dense matrix and for a CSR matrix with a mean row below 16 entries whose SpMV is
+ * neither the ELL / row-class coded stencil kernel nor the column-blocked two-phase one (DESIGN.md section 8e has the measurements).
+ * One rank only: LZ_ERR_STATE on a handle with a communicator and with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE.  Every call
+ * behind lz_expm_begin answers LZ_ERR_STATE before it, after the matrix changed its padded row length, with no matrix set, and for a
+ * real basis once a complex matrix is set. */
+/* allocate the basis for m steps (2 <= m <= min(64, n): the real form of a planar C has 2 m rows, launch_trl_restart's limit),
+ * zero it, V[0] = v0 / |v0| (v0: n doubles, or n complex with cplx).  LZ_ERR_ARG for cplx = 0 while a complex matrix is set. */
+int lz_expm_begin(lz_handle h, int m, int cplx, const double* v0);
+/* steps j = k0 .. k1 - 1 (0 <= k0 < k1 <= m) without a host synchronisation, each as lz_trl_extend / lz_ztrl_extend run it: w = A V[j],
+ * classical Gram-Schmidt against V[0..j] with the second pass behind the DGKS gate, beta_j = |w|, V[j + 1] = w / beta_j.  proj_out
+ * (m x m elements, row-major) and beta_out[m] as there; rows k0 .. k1 - 1 are written on the device, the whole arrays are copied. */
+int lz_expm_extend(lz_handle h, int k0, int k1, double* proj_out, double* beta_out);
+/* in place: V[c] = sum_{i < mm} C[i, c] V[i] for c < ncols (C: mm x ncols row-major, complex with a planar basis; 1 <= mm <= m,
+ * 1 <= ncols < mm), then V[0] = V[0] / |V[0]| with that norm in *norm_out (may be NULL).  Rows mm and above have no weight in the
+ * result, whatever they hold (a breakdown leaves NaN there).  mm == 1 takes ncols == 1 and scales row 0 (row 1 is cleared).  Rows
+ * ncols .. m are undefined afterwards until the next extension writes them. */
+int lz_expm_combine(lz_handle h, int mm, int ncols, const double* C, double* norm_out);
+/* basis rows j0 .. j0 + count - 1 (j0 + count <= m + 1).  Real basis: raw rows with their padding, as lz_trl_get_rows; planar basis:
+ * unpadded rows of n complex numbers, as lz_ztrl_get_rows. */
+int lz_expm_get_rows(lz_handle h, int j0, int count, double* rows, int64_t ld);
+/* y = A x for the REAL matrix set and host vectors of n complex128 each, through the mixed product in the form lz_expm_set_product selects: the
+ * tests' way to its kernels.  Needs no lz_expm_begin. */
+int lz_zspmv_real_host(lz_handle h, const double* x, double* y);
+/* out[0] = the route of the basis under the matrix now set (0 real, 1 mixed, 2 complex; -1 before lz_expm_begin), out[1] = the form
+ * the last mixed product took (0 none yet, 1 two launches, 2 the two-plane kernel), out[2] = the lanes per row of the two-plane CSR
+ * kernel for the CSR matrix now set (0: none set) */
+int lz_expm_info(lz_handle h, int* out);
+/* the form of the mixed product from now on (read at every product): 0 automatic (above), 1 two launches of the real product always,
+ * 2 the two-plane kernel always (A/B, tests).  Kept on the handle until lz_destroy.  LZ_ERR_ARG for anything else. */
+int lz_expm_set_product(lz_handle h, int form);
+/* *ms_out = the device time (hipEvents) of one product w = A V[0] of the route, in the form lz_expm_set_product selects on the mixed route: the mean
+ * of reps launches behind one warm-up launch.  The work vector is overwritten.  The measurements of tools/expm_probe.py */
+int lz_expm_product_time(lz_handle h, int reps, double* ms_out);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

@@ -195,6 +195,14 @@ SIGNATURES = {
     "lz_ztrl_residuals": (C.c_int, [_P, C.c_int, _D, _D]),
     "lz_ztrl_set_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
     "lz_ztrl_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_expm_begin": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "lz_expm_extend": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_expm_combine": (C.c_int, [_P, C.c_int, C.c_int, _D, _D]),
+    "lz_expm_get_rows": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int64]),
+    "lz_zspmv_real_host": (C.c_int, [_P, _D, _D]),
+    "lz_expm_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_expm_product_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_expm_set_product": (C.c_int, [_P, C.c_int]),
     "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
     "lz_gk_set_dense": (C.c_int, [_P, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int]),
     "lz_gk_plan": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1044,6 +1052,66 @@ class Handle:
         out = np.empty((int(count), self.rows), dtype=np.complex128)
         self.check(self.lib.lz_ztrl_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
         return out
+
+    # -- matrix exponential action (lanczos_amd.expm_multiply): a basis of its own, real or planar complex, on whichever matrix is set
+    def expm_begin(self, m, v0, cplx):
+        """``cplx``: the planar complex basis (required on a complex matrix; on a real one it selects the mixed product)"""
+        v0 = c128(v0) if cplx else f64(v0)
+        assert v0.shape == (self.rows,)
+        self.expm_m, self.expm_cplx = int(m), bool(cplx)
+        self.check(self.lib.lz_expm_begin(self._h, int(m), 1 if cplx else 0, dptr(v0)))
+
+    def expm_extend(self, k0, k1):
+        """steps k0 .. k1-1 -> (proj (m, m): row j = <V_i, A V[j]> for i <= j, written for k0 <= j < k1; beta (m,) real)"""
+        m = self.expm_m
+        proj = np.zeros((m, m), dtype=np.complex128 if self.expm_cplx else np.float64)
+        beta = np.zeros(m)
+        self.check(self.lib.lz_expm_extend(self._h, int(k0), int(k1), dptr(proj), dptr(beta)))
+        return proj, beta
+
+    def expm_combine(self, mm, Cm):
+        """rows ``0 .. ncols-1`` become ``sum_i Cm[i, c] V_i`` over the first ``mm`` rows, row 0 is normalised; returns its norm before that"""
+        Cm = c128(Cm) if self.expm_cplx else f64(Cm)
+        assert Cm.ndim == 2 and Cm.shape[0] == int(mm)
+        nrm = C.c_double()
+        self.check(self.lib.lz_expm_combine(self._h, int(mm), Cm.shape[1], dptr(Cm), C.byref(nrm)))
+        return nrm.value
+
+    def expm_get_rows(self, j0, count):
+        """rows j0 .. j0 + count - 1 as (count, n), without padding"""
+        if self.expm_cplx:
+            out = np.empty((int(count), self.rows), dtype=np.complex128)
+            self.check(self.lib.lz_expm_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
+            return out
+        out = np.empty((int(count), self.padded_rows(self.rows)))
+        self.check(self.lib.lz_expm_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
+        return np.ascontiguousarray(out[:, : self.rows])
+
+    def zspmv_real(self, x):
+        """A x for the real matrix set and a complex x, through the mixed product (in the form ``expm_set_product`` selects), host vectors"""
+        x = c128(x)
+        assert x.shape == (self.rows,)
+        y = np.empty(self.rows, dtype=np.complex128)
+        self.check(self.lib.lz_zspmv_real_host(self._h, dptr(x), dptr(y)))
+        return y
+
+    def expm_set_product(self, form):
+        """the mixed product from now on: 0 automatic, 1 two launches of the real product, 2 the two-plane kernel"""
+        self.check(self.lib.lz_expm_set_product(self._h, int(form)))
+
+    def expm_product_time(self, reps=20):
+        """device milliseconds of one product ``A V[0]`` of the route (mean of ``reps`` launches); overwrites the work vector"""
+        ms = C.c_double()
+        self.check(self.lib.lz_expm_product_time(self._h, int(reps), C.byref(ms)))
+        return ms.value
+
+    def expm_info(self):
+        """{"route": "real" / "mixed" / "complex" (None before ``expm_begin``), "product": None / "two-launch" / "two-plane" - the form
+        of the last mixed product -, "group": lanes per row of the two-plane CSR kernel for the CSR matrix set (0: none)}"""
+        out = (C.c_int * 3)()
+        self.check(self.lib.lz_expm_info(self._h, out))
+        return {"route": {0: "real", 1: "mixed", 2: "complex"}.get(out[0]), "product": {1: "two-launch", 2: "two-plane"}.get(out[1]),
+                "group": int(out[2])}
 
     # -- Golub-Kahan-Lanczos (lanczos_amd.svds): a rectangular operator and two bases of their own; side 0 = U (length p), 1 = V (length q)
     def gk_set_csr(self, A, AT):

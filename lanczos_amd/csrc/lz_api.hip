@@ -520,6 +520,7 @@ int lz_destroy(lz_handle h) {
   orth_free(h->trl_wk);
   gk_free(h);
   z_free(h);
+  expm_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

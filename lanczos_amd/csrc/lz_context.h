@@ -1,5 +1,5 @@
 // Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip, lz_orth.hip and the
-// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip, lz_expm.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -116,6 +116,19 @@ struct ZState {
   OrthBasis B;              // planes == 2, m + 1 complex rows
   OrthWork wk;              // small arrays: see ztrl_small_layout in lz_ztrl_api.hip
   int m = 0;
+};
+
+// Matrix exponential action (lz_expm.hip; lanczos_amd.expm_multiply): the propagator's basis, real (planes == 1) or planar complex, of
+// its own beside h->trl and h->z.B, so eigsh's bases survive a propagation on the same handle and the other way round.  The matrix is
+// whichever is set: the real one (h->kind != 0; with a planar basis the product is the mixed one) or the complex one (h->z.kind != 0).
+struct ExpmState {
+  OrthBasis B;              // m + 1 rows
+  OrthWork wk;              // small arrays: see expm_small_layout in lz_expm.hip; part also takes the real product's partials
+  int m = 0;
+  int form = 0;             // lz_expm_set_product: 0 auto, 1 two launches of the real product, 2 the two-plane kernel
+  int product = 0;          // the form the last mixed product took: 0 none yet, 1 two launches of the real product, 2 the two-plane kernel
+  double* xtmp = nullptr;   // lz_zspmv_real_host: x and y in planar form (4 padded vectors)
+  int64_t xtmp_pad = 0;
 };
 
 struct lz_context {
@@ -258,6 +271,7 @@ struct lz_context {
   TrlPoly poly;  // none, the Chebyshev filter or the Chebyshev series
   GkState gk;    // Golub-Kahan-Lanczos (lz_gk_*): freed by gk_free
   ZState z;      // complex Hermitian matrix and its thick-restart basis (lz_set_*_cplx, lz_ztrl_*): freed by z_free
+  ExpmState ex;  // the propagator's basis (lz_expm_*): freed by expm_free
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -371,6 +385,9 @@ int z_drop_matrix(lz_handle h);
 void z_free(lz_handle h);
 // w = A x on the complex matrix, planar vectors (real part at x / y, imaginary part at x + ld / y + ld); writes n entries of each part
 void z_matvec(lz_handle h, const double* x, double* y, int64_t ld);
+
+// matrix exponential action (lz_expm.hip): releases everything h->ex owns (lz_destroy)
+void expm_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.
