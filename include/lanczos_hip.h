@@ -626,6 +626,48 @@ int lz_expm_set_product(lz_handle h, int form);
  * of reps launches behind one warm-up launch.  The work vector is overwritten.  The measurements of tools/expm_probe.py */
 int lz_expm_product_time(lz_handle h, int reps, double* ms_out);
 
+/* ---- symmetric linear solves (lanczos_amd.minres; MINRES, Paige & Saunders 1975) ------------------------------------------------
+ * (A - shift I) x = b for the REAL symmetric matrix set, definite or not: the Lanczos three-term recurrence with no basis stored and
+ * the solution updated from the QR factorisation of the tridiagonal matrix, one Givens rotation per step (SciPy's sign convention:
+ * cs = -1, sn = 0 at the start).  Seven padded vectors of their own: the fixed-n run's basis, the thick-restart basis and the
+ * propagator's basis on the same handle are untouched; every matrix setter drops the state.  A step is four launches - the matrix'
+ * product with its x_own . y epilogue, a one-block kernel for alpha, one streaming pass (the three-term, the partials of |r|^2 and the
+ * END of the step before: w and x += phi w, whose scalars were not known sooner) and a one-block kernel for beta, the rotation and
+ * the stopping rule.  The update therefore lags one step inside lz_minres_run and is applied before it returns: between two calls
+ * the state is never lagged.  v_{k+1} = r / beta is never stored by a pass of its own: the product divides as it reads r where the
+ * matrix has the scale-on-read SpMV (a row-class coded or ELL-ordered stencil), else the product runs on r and the streaming pass
+ * divides.  No atomics: the same input gives the same bits.  One rank only: LZ_ERR_STATE with no real matrix, on a handle with a
+ * communicator and with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE; every call behind lz_minres_begin answers LZ_ERR_STATE before
+ * it and after a matrix setter. */
+/* allocate and zero, r0 = b - (A - shift I) x0 by one product (x0 NULL: r0 = b, no product), beta1 = |r0|.  b, x0: n doubles. */
+int lz_minres_begin(lz_handle h, const double* b, const double* x0, double shift);
+/* up to iters steps without a host synchronisation, then the pending update, then one synchronisation.  Stopping rule, on the device:
+ * after the first step with phibar <= rtol beta1, or whose beta is zero or not finite, the done flag is set and every later launch of
+ * this section returns at once (the products of the rest of the call still run; their output is not read).  A call on a state that
+ * is done enqueues nothing.  state_out (8 doubles, may be NULL): steps done in total, done, phibar (the estimate of
+ * |b - (A - shift I) x|), beta1, sqrt(tnorm2) (an estimate of |A - shift I|), the last alpha, the last beta, the last phi. */
+int lz_minres_run(lz_handle h, int iters, double rtol, double* state_out);
+/* out[0 .. count) = phibar after steps 1 .. count.  count may pass the steps done, up to the steps lz_minres_run was asked for so far
+ * (the history holds 1024 at least): a step that did not run, or that lz_minres_set_state skipped, reads zero. */
+int lz_minres_history(lz_handle h, double* out, int count);
+/* a vector of the state as n host doubles; with k the step that would run next: x_{k-1}, v_k (formed on read: r / |r|), v_{k-1},
+ * w_{k-1}, w_{k-2}, and r = the un-normalised v_k.  which | LZ_MINRES_RAW: the padded device vector as it is (lz_padded_rows(n)
+ * doubles; for LZ_MINRES_V: r's, divided) - the tests' look at the padding. */
+enum { LZ_MINRES_X = 0, LZ_MINRES_V = 1, LZ_MINRES_VPREV = 2, LZ_MINRES_W1 = 3, LZ_MINRES_W2 = 4, LZ_MINRES_R = 5, LZ_MINRES_RAW = 8 };
+int lz_minres_get(lz_handle h, int which, double* out);
+/* upload the state that step k >= 1 starts from (allocates as lz_minres_begin does): x_{k-1}, v_k (taken as given, not normalised),
+ * v_{k-1}, w_{k-1}, w_{k-2} - n doubles each - and scalars[9] = beta_k, cs, sn, dbar, epsln, phibar, tnorm2, beta1, shift.  The
+ * history of steps 1 .. k - 1 reads zero.  Tests drive one step from chosen numbers with it, as lz_os_state_set does for lz_os_step. */
+int lz_minres_set_state(lz_handle h, int k, const double* x, const double* vk, const double* vkm1, const double* wkm1, const double* wkm2,
+                        const double* scalars);
+/* ms_out[0] = the device time (hipEvents) of one product of the plan, ms_out[1] = of one k_minres_step with the three-term and the
+ * lagged update: each the mean of reps launches behind one warm-up launch.  The state is spent afterwards (LZ_ERR_STATE until the next
+ * lz_minres_begin).  The measurements of tools/minres_probe.py */
+int lz_minres_step_time(lz_handle h, int reps, double* ms_out);
+/* out[0] = launches per iteration of the plan for the matrix set, product included; out[1] = 1 where the product scales on read;
+ * out[2] = 1 while a state is live */
+int lz_minres_info(lz_handle h, int* out);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

@@ -203,6 +203,13 @@ SIGNATURES = {
     "lz_expm_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_expm_product_time": (C.c_int, [_P, C.c_int, _D]),
     "lz_expm_set_product": (C.c_int, [_P, C.c_int]),
+    "lz_minres_begin": (C.c_int, [_P, _D, _D, C.c_double]),
+    "lz_minres_run": (C.c_int, [_P, C.c_int, C.c_double, _D]),
+    "lz_minres_history": (C.c_int, [_P, _D, C.c_int]),
+    "lz_minres_get": (C.c_int, [_P, C.c_int, _D]),
+    "lz_minres_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
+    "lz_minres_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_minres_step_time": (C.c_int, [_P, C.c_int, _D]),
     "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
     "lz_gk_set_dense": (C.c_int, [_P, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int]),
     "lz_gk_plan": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1086,6 +1093,61 @@ class Handle:
         out = np.empty((int(count), self.padded_rows(self.rows)))
         self.check(self.lib.lz_expm_get_rows(self._h, int(j0), int(count), dptr(out), out.shape[1]))
         return np.ascontiguousarray(out[:, : self.rows])
+
+    # -- symmetric linear solves (lanczos_amd.minres): seven vectors of their own on the real matrix set
+    MINRES_VECTORS = {"x": 0, "v": 1, "v_prev": 2, "w1": 3, "w2": 4, "r": 5}
+    MINRES_STATE = ("iterations", "done", "phibar", "beta1", "anorm", "alpha", "beta", "phi")
+
+    def minres_begin(self, b, x0=None, shift=0.0):
+        """``r0 = b - (A - shift I) x0`` (``x0`` None: ``r0 = b``); a fresh state"""
+        b = f64(b)
+        assert b.shape == (self.rows,)
+        if x0 is not None:
+            x0 = f64(x0)
+            assert x0.shape == (self.rows,)
+        self.check(self.lib.lz_minres_begin(self._h, dptr(b), dptr(x0) if x0 is not None else None, float(shift)))
+
+    def minres_run(self, iters, rtol):
+        """up to ``iters`` steps with no host synchronisation between them -> ``{"iterations", "done", "phibar", "beta1", "anorm", "alpha",
+        "beta", "phi"}`` (the totals and the last step's scalars)"""
+        out = np.zeros(8)
+        self.check(self.lib.lz_minres_run(self._h, int(iters), float(rtol), dptr(out)))
+        st = dict(zip(self.MINRES_STATE, (float(v) for v in out)))
+        st["iterations"], st["done"] = int(out[0]), bool(out[1])
+        return st
+
+    def minres_history(self, count):
+        """``phibar`` after steps ``1 .. count``"""
+        out = np.zeros(int(count))
+        self.check(self.lib.lz_minres_history(self._h, dptr(out), int(count)))
+        return out
+
+    def minres_get(self, which, raw=False):
+        """a vector of the state (``"x"``, ``"v"`` = v_k, ``"v_prev"``, ``"w1"`` = w_{k-1}, ``"w2"``, ``"r"``) as ``n`` doubles;
+        ``raw``: the padded device vector"""
+        out = np.empty(self.padded_rows(self.rows) if raw else self.rows)
+        self.check(self.lib.lz_minres_get(self._h, self.MINRES_VECTORS[which] | (8 if raw else 0), dptr(out)))
+        return out
+
+    def minres_set_state(self, k, x, vk, vkm1, wkm1, wkm2, scalars):
+        """the state step ``k`` starts from; ``scalars`` = (beta_k, cs, sn, dbar, epsln, phibar, tnorm2, beta1, shift)"""
+        vecs = [f64(v) for v in (x, vk, vkm1, wkm1, wkm2)]
+        assert all(v.shape == (self.rows,) for v in vecs)
+        sc = f64(scalars)
+        assert sc.shape == (9,)
+        self.check(self.lib.lz_minres_set_state(self._h, int(k), *(dptr(v) for v in vecs), dptr(sc)))
+
+    def minres_step_time(self, reps=20):
+        """device milliseconds of ``(one product, one k_minres_step)`` of the plan (means of ``reps`` launches); spends the state"""
+        out = np.zeros(2)
+        self.check(self.lib.lz_minres_step_time(self._h, int(reps), dptr(out)))
+        return float(out[0]), float(out[1])
+
+    def minres_info(self):
+        """{"launches_per_iteration", "scale_on_read": the product forms v = r / beta as it reads r, "live"}"""
+        out = (C.c_int * 3)()
+        self.check(self.lib.lz_minres_info(self._h, out))
+        return {"launches_per_iteration": int(out[0]), "scale_on_read": bool(out[1]), "live": bool(out[2])}
 
     def zspmv_real(self, x):
         """A x for the real matrix set and a complex x, through the mixed product (in the form ``expm_set_product`` selects), host vectors"""

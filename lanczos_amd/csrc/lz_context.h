@@ -1,5 +1,5 @@
 // Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip, lz_orth.hip and the
-// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip, lz_expm.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip, lz_expm.hip, lz_minres.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -129,6 +129,24 @@ struct ExpmState {
   int product = 0;          // the form the last mixed product took: 0 none yet, 1 two launches of the real product, 2 the two-plane kernel
   double* xtmp = nullptr;   // lz_zspmv_real_host: x and y in planar form (4 padded vectors)
   int64_t xtmp_pad = 0;
+};
+
+// MINRES (lz_minres.hip; lanczos_amd.minres): (A - shift I) x = b on the real matrix set.  No basis: seven padded vectors of ld doubles
+// each behind vec, in this order - V[0], V[1] (v_j lives in V[j & 1]), Y (the product), R (the un-normalised residual: v_{k} = R / nu),
+// W[0], W[1] (w_j lives in W[j & 1]), X - and the small device state of minres_layout (lz_minres.hip).  Between two calls of the ABI
+// the pending update of the lagged step is applied (the flush), so steps / done below mirror the device.
+struct MinresState {
+  double* vec = nullptr;   // 7 * ld doubles; [rows, ld) of each is zero
+  double* ds = nullptr;    // scalars (kMinresDoubles)
+  int* di = nullptr;       // done, step counter (kMinresInts)
+  double* part = nullptr;  // the product's alpha partials, then the step kernel's |r|^2 partials
+  size_t part_cap = 0;
+  double* hist = nullptr;  // phibar after every step
+  int hist_cap = 0;
+  int64_t ld = 0;
+  bool live = false;       // lz_minres_begin / lz_minres_set_state ran on the matrix now set
+  int steps = 0;           // steps done (the device's counter, as of the last synchronisation)
+  int done = 0;
 };
 
 struct lz_context {
@@ -272,6 +290,7 @@ struct lz_context {
   GkState gk;    // Golub-Kahan-Lanczos (lz_gk_*): freed by gk_free
   ZState z;      // complex Hermitian matrix and its thick-restart basis (lz_set_*_cplx, lz_ztrl_*): freed by z_free
   ExpmState ex;  // the propagator's basis (lz_expm_*): freed by expm_free
+  MinresState mr;  // the linear solver's vectors (lz_minres_*): freed by minres_free, dropped by every matrix setter (z_drop_matrix)
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -388,6 +407,9 @@ void z_matvec(lz_handle h, const double* x, double* y, int64_t ld);
 
 // matrix exponential action (lz_expm.hip): releases everything h->ex owns (lz_destroy)
 void expm_free(lz_handle h);
+
+// MINRES (lz_minres.hip): releases everything h->mr owns (lz_destroy)
+void minres_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.
