@@ -668,6 +668,54 @@ int lz_minres_step_time(lz_handle h, int reps, double* ms_out);
  * out[2] = 1 while a state is live */
 int lz_minres_info(lz_handle h, int* out);
 
+/* ---- least-squares solves (lanczos_amd.lsmr; LSMR, Fong & Saunders 2011) --------------------------------------------------------
+ * min |A x - b|^2 + damp^2 |x|^2 for the rectangular matrix lz_gk_set_csr / lz_gk_set_dense holds (tall orientation, p x q):
+ * transposed == 0 means A is that matrix (b: p doubles, x: q doubles), transposed == 1 means A is its transpose (b: q, x: p).
+ * Golub-Kahan bidiagonalisation with no basis kept and SciPy's lsmr scalar for scalar (the same rotations, the same estimates of |r|,
+ * |A^T r|, |A| and cond(A)).  Seven padded vectors of its own, two of b's length and five of x's: no lz_gk_begin is needed, the bases
+ * of lz_gk_*, the square matrix and every other state on the handle are untouched; lz_gk_set_csr / lz_gk_set_dense drop the state.
+ * u and v are kept un-normalised together with their divisors, and every kernel divides where it reads.  A step is the two products
+ * and four launches of its own: one streaming pass over b's length (u = A v - alpha u with the partials of |u|^2: 24 B a row), a
+ * one-block kernel for beta, one streaming pass over x's length (v = A^T u - beta v with the partials of |v|^2 and, from the same
+ * load of v, the END of the step before: hbar, x, h and the partials of |x|^2, whose scalars were not known before alpha was: 72 B a
+ * row) and a one-block kernel for alpha, the rotations, the estimates and the stopping tests.  The update therefore lags one step
+ * inside lz_lsmr_run and is applied before it returns: between two calls the state is never lagged.  The tests of step k use
+ * |x_{k-1}|, which the lagged pass yields (SciPy uses |x_k|).  No atomics: the same input gives the same bits.  One rank only:
+ * LZ_ERR_STATE with no rectangular matrix, on a handle with a communicator and with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE;
+ * every call behind lz_lsmr_begin answers LZ_ERR_STATE before it and after lz_gk_set_csr / lz_gk_set_dense. */
+/* allocate and zero, u = b - A x0 by one product (x0 NULL: u = b, no product), beta_1 = |u|, v = A^T u / beta_1, alpha_1 = |v|; the
+ * pending update is the empty one that makes h_1 = v_1.  The state is done at once (istop 0) when alpha_1 beta_1 = 0 or b = 0. */
+int lz_lsmr_begin(lz_handle h, int transposed, const double* b, const double* x0, double damp);
+/* up to iters steps without a host synchronisation, then the pending update, then one synchronisation.  The stopping tests run on
+ * the device with SciPy's codes 1 .. 6 (conlim <= 0: no limit on cond(A)); the first step that meets one sets the done flag and every
+ * later launch of this section in the call returns at once (the products of the rest of the call still run; their output is not
+ * read).  A beta that is not finite sets the flag with the state as it is and reports 7.  A call on a state that is done enqueues
+ * nothing.  state_out (16 doubles, may be NULL): steps done in total, done, istop, normr, normar, normA, condA, |x| of the x now
+ * held, alpha, beta, rho, rhobar, zeta, zetabar, |x_{k-1}| as the last step's tests saw it, normb. */
+int lz_lsmr_run(lz_handle h, int iters, double atol, double btol, double conlim, double* state_out);
+/* a vector of the state as host doubles: x, u_k and v_k (formed on read: divided as the kernels divide), h, hbar.  which |
+ * LZ_LSMR_RAW: the padded device vector as it is (lz_padded_rows of its length; U and V un-normalised: beta_k u_k and alpha_k v_k) -
+ * the tests' look at the padding. */
+enum { LZ_LSMR_X = 0, LZ_LSMR_U = 1, LZ_LSMR_V = 2, LZ_LSMR_H = 3, LZ_LSMR_HBAR = 4, LZ_LSMR_RAW = 8 };
+int lz_lsmr_get(lz_handle h, int which, double* out);
+/* upload the state that step k >= 1 starts from (allocates as lz_lsmr_begin does) with the update of step k - 1 pending: x_{k-2},
+ * u_k and v_k (taken as given, their divisors set to 1), h_{k-1}, hbar_{k-2}, and scalars[24] = alpha, beta, alphabar, rho, rhobar,
+ * cbar, sbar, zeta, zetabar, betadd, betad, rhodold, tautildeold, thetatilde, d, normA2, maxrbar, minrbar, damp, normb, and c1, c2,
+ * c3 of the pending update (hbar = h - c1 hbar, x += c2 hbar, h = v_k - c3 h), one spare.  The history of steps 1 .. k - 1 reads
+ * zero.  Tests drive one step from chosen numbers with it. */
+int lz_lsmr_set_state(lz_handle h, int transposed, int k, const double* x, const double* u, const double* v, const double* hvec,
+                      const double* hbar, const double* scalars);
+/* out[2 i], out[2 i + 1] = normr, normar after step i + 1, i < count.  count may pass the steps done, up to the steps lz_lsmr_run was
+ * asked for so far (the history holds 1024 at least): a step that did not run reads zero. */
+int lz_lsmr_history(lz_handle h, double* out, int count);
+/* out[0] = launches of the solver's own per iteration beside the two products (4); out[1] = 1 while a state is live; out[2] = its
+ * transposed */
+int lz_lsmr_info(lz_handle h, int* out);
+/* ms_out[0 .. 4) = the device times (hipEvents) of the product A v, of k_lsmr_u, of the product A^T u and of k_lsmr_v with the
+ * lagged update: each the mean of reps launches behind one warm-up launch.  The state is spent afterwards (LZ_ERR_STATE until the
+ * next lz_lsmr_begin).  The measurements of tools/lsmr_probe.py */
+int lz_lsmr_step_time(lz_handle h, int reps, double* ms_out);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

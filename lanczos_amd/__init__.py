@@ -18,7 +18,8 @@ from .svds import svds
 from .eigs import eigs
 from .expm import expm_multiply
 from .minres import minres
+from .lsmr import lsmr
 
-__all__ = ["Lanczos", "IrrLanczos", "Hamiltonian", "StencilOperator", "eigsh", "svds", "eigs", "expm_multiply", "minres", "LanczosHipError", "load_library", "FLAG_PROFILE", "FLAG_QTW_MFMA", "FLAG_QTW_VALU",
+__all__ = ["Lanczos", "IrrLanczos", "Hamiltonian", "StencilOperator", "eigsh", "svds", "eigs", "expm_multiply", "minres", "lsmr", "LanczosHipError", "load_library", "FLAG_PROFILE", "FLAG_QTW_MFMA", "FLAG_QTW_VALU",
            "FLAG_SPMV_SCALAR", "FLAG_FUSED_NORM", "FLAG_REORTH_PARTIAL"]
 __version__ = "0.1.0"

@@ -210,6 +210,13 @@ SIGNATURES = {
     "lz_minres_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
     "lz_minres_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_minres_step_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_lsmr_begin": (C.c_int, [_P, C.c_int, _D, _D, C.c_double]),
+    "lz_lsmr_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double, _D]),
+    "lz_lsmr_get": (C.c_int, [_P, C.c_int, _D]),
+    "lz_lsmr_set_state": (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _D, _D, _D, _D]),
+    "lz_lsmr_history": (C.c_int, [_P, _D, C.c_int]),
+    "lz_lsmr_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_lsmr_step_time": (C.c_int, [_P, C.c_int, _D]),
     "lz_gk_set_csr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _I32, _I32, _D, _I32, _I32, _D]),
     "lz_gk_set_dense": (C.c_int, [_P, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int]),
     "lz_gk_plan": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1148,6 +1155,75 @@ class Handle:
         out = (C.c_int * 3)()
         self.check(self.lib.lz_minres_info(self._h, out))
         return {"launches_per_iteration": int(out[0]), "scale_on_read": bool(out[1]), "live": bool(out[2])}
+
+    # -- least-squares solves (lanczos_amd.lsmr): seven vectors of their own on the rectangular (gk) matrix; A is that matrix (p x q) or,
+    # with ``transposed``, its transpose
+    LSMR_VECTORS = {"x": 0, "u": 1, "v": 2, "h": 3, "hbar": 4}
+    LSMR_STATE = ("iterations", "done", "istop", "normr", "normar", "normA", "condA", "normx", "alpha", "beta", "rho", "rhobar", "zeta",
+                  "zetabar", "normx_lagged", "normb")
+    LSMR_SCALARS = ("alpha", "beta", "alphabar", "rho", "rhobar", "cbar", "sbar", "zeta", "zetabar", "betadd", "betad", "rhodold",
+                    "tautildeold", "thetatilde", "d", "normA2", "maxrbar", "minrbar", "damp", "normb", "c1", "c2", "c3")
+
+    def _lsmr_lengths(self, transposed):
+        """(length of b, length of x) for ``A`` = the gk matrix or its transpose"""
+        p, q = self.gk_shape
+        return (q, p) if transposed else (p, q)
+
+    def lsmr_begin(self, b, x0=None, damp=0.0, transposed=False):
+        """``u = b - A x0`` (``x0`` None: ``u = b``), ``v = A^T u``; a fresh state with the empty pending update"""
+        nb, nx = self._lsmr_lengths(transposed)
+        b = f64(b)
+        assert b.shape == (nb,)
+        if x0 is not None:
+            x0 = f64(x0)
+            assert x0.shape == (nx,)
+        self.lsmr_transposed = bool(transposed)
+        self.check(self.lib.lz_lsmr_begin(self._h, 1 if transposed else 0, dptr(b), dptr(x0) if x0 is not None else None, float(damp)))
+
+    def lsmr_run(self, iters, atol, btol, conlim):
+        """up to ``iters`` steps with no host synchronisation between them -> a dict of ``LSMR_STATE`` (the totals, the estimates and
+        the last step's scalars; ``normx`` is the norm of the ``x`` now held)"""
+        out = np.zeros(16)
+        self.check(self.lib.lz_lsmr_run(self._h, int(iters), float(atol), float(btol), float(conlim), dptr(out)))
+        st = dict(zip(self.LSMR_STATE, (float(v) for v in out)))
+        st["iterations"], st["done"], st["istop"] = int(out[0]), bool(out[1]), int(out[2])
+        return st
+
+    def lsmr_history(self, count):
+        """``(count, 2)``: ``normr``, ``normar`` after steps ``1 .. count``"""
+        out = np.zeros((int(count), 2))
+        self.check(self.lib.lz_lsmr_history(self._h, dptr(out), int(count)))
+        return out
+
+    def lsmr_get(self, which, raw=False):
+        """a vector of the state (``"x"``, ``"u"`` = u_k, ``"v"`` = v_k, ``"h"``, ``"hbar"``); ``raw``: the padded device vector"""
+        nb, nx = self._lsmr_lengths(self.lsmr_transposed)
+        n = nb if which == "u" else nx
+        out = np.empty(self.padded_rows(n) if raw else n)
+        self.check(self.lib.lz_lsmr_get(self._h, self.LSMR_VECTORS[which] | (8 if raw else 0), dptr(out)))
+        return out
+
+    def lsmr_set_state(self, k, x, u, v, hvec, hbar, scalars, transposed=False):
+        """the state step ``k`` starts from, the update of step ``k - 1`` pending; ``scalars``: the 23 of ``LSMR_SCALARS``"""
+        nb, nx = self._lsmr_lengths(transposed)
+        vecs = [f64(a) for a in (x, u, v, hvec, hbar)]
+        assert [a.shape for a in vecs] == [(nx,), (nb,), (nx,), (nx,), (nx,)]
+        sc = np.zeros(24)
+        sc[:23] = f64(scalars)
+        self.lsmr_transposed = bool(transposed)
+        self.check(self.lib.lz_lsmr_set_state(self._h, 1 if transposed else 0, int(k), *(dptr(a) for a in vecs), dptr(sc)))
+
+    def lsmr_step_time(self, reps=20):
+        """device milliseconds of ``(A v, k_lsmr_u, A^T u, k_lsmr_v)`` (means of ``reps`` launches); spends the state"""
+        out = np.zeros(4)
+        self.check(self.lib.lz_lsmr_step_time(self._h, int(reps), dptr(out)))
+        return tuple(float(v) for v in out)
+
+    def lsmr_info(self):
+        """{"own_launches_per_iteration": the solver's launches beside the two products, "live", "transposed"}"""
+        out = (C.c_int * 3)()
+        self.check(self.lib.lz_lsmr_info(self._h, out))
+        return {"own_launches_per_iteration": int(out[0]), "live": bool(out[1]), "transposed": bool(out[2])}
 
     def zspmv_real(self, x):
         """A x for the real matrix set and a complex x, through the mixed product (in the form ``expm_set_product`` selects), host vectors"""

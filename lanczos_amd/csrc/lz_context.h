@@ -1,5 +1,5 @@
 // Shared host-side state of the C ABI (lz_api.hip, lz_loops.hip, lz_matrix.hip, lz_ritz.hip, lz_twosided_api.hip, lz_orth.hip and the
-// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip, lz_expm.hip, lz_minres.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
+// three solvers on it, lz_trl_api.hip, lz_gk_api.hip and lz_ztrl_api.hip, lz_zspmv.hip, lz_expm.hip, lz_minres.hip, lz_lsmr.hip): the handle, the error macros, the per-launch profiling scope and the helpers those files call across each other.  Internal: nothing
 // here is part of include/lanczos_hip.h.
 #pragma once
 
@@ -149,6 +149,27 @@ struct MinresState {
   int done = 0;
 };
 
+// LSMR (lz_lsmr.hip; lanczos_amd.lsmr): min |A x - b|^2 + damp^2 |x|^2 on the rectangular matrix h->gk holds (A is that matrix or, with
+// transposed, its transpose).  No basis: two padded vectors of b's length behind bvec - UH (the un-normalised u: u_k = UH / nu_u), Y (the
+// product A v) - and five of x's length behind xvec - VH (the un-normalised v: v_k = VH / nu_v), Z (the product A^T u), H, HBAR, X - and
+// the small device state of lz_lsmr.hip.  Between two calls of the ABI the pending update of the lagged step is applied (the flush),
+// so steps / done below mirror the device.
+struct LsmrState {
+  double* bvec = nullptr;  // 2 * bpad doubles; [blen, bpad) of each is zero
+  double* xvec = nullptr;  // 5 * xpad doubles; [xlen, xpad) of each is zero
+  double* ds = nullptr;    // scalars (kLsmrDoubles)
+  int* di = nullptr;       // done, step counter, istop, fresh (kLsmrInts)
+  double* part = nullptr;  // the partials of |u|^2, |v|^2, |x|^2 (kLsmrMaxBlocks each) and a spare set for lz_lsmr_begin
+  double* hist = nullptr;  // normr, normar after every step
+  int hist_cap = 0;
+  int64_t blen = 0, bpad = 0, xlen = 0, xpad = 0;
+  int transposed = 0;
+  bool live = false;       // lz_lsmr_begin / lz_lsmr_set_state ran on the gk matrix now set
+  bool pending = false;    // the update of the last step has not been applied (behind begin / set_state: the flush of a run applies it)
+  int steps = 0;           // steps done (the device's counter, as of the last synchronisation)
+  int done = 0;
+};
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -291,6 +312,7 @@ struct lz_context {
   ZState z;      // complex Hermitian matrix and its thick-restart basis (lz_set_*_cplx, lz_ztrl_*): freed by z_free
   ExpmState ex;  // the propagator's basis (lz_expm_*): freed by expm_free
   MinresState mr;  // the linear solver's vectors (lz_minres_*): freed by minres_free, dropped by every matrix setter (z_drop_matrix)
+  LsmrState ls;    // the least-squares solver's vectors (lz_lsmr_*): freed by lsmr_free, dropped by lz_gk_set_csr / lz_gk_set_dense
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -397,6 +419,8 @@ int upload_csr(lz_handle h, CsrDev& A, const char* who, int64_t rows, int64_t nc
 
 // Golub-Kahan-Lanczos state (lz_gk_api.hip): releases everything h->gk owns (lz_destroy)
 void gk_free(lz_handle h);
+// y = Aop x (transpose == 0) or Aop^T x with whichever rectangular operator h->gk holds (CSR or the one dense copy); y[len .. pad) = 0
+hipError_t gk_product(lz_handle h, int transpose, const double* x, double* y, int64_t pad);
 
 // complex Hermitian state (lz_zspmv.hip).  z_drop_matrix: what every real matrix setter calls - the complex matrix is gone (its basis
 // stays allocated for the next one); z_free: everything h->z owns (lz_destroy)
@@ -410,6 +434,9 @@ void expm_free(lz_handle h);
 
 // MINRES (lz_minres.hip): releases everything h->mr owns (lz_destroy)
 void minres_free(lz_handle h);
+
+// LSMR (lz_lsmr.hip): releases everything h->ls owns (lz_destroy)
+void lsmr_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.

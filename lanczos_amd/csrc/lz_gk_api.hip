@@ -91,13 +91,6 @@ void gk_free_dense(DenseDev& D) {
   D = DenseDev();
 }
 
-// y = Aop x (transpose == 0) or Aop^T x with whichever operator the state holds; y[len .. pad) = 0
-hipError_t gk_product(lz_handle h, int transpose, const double* x, double* y, int64_t pad) {
-  const GkState& g = h->gk;
-  if (!g.D.S) return launch_spmv_rect(transpose ? g.AT : g.A, x, y, pad, h->stream);
-  return (transpose != 0) == g.D.stored_t ? launch_dense_rowdot(g.D, x, y, pad, h->stream) : launch_dense_colsum(g.D, x, y, pad, h->stream);
-}
-
 // the work vectors of both sides, sized for (p, q); the basis of an earlier operator is gone by now
 int gk_alloc_work(lz_handle h, int64_t p, int64_t q) {
   GkState& g = h->gk;
@@ -133,6 +126,13 @@ int gk_store_x(lz_handle h, int side, int k, const double* x) {
 
 namespace lz {
 namespace api {
+// y = Aop x (transpose == 0) or Aop^T x with whichever operator the state holds; y[len .. pad) = 0
+hipError_t gk_product(lz_handle h, int transpose, const double* x, double* y, int64_t pad) {
+  const GkState& g = h->gk;
+  if (!g.D.S) return launch_spmv_rect(transpose ? g.AT : g.A, x, y, pad, h->stream);
+  return (transpose != 0) == g.D.stored_t ? launch_dense_rowdot(g.D, x, y, pad, h->stream) : launch_dense_colsum(g.D, x, y, pad, h->stream);
+}
+
 void gk_free(lz_handle h) {
   GkState& g = h->gk;
   gk_free_csr(g.A);
@@ -162,6 +162,7 @@ int lz_gk_set_csr(lz_handle h, int64_t p, int64_t q, int64_t nnz, const int32_t*
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   GkState& g = h->gk;
   g.set = false;
+  h->ls.live = false;  // (the least-squares state was made for the matrix that goes)
   LZ_TRY(gk_free_basis(h));
   gk_free_dense(g.D);
   int fixed_k = 0, max_nnz = 0, max_nnzT = 0;
@@ -186,6 +187,7 @@ int lz_gk_set_dense(lz_handle h, int64_t p, int64_t q, const double* S, int64_t 
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   GkState& g = h->gk;
   g.set = false;
+  h->ls.live = false;  // (the least-squares state was made for the matrix that goes)
   LZ_TRY(gk_free_basis(h));
   gk_free_csr(g.A);
   gk_free_csr(g.AT);
