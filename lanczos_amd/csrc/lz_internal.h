@@ -347,11 +347,12 @@ void launch_omega(const double* part, int np, double* nrm2, const double* alpha,
 // the gates (ist: omega_onered_ints(n) ints).
 inline size_t omega_onered_ints(int n) { return (size_t)4 + n + 2; }
 void launch_partial_onered_post(double* buf, double* bufn, int nzero_next, int m, int ldp, double* alpha_slot, double* nrm2, const double* alpha,
-                                int j, int n, double* st, int* ist, double kappa, hipStream_t s);
+                                int j, int n, double* st, int* ist, double kappa, double* beta_prev, double* uu_keep, hipStream_t s);
 // r = r - beta vm (vm may be nullptr: r unchanged) + block partials of [r.r, u.r, u.u] at part[b], part[G + b], part[2 G + b]; returns G
 int launch_three_term_self(double* r, const double* u, const double* vm, const double* beta, int64_t len, double* part, hipStream_t s);
 void launch_fused_prepare(double* c, int j, double* beta_slot, hipStream_t s);
-void launch_onereduce_prepare(double* buf, int m, int ldp, double* alpha_slot, double* bad, hipStream_t s);
+void launch_onereduce_prepare(double* buf, int m, int ldp, double* alpha_slot, double* bad, double* beta_prev, double* uu_keep, hipStream_t s);
+void launch_onereduce_finish(const double* buf, int ldp, double* alpha_last, double* beta_last, const double* uu_keep, hipStream_t s);
 // r = (r - alpha v_j) - beta v_jm1 ; part[b] = partial ||r||^2 ; returns number of partials
 int launch_three_term(double* r, const double* vj, const double* vjm1, const double* alpha, const double* beta,
                       int64_t len, double* part, hipStream_t s);

@@ -219,7 +219,8 @@ static QtwFuse qtw_prologue_fuse(lz_handle h, int j, const double* apart, int np
 // State entering step j: r holds the two-term residual r'' = A u - beta v_{j-2} of the newest vector u = v_{j-1} (at j = 0:
 // r'' = A v0, u = v0 in basis row 0), and the local partial of alpha = u.(A u) sits in the reduce buffer.  Step j:
 //   pass 1 dots rows 0..j-1 against BOTH columns (r'', u) + the three self terms   -> one all-reduce with alpha
-//   prepare: alpha, c_i = V_i.r'' - alpha V_i.u, |r|^2 = r''.r'' - 2 alpha u.r'' + alpha^2 u.u
+//   prepare: alpha = u.(A u) / u.u, c_i = V_i.r'' - alpha V_i.u, |r|^2 = r''.r'' - 2 alpha u.r'' + alpha^2 u.u; the beta of the
+//            step before *= sqrt(u.u / the u.u before): the three-sum norm left u that far off unit length
 //   r = r'' - alpha u;  update: beta = |r|, V[j] = 2 r/beta - sum c_i/beta V_i - ...   (unchanged kernels from here)
 //   exchange V[j]; r = A V[j] (alpha partial into the buffer); r'' = r - beta V[j-1]
 inline int onered_ldp(int m) { return qtw_ldp(m + 2); }
@@ -254,6 +255,7 @@ static int step_onereduce_head(lz_handle h, int j, int urow, double* part, doubl
 
 int run_loop_onereduce(lz_handle h, int n) {
   const double M = (double)h->rows;
+  double* const uu_keep = h->d_beta + n;  // (d_beta has n + 1 doubles, the coefficients use n - 1) u.u of the step before
   LZ_TRY(step_spmv(h, 0, h->d_c + onered_slot(0), false));  // warm-up: r'' = A v0 (Lanczos.py:108), alpha0 partial
   for (int j = 0; j < n; ++j) {
     begin_iter(h, j);
@@ -261,7 +263,10 @@ int run_loop_onereduce(lz_handle h, int n) {
     LZ_TRY(step_onereduce_head(h, j, urow, h->d_part, h->d_c, nullptr, nullptr));
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
-      launch_onereduce_prepare(h->d_c, j, onered_ldp(j), h->d_alpha + urow, h->d_nrm2 + 1, h->stream);  // j = 0: alpha[0] of the warm-up, rewritten below
+      // (j = 0: alpha[0] of the warm-up, rewritten below.  Step 0's beta has Python's index -1, the slot the last step rewrites:
+      // the first beta that the next u.u corrects is step 1's)
+      launch_onereduce_prepare(h->d_c, j, onered_ldp(j), h->d_alpha + urow, h->d_nrm2 + 1, j >= 2 ? beta_slot(h, n, j - 1) : nullptr, uu_keep,
+                               h->stream);
       LZ_TRY(check_launch(h, "onereduce_prepare"));
     }
     LZ_TRY(step_two_term(h, basis_row(h, urow), h->d_alpha + urow, "three_term(alpha)"));  // r = r'' - alpha u
@@ -272,9 +277,17 @@ int run_loop_onereduce(lz_handle h, int n) {
       LZ_TRY(check_launch(h, "update"));
     }
     const bool last = j == n - 1;
-    LZ_TRY(step_spmv(h, j, last ? h->d_alpha + j : h->d_c + onered_slot(j + 1), last));  // the last alpha has no pass to ride on
+    LZ_TRY(step_spmv(h, j, h->d_c + onered_slot(last ? 0 : j + 1), false));
     // r'' = A V[j] - beta V[j-1]; at j = 0 the reference's V[-1] is the zero row
     if (!last && j > 0) LZ_TRY(step_two_term(h, basis_row(h, j - 1), beta_slot(h, n, j), "three_term(beta)"));
+  }
+  // The last alpha has no sweep to ride on: it travels with the self terms of a pass over no rows, whose u.u puts the last alpha and
+  // the last beta on the length of the last vector (k_onereduce_prepare) - one all-reduce, as the lone alpha was
+  LZ_TRY(step_onereduce_head(h, 0, n - 1, h->d_part, h->d_c, nullptr, nullptr));
+  {
+    Scope sc(h, LZ_K_FINAL, 0, 0);
+    launch_onereduce_finish(h->d_c, onered_ldp(0), h->d_alpha + (n - 1), n >= 2 ? beta_slot(h, n, n - 1) : nullptr, uu_keep, h->stream);
+    LZ_TRY(check_launch(h, "onereduce_finish"));
   }
   return LZ_OK;
 }
@@ -1178,7 +1191,7 @@ int run_loop_partial_device(lz_handle h, int n, int j0 = 0, const double* state_
 //            [r'' = A v_j - beta v_{j-1} + the three self terms' partials]  [their sums + alpha's into the next buffer]
 // Two buffers alternate (the update of step j still reads buffer j & 1 while the post kernel clears the other).  No host
 // synchronisation inside the loop over RCCL.  The three-sum ||r||^2 cancels like the full one-reduce loop's: same guard, same
-// repeat of the solve (on the three-collective device loop) when it fires.
+// repeat of the solve (on the three-collective device loop) when it fires; same coefficients relative to u.u, same last alpha.
 int run_loop_partial_onereduce(lz_handle h, int n) {
   const double M = (double)h->rows;
   if (h->om_n < n + 4) {  // (omega_onered_ints(n) <= omega_state_ints(n + 4) + 1)
@@ -1187,10 +1200,11 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
     h->om_n = n + 4;
   }
   const double kappa = h->tune[20] > 0 ? (double)h->tune[20] : 4.0;
+  double* const uu_keep = h->d_beta + n;  // (d_beta has n + 1 doubles, the coefficients use n - 1) u.u of the step before
   const size_t bstride = (size_t)2 * qtw_ldp(n + 2) + 8;
   {
     Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_partial_onered_post(nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, -1, n, h->d_om, h->d_omi, kappa, h->stream);
+    launch_partial_onered_post(nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, -1, n, h->d_om, h->d_omi, kappa, nullptr, nullptr, h->stream);
     LZ_TRY(check_launch(h, "partial_onered_post(init)"));
   }
   unsigned* ticket = reinterpret_cast<unsigned*>(h->d_omi + omega_onered_ints(n));
@@ -1214,7 +1228,7 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
     {
       Scope sc(h, LZ_K_FINAL, 0, 0);
       launch_partial_onered_post(buf, last ? nullptr : bufn, last ? 0 : onered_slot(j + 1) + 1, m, ldp, h->d_alpha + urow, h->d_nrm2, h->d_alpha, j, n,
-                                 h->d_om, h->d_omi, kappa, h->stream);
+                                 h->d_om, h->d_omi, kappa, j >= 2 ? beta_slot(h, n, j - 1) : nullptr, uu_keep, h->stream);
       LZ_TRY(check_launch(h, "partial_onered_post"));
     }
     if (lean) {
@@ -1235,8 +1249,12 @@ int run_loop_partial_onereduce(lz_handle h, int n) {
         LZ_TRY(check_launch(h, "scale_store(gated)"));
       }
     }
-    if (last) {
-      LZ_TRY(step_spmv(h, j, h->d_alpha + j, true));  // the last alpha has no pass to ride on
+    if (last) {  // the last alpha travels with the last vector's u.u (an ungated pass over no rows), as in run_loop_onereduce
+      LZ_TRY(step_spmv(h, j, h->d_c + onered_slot(0), false));
+      LZ_TRY(step_onereduce_head(h, 0, j, h->d_part, h->d_c, nullptr, nullptr));
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_onereduce_finish(h->d_c, onered_ldp(0), h->d_alpha + j, n >= 2 ? bslot : nullptr, uu_keep, h->stream);
+      LZ_TRY(check_launch(h, "onereduce_finish"));
       break;
     }
     // r'' = A V[j] - beta V[j-1] (at j = 0 the reference's V[-1] is the zero row) + the self terms of the next step's ||r||^2;

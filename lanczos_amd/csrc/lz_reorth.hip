@@ -186,7 +186,8 @@ void launch_omega(const double* part, int np, double* nrm2, const double* alpha,
 __global__ __launch_bounds__(kFinalThreads) void k_partial_onered_post(double* __restrict__ buf, double* __restrict__ bufn, int nzero_next, int m,
                                                                        int ldp, double* __restrict__ alpha_slot, double* __restrict__ nrm2,
                                                                        const double* __restrict__ alpha, int j, int n, double* __restrict__ st,
-                                                                       int* __restrict__ ist, double kappa) {
+                                                                       int* __restrict__ ist, double kappa, double* __restrict__ beta_prev,
+                                                                       double* __restrict__ uu_keep) {
   __shared__ double sm[kFinalThreads / 64];
   __shared__ double s_v;
   __shared__ int s_flag;
@@ -196,18 +197,23 @@ __global__ __launch_bounds__(kFinalThreads) void k_partial_onered_post(double* _
     return;
   }
   const int g = ist[j & 1];
-  const double a = buf[ldp + m + 2];
+  // alpha relative to u.u, and the beta of the step before put on u's measured length: as k_onereduce_prepare, and for its reason.
+  // (The recurrence below keeps the norms as they were when they formed their vectors: hb is not touched.)
+  const double uu = buf[ldp + m];
+  const double a = buf[ldp + m + 2] / uu;
   if (bufn)
     for (int i = threadIdx.x; i < nzero_next; i += kFinalThreads) bufn[i] = 0.0;
   if (g)
     for (int i = threadIdx.x; i < m; i += kFinalThreads) buf[i] = buf[i] - a * buf[ldp + i];
   if (threadIdx.x == 0) {
-    const double rr = buf[m], uu = buf[ldp + m], ur = buf[ldp + m + 1];
+    const double rr = buf[m], ur = buf[ldp + m + 1];
     const double v = (rr - 2.0 * a * ur) + a * a * uu;
     if (!(v > 1e-4 * rr)) nrm2[1] = 1.0;  // cancellation guard, as k_onereduce_prepare
     buf[m] = v;
     nrm2[0] = v;
     alpha_slot[0] = a;
+    if (beta_prev) beta_prev[0] = beta_prev[0] * sqrt(uu / uu_keep[0]);
+    uu_keep[0] = uu;
     s_v = v;
   }
   __syncthreads();
@@ -306,9 +312,9 @@ __global__ __launch_bounds__(kFinalThreads) void k_partial_onered_post(double* _
   }
 }
 void launch_partial_onered_post(double* buf, double* bufn, int nzero_next, int m, int ldp, double* alpha_slot, double* nrm2, const double* alpha,
-                                int j, int n, double* st, int* ist, double kappa, hipStream_t s) {
+                                int j, int n, double* st, int* ist, double kappa, double* beta_prev, double* uu_keep, hipStream_t s) {
   hipLaunchKernelGGL(k_partial_onered_post, dim3(1), dim3(kFinalThreads), 0, s, buf, bufn, nzero_next, m, ldp, alpha_slot, nrm2, alpha, j, n, st, ist,
-                     kappa);
+                     kappa, beta_prev, uu_keep);
 }
 
 // up to four independent k_final_sum's in one launch (block q adds its own run into its own slot)
@@ -1221,20 +1227,44 @@ __global__ void k_fused_prepare(double* __restrict__ c, int j, double* __restric
 // The three-sum form of |r|^2 cancels: its relative error is about eps (alpha^2 + beta^2) / beta^2.  Where that would
 // break the 1e-10 bar (|r|^2 below 1e-4 of r''.r'', or not positive at all: shifted spectra, a nearly converged Krylov
 // space) the kernel raises the sticky flag `bad`; lz_run then repeats the solve on the default two-reduce loop.
-__global__ void k_onereduce_prepare(double* __restrict__ buf, int m, int ldp, double* __restrict__ alpha_slot, double* __restrict__ bad) {
-  const double a = buf[ldp + m + 2];
+//
+// The same cancellation leaves u itself off unit length: u was scaled by 1 / sqrt(v) of the step before, so |u| - 1 carries that
+// v's relative error, alpha = u.(A u) twice that and beta all of it (on a shifted Laplacian, |alpha| = 3.5 beta, 13 to 21 times
+// the rounding of the two-reduce loop).  u.u arrives in this very buffer without cancellation, so the coefficients are taken
+// relative to it: alpha = u.(A u) / u.u here and in c_i, |r|^2 (the Rayleigh quotient of u as it is), and - now that the length
+// of the u it formed is known - the previous step's beta, sqrt(v) when it was stored, becomes |r| / |u_before| =
+// sqrt(v) sqrt(u.u / uu_keep[0]) (beta_prev; nullptr: no previous step of this run).  uu_keep[0] keeps u.u for the next call.
+__global__ void k_onereduce_prepare(double* __restrict__ buf, int m, int ldp, double* __restrict__ alpha_slot, double* __restrict__ bad,
+                                    double* __restrict__ beta_prev, double* __restrict__ uu_keep) {
+  const double uu = buf[ldp + m];
+  const double a = buf[ldp + m + 2] / uu;
   for (int i = threadIdx.x; i < m; i += blockDim.x) buf[i] = buf[i] - a * buf[ldp + i];
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double rr = buf[m], uu = buf[ldp + m], ur = buf[ldp + m + 1];
+    const double rr = buf[m], ur = buf[ldp + m + 1];
     const double v = (rr - 2.0 * a * ur) + a * a * uu;
     if (!(v > 1e-4 * rr)) bad[0] = 1.0;
     buf[m] = v;
     alpha_slot[0] = a;
+    if (beta_prev) beta_prev[0] = beta_prev[0] * sqrt(uu / uu_keep[0]);
+    uu_keep[0] = uu;
   }
 }
-void launch_onereduce_prepare(double* buf, int m, int ldp, double* alpha_slot, double* bad, hipStream_t s) {
-  hipLaunchKernelGGL(k_onereduce_prepare, dim3(1), dim3(kTPB), 0, s, buf, m, ldp, alpha_slot, bad);
+void launch_onereduce_prepare(double* buf, int m, int ldp, double* alpha_slot, double* bad, double* beta_prev, double* uu_keep, hipStream_t s) {
+  hipLaunchKernelGGL(k_onereduce_prepare, dim3(1), dim3(kTPB), 0, s, buf, m, ldp, alpha_slot, bad, beta_prev, uu_keep);
+}
+// After the last step of the one-reduce loop: buf holds the all-reduced self terms of a pass over no rows with u = the last basis row
+// (u.u at buf[ldp], u.(A u) at buf[ldp + 2]).  The last alpha and the last beta get what k_onereduce_prepare gives every earlier one.
+__global__ void k_onereduce_finish(const double* __restrict__ buf, int ldp, double* __restrict__ alpha_last, double* __restrict__ beta_last,
+                                   const double* __restrict__ uu_keep) {
+  if (threadIdx.x == 0) {
+    const double uu = buf[ldp];
+    alpha_last[0] = buf[ldp + 2] / uu;
+    if (beta_last) beta_last[0] = beta_last[0] * sqrt(uu / uu_keep[0]);
+  }
+}
+void launch_onereduce_finish(const double* buf, int ldp, double* alpha_last, double* beta_last, const double* uu_keep, hipStream_t s) {
+  hipLaunchKernelGGL(k_onereduce_finish, dim3(1), dim3(64), 0, s, buf, ldp, alpha_last, beta_last, uu_keep);
 }
 
 void launch_fused_prepare(double* c, int j, double* beta_slot, hipStream_t s) {

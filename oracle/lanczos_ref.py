@@ -245,6 +245,9 @@ def execute_lanczos_one_reduce(H, n, bounds, seed=99, v0=None, allreduce=None, s
     alpha, |r|^2 = (r''.r'' - 2 alpha u.r'') + alpha^2 u.u, w = (r'' - alpha u) / beta and - when the step sweeps - c_i = (p_i - alpha
     q_i) / beta, c_j = |r|^2 / beta^2, V[j] = 2 w - sum_{i<=j} c_i V_i (row j being w); else V[j] = w.  With ``partial`` the sweep runs
     only where the look-ahead gate (oracle/partial_gates.LookaheadGate: engine 8's device logic) says so, and p, q are zero otherwise.
+    In both loops alpha is u.(A u) / u.u, the beta of the step before is put on u's measured length once the next u.u is known (the
+    gate sees the norms as they were when they formed their vectors), and the last alpha shares its collective with the last vector's
+    u.u (k_onereduce_prepare, k_partial_onered_post, k_onereduce_finish).
     Calling convention as ``execute_lanczos_partitioned``.  Returns ``(alpha, beta, V, gates, allreduce_calls)``."""
     from . import partial_gates as pg
 
@@ -291,6 +294,7 @@ def execute_lanczos_one_reduce(H, n, bounds, seed=99, v0=None, allreduce=None, s
     alpha = np.zeros(n)
     beta = np.zeros(n - 1)
     gate = pg.LookaheadGate(n, kappa) if partial else None
+    uu_keep = 1.0  # u.u of the step before
     rs = matvec([V[0] for V in Vs])  # r'' = A v0
     apart = [np.dot(r, V[0]) for r, V in zip(rs, Vs)]
     for j in range(n):
@@ -304,6 +308,12 @@ def execute_lanczos_one_reduce(H, n, bounds, seed=99, v0=None, allreduce=None, s
             loc.append(np.concatenate([p_, [np.dot(r, r)], q_, [np.dot(u, u), np.dot(u, r), ap]]))
         buf = gsum(loc)  # THE collective of this iteration
         p_, rr, q_, uu, ur, a = buf[:m], buf[m], buf[m + 1:2 * m + 1], buf[2 * m + 1], buf[2 * m + 2], buf[2 * m + 3]
+        # both loops take the coefficients relative to u.u (k_onereduce_prepare, k_partial_onered_post): u was scaled by the
+        # cancelling three-sum norm of the step before, and u.u, which arrives without cancellation, says by how much that missed
+        a = a / uu
+        if j >= 2:
+            beta[j - 2] = beta[j - 2] * np.sqrt(uu / uu_keep)
+        uu_keep = uu
         alpha[urow] = a
         vv = (rr - 2.0 * a * ur) + a * a * uu
         bj = np.sqrt(vv)
@@ -321,7 +331,12 @@ def execute_lanczos_one_reduce(H, n, bounds, seed=99, v0=None, allreduce=None, s
         rs = matvec([V[j] for V in Vs])
         apart = [np.dot(V[j], r) for r, V in zip(rs, Vs)]
         if j == n - 1:
-            alpha[j] = gsum(apart)[0]  # the last alpha has no pass to ride on
+            # the last alpha has no pass to ride on: it travels with the last vector's u.u, which puts it and the last beta on
+            # that vector's length
+            fin = gsum([np.array([np.dot(V[j], V[j]), ap]) for V, ap in zip(Vs, apart)])
+            alpha[j] = fin[1] / fin[0]
+            if n >= 2:
+                beta[j - 1] = beta[j - 1] * np.sqrt(fin[0] / uu_keep)
             break
         if j > 0:
             rs = [r - V[j - 1] * bj for r, V in zip(rs, Vs)]

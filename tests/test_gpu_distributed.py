@@ -151,7 +151,7 @@ def test_partitioned_run_on_one_gpu(tmp_path, world):
                 assert r["sweeps"] == res[0][name]["sweeps"]
                 if name.endswith("_onereduce"):
                     # ONE all-reduce + one exchange per iteration, sweep or no sweep: (n + 1) exchanges + n
-                    # combined all-reduces + the last alpha - against exchange + three all-reduces per step in the device loop
+                    # combined all-reduces + the last alpha (with the last vector's u.u) - against exchange + three all-reduces per step in the device loop
                     assert r["engine"] == "partial-one-reduce" and r["misses"] == 0, (name, r)
                     assert r["comm_launches"] == 2 * r["n"] + 2, (name, r)
                     assert r["orth"] < 1e-6, (name, r)
@@ -165,7 +165,7 @@ def test_partitioned_run_on_one_gpu(tmp_path, world):
             assert r["da"] < ctol and r["db"] < ctol and r["dth"] < 1e-10 and r["dV"] < 1e-10 and r["dY"] < 1e-12, (name, r)
             assert r["comm_launches"] > 0 and r["sweeps"] == r["n"] and r["orth"] < 1e-12, (name, r)
         # collectives per run: default (fused norm) = (n + 1) exchanges + (n + 1) alpha all-reduces + n coefficient
-        # all-reduces; one-reduce = (n + 1) exchanges + n combined all-reduces + the last alpha
+        # all-reduces; one-reduce = (n + 1) exchanges + n combined all-reduces + the last alpha (with the last vector's u.u)
         assert per_rank["lap2d"]["comm_launches"] == 3 * 40 + 2 and per_rank["lap2d_onereduce"]["comm_launches"] == 2 * 40 + 2, per_rank
 
 
@@ -256,7 +256,7 @@ def test_partial_one_reduce_loop_over_a_one_rank_rccl_communicator():
     assert h.last_engine() == "partial-one-reduce" and h.last_host_syncs() == 0 and h.last_sweep_misses() == 0
     assert 1 < s0 < n and h.last_sweeps() == s0
     assert np.array_equal(a0, a1) and np.array_equal(b0, b1) and np.array_equal(V0, h.get_basis())
-    assert h.timings()["comm"]["launches"] == 2 * n + 2  # (n + 1) all-gathers + n combined all-reduces + the last alpha
+    assert h.timings()["comm"]["launches"] == 2 * n + 2  # (n + 1) all-gathers + n combined all-reduces + the last alpha (with the last u.u)
     h.close()
     h0.close()
 

@@ -480,7 +480,8 @@ def test_three_term_bit_exact(hip, M, n, j):
 
 @pytest.mark.parametrize("M,n,j,nrows", [(1000, 6, 3, 4), (70000, 12, 11, 12), (5121, 7, 2, 7), (33, 4, 0, 1), (20000, 40, 39, 40)])
 def test_reorth_matches_numpy(hip, M, n, j, nrows):
-    """reference reorthogonalize(V, j): c = sum(V[j]*V, axis=1); V[j] = 2 V[j] - sum(c[:,None]*V, axis=0)."""
+    """reference reorthogonalize(V, j): c = sum(V[j]*V, axis=1); V[j] = 2 V[j] - sum(c[:,None]*V, axis=0).
+    (Every edge of the sweep's launch-time plan against longdouble: tests/test_gpu_reorth_step.py, tests/test_gpu_reorth_loops.py.)"""
     rng = np.random.default_rng(M + 7 * j)
     V = np.zeros((n, M))
     V[:nrows] = rng.standard_normal((nrows, M)) / np.sqrt(M)
@@ -505,6 +506,7 @@ def test_reorth_matches_numpy(hip, M, n, j, nrows):
 
 
 def test_scale_then_reorth(hip):
+    """(The scaling and the fused-norm modes at every edge of the plan: tests/test_gpu_reorth_step.py, tests/test_gpu_reorth_loops.py.)"""
     M, n, j = 30011, 8, 5
     rng = np.random.default_rng(11)
     V = np.zeros((n, M))

@@ -86,7 +86,7 @@ def test_sweep_log_of_the_other_loops(hip):
 @pytest.mark.parametrize("partial", [False, True])
 def test_one_collective_loops_against_their_restatement(hip, build, n, partial):
     """`oracle.execute_lanczos_one_reduce` restates what the one-collective loops compute (the two-column pass, the three-sum |r|^2, the
-    subtraction order, the look-ahead gate): the device loops (engines 6 and 8) must deliver its coefficients to 1e-11 of the scale on
+    coefficients taken relative to u.u, the subtraction order, the look-ahead gate): the device loops (engines 6 and 8) must deliver its coefficients to 1e-11 of the scale on
     these well-conditioned runs - and, for the partial loop, the same sweep schedule."""
     A = build()
     H = A.to_scipy()

@@ -167,7 +167,7 @@ def test_two_rank_gloo_partitioned_lanczos(tmp_path):
             for suffix in ("_onereduce", "_partial_onereduce"):
                 da, db, d1, gates, gates1, calls, n = per_rank[name + suffix]
                 assert da < 1e-11 and db < 1e-11 and d1 < 1e-11, (name + suffix, da, db, d1)
-                assert calls == n + 1  # ONE all-reduce per step + the last alpha
+                assert calls == n + 1  # ONE all-reduce per step + the last alpha (with the last vector's u.u)
                 assert gates == gates1 == res[0][name + suffix][3]  # the same decisions on every rank, and as on one rank
                 assert gates[0] == 1 and (sum(gates) == n if suffix == "_onereduce" else sum(gates) < n)
 
