@@ -716,6 +716,57 @@ int lz_lsmr_info(lz_handle h, int* out);
  * next lz_lsmr_begin).  The measurements of tools/lsmr_probe.py */
 int lz_lsmr_step_time(lz_handle h, int reps, double* ms_out);
 
+/* ---- non-symmetric linear solves (lanczos_amd.bicgstab; BiCGSTAB, van der Vorst 1992) -------------------------------------------
+ * A x = b for the REAL square matrix set, symmetric or not, SciPy's bicgstab scalar for scalar: no basis, no transpose product.  With
+ * k = 0, 1, ... SciPy's `iteration`, r~ = r_0 and rho = r~ . r, iteration k is
+ *     head tests, in this order: |r| < atol (code 0), |rho| < eps^2 (-10), from k = 1 on |omega| < eps^2 (-11)
+ *     p = (p - omega v) beta + r,  beta = (rho / rho_prev)(alpha / omega)        (k = 0: p = r)
+ *     v = A p,  rv = r~ . v (rv == 0: -11),  alpha = rho / rv
+ *     s = r - alpha v;  |s| < atol: x += alpha p, code 0 - the half-step exit, the residual kept is s
+ *     t = A s,  omega = (t . s) / (t . t),  x = (x + alpha p) + omega s,  r = s - omega t,  rho_prev = rho,  rho = r~ . r
+ * Six padded vectors of its own (x, r - which holds s between the two products -, r~, p, v, t): every other state on the handle is
+ * untouched; every setter of the square matrix drops the state.  The products are the handle's in whatever plan the matrix has; their
+ * x_own . y epilogue yields r~ . v and t . s (the column-blocked two-phase plan cannot take an x_own that is not x: there one more
+ * launch forms r~ . v and the t . t pass forms t . s).  Beside them an iteration is seven launches: four streaming passes (p: 32 B a
+ * row; s and the partials of |s|^2: 24; the partials of t . t: 8; both updates of x, r and the partials of |r|^2 and r~ . r: 56) and
+ * three one-block kernels (alpha; omega and the half-step test; rho, beta and the head tests of the NEXT iteration, so an iteration
+ * that ends with |r| < atol reports 0 at once).  No atomics: the same input gives the same bits.  One rank only: LZ_ERR_STATE with no
+ * real square matrix, on a handle with a communicator and with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE; every call behind
+ * lz_bicgstab_begin answers LZ_ERR_STATE before it and after a matrix setter. */
+/* allocate and zero all six vectors, r = b - A x0 by one product (x0 NULL: r = b, no product), r~ = r, the partials of rho = r~ . r
+ * and |r|^2.  The head tests of iteration 0 need atol: the first lz_bicgstab_run applies them.  b, x0: n doubles. */
+int lz_bicgstab_begin(lz_handle h, const double* b, const double* x0);
+/* first the head tests of a state fresh from lz_bicgstab_begin / lz_bicgstab_set_state, then up to iters iterations without a host
+ * synchronisation, then one synchronisation.  Every test runs on the device against atol_eff (the caller's max(atol, rtol |b|)); the
+ * first that is met sets the done flag and every later launch of this section returns at once (the products of the rest of the call
+ * still run; their output is not read).  A call on a state that is done enqueues nothing.  state_out (16 doubles, may be NULL):
+ * iterations that updated x in total (a half-step exit counts), done, code (0, -10, -11), exit kind (0 none yet, 1 half step,
+ * 2 full step: |r| < atol at a head test, 3 breakdown), 1 where a head test set the flag (0: inside an iteration), the recurrence's
+ * |r| (|s| behind a half-step exit), rho, rho_prev, alpha, omega, beta, the last |s|, rv, t . s, t . t, one spare. */
+int lz_bicgstab_run(lz_handle h, int iters, double atol_eff, double* state_out);
+/* out[2 i], out[2 i + 1] = |s|, |r| of iteration i, i < count (behind a half-step exit |r| repeats |s|).  count may pass the
+ * iterations done, up to those lz_bicgstab_run was asked for so far (the history holds 1024 at least): an iteration that did not run,
+ * or that lz_bicgstab_set_state skipped, reads zero. */
+int lz_bicgstab_history(lz_handle h, double* out, int count);
+/* a vector of the state as n host doubles: x, r (s behind a half-step exit), r~, p, v = A p, t = A s as the last iteration left
+ * them.  which | LZ_BICGSTAB_RAW: the padded device vector as it is (lz_padded_rows(n) doubles) - the tests' look at the padding. */
+enum { LZ_BICGSTAB_X = 0, LZ_BICGSTAB_R = 1, LZ_BICGSTAB_RTILDE = 2, LZ_BICGSTAB_P = 3, LZ_BICGSTAB_V = 4, LZ_BICGSTAB_T = 5, LZ_BICGSTAB_RAW = 8 };
+int lz_bicgstab_get(lz_handle h, int which, double* out);
+/* upload the state that iteration k >= 0 starts from (allocates and zeroes as lz_bicgstab_begin does): x, r, r~, p, v - n doubles
+ * each; p and v of the iteration before, not read when k = 0 - and scalars[3] = rho_prev, alpha, omega.  rho and |r| are formed on the
+ * device exactly as lz_bicgstab_begin forms them, and the first lz_bicgstab_run applies the head tests of iteration k to them.  The
+ * history of iterations 0 .. k - 1 reads zero.  Tests drive one iteration, and the breakdown exits, from chosen numbers with it. */
+int lz_bicgstab_set_state(lz_handle h, int k, const double* x, const double* r, const double* rtilde, const double* p, const double* v,
+                          const double* scalars);
+/* ms_out[0 .. 6) = the device times (hipEvents) of the product v = A p, of the product t = A s, of k_bicgstab_p, k_bicgstab_s,
+ * k_bicgstab_tt and k_bicgstab_r: each the mean of reps launches behind one warm-up launch.  Needs a state that has run at least one
+ * iteration and is not done; the state is spent afterwards (LZ_ERR_STATE until the next lz_bicgstab_begin).  The measurements of
+ * tools/bicgstab_probe.py */
+int lz_bicgstab_step_time(lz_handle h, int reps, double* ms_out);
+/* out[0] = launches per iteration of the plan for the matrix set, each product counted as one (9, or 10 where the product cannot form
+ * r~ . v); out[1] = 1 where the products' epilogue yields r~ . v and t . s; out[2] = 1 while a state is live */
+int lz_bicgstab_info(lz_handle h, int* out);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

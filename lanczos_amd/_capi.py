@@ -210,6 +210,13 @@ SIGNATURES = {
     "lz_minres_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
     "lz_minres_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_minres_step_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_bicgstab_begin": (C.c_int, [_P, _D, _D]),
+    "lz_bicgstab_run": (C.c_int, [_P, C.c_int, C.c_double, _D]),
+    "lz_bicgstab_history": (C.c_int, [_P, _D, C.c_int]),
+    "lz_bicgstab_get": (C.c_int, [_P, C.c_int, _D]),
+    "lz_bicgstab_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
+    "lz_bicgstab_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_bicgstab_step_time": (C.c_int, [_P, C.c_int, _D]),
     "lz_lsmr_begin": (C.c_int, [_P, C.c_int, _D, _D, C.c_double]),
     "lz_lsmr_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double, _D]),
     "lz_lsmr_get": (C.c_int, [_P, C.c_int, _D]),
@@ -1155,6 +1162,64 @@ class Handle:
         out = (C.c_int * 3)()
         self.check(self.lib.lz_minres_info(self._h, out))
         return {"launches_per_iteration": int(out[0]), "scale_on_read": bool(out[1]), "live": bool(out[2])}
+
+    # -- non-symmetric linear solves (lanczos_amd.bicgstab): six vectors of their own on the real square matrix set
+    BICGSTAB_VECTORS = {"x": 0, "r": 1, "rtilde": 2, "p": 3, "v": 4, "t": 5}
+    BICGSTAB_STATE = ("iterations", "done", "code", "exit", "head", "rnorm", "rho", "rho_prev", "alpha", "omega", "beta", "snorm", "rv",
+                      "ts", "tt")
+    BICGSTAB_EXITS = {0: None, 1: "half", 2: "full", 3: "breakdown"}
+
+    def bicgstab_begin(self, b, x0=None):
+        """``r = b - A x0`` (``x0`` None: ``r = b``), ``rtilde = r``; a fresh state whose head tests the first ``bicgstab_run`` applies"""
+        b = f64(b)
+        assert b.shape == (self.rows,)
+        if x0 is not None:
+            x0 = f64(x0)
+            assert x0.shape == (self.rows,)
+        self.check(self.lib.lz_bicgstab_begin(self._h, dptr(b), dptr(x0) if x0 is not None else None))
+
+    def bicgstab_run(self, iters, atol_eff):
+        """up to ``iters`` iterations with no host synchronisation between them -> a dict of ``BICGSTAB_STATE`` (the totals, how the
+        state ended - ``exit`` is None, ``"half"``, ``"full"`` or ``"breakdown"`` - and the last iteration's scalars)"""
+        out = np.zeros(16)
+        self.check(self.lib.lz_bicgstab_run(self._h, int(iters), float(atol_eff), dptr(out)))
+        st = dict(zip(self.BICGSTAB_STATE, (float(v) for v in out)))
+        st["iterations"], st["done"], st["code"], st["head"] = int(out[0]), bool(out[1]), int(out[2]), bool(out[4])
+        st["exit"] = self.BICGSTAB_EXITS[int(out[3])]
+        return st
+
+    def bicgstab_history(self, count):
+        """``(count, 2)``: ``|s|``, ``|r|`` of iterations ``0 .. count - 1``"""
+        out = np.zeros((int(count), 2))
+        self.check(self.lib.lz_bicgstab_history(self._h, dptr(out), int(count)))
+        return out
+
+    def bicgstab_get(self, which, raw=False):
+        """a vector of the state (``"x"``, ``"r"``, ``"rtilde"``, ``"p"``, ``"v"``, ``"t"``) as ``n`` doubles; ``raw``: the padded device vector"""
+        out = np.empty(self.padded_rows(self.rows) if raw else self.rows)
+        self.check(self.lib.lz_bicgstab_get(self._h, self.BICGSTAB_VECTORS[which] | (8 if raw else 0), dptr(out)))
+        return out
+
+    def bicgstab_set_state(self, k, x, r, rtilde, p, v, scalars):
+        """the state iteration ``k`` (from 0) starts from; ``scalars`` = (rho_prev, alpha, omega)"""
+        vecs = [f64(a) for a in (x, r, rtilde, p, v)]
+        assert all(a.shape == (self.rows,) for a in vecs)
+        sc = f64(scalars)
+        assert sc.shape == (3,)
+        self.check(self.lib.lz_bicgstab_set_state(self._h, int(k), *(dptr(a) for a in vecs), dptr(sc)))
+
+    def bicgstab_step_time(self, reps=20):
+        """device milliseconds of ``(A p, A s, k_bicgstab_p, k_bicgstab_s, k_bicgstab_tt, k_bicgstab_r)`` (means of ``reps`` launches);
+        spends the state"""
+        out = np.zeros(6)
+        self.check(self.lib.lz_bicgstab_step_time(self._h, int(reps), dptr(out)))
+        return tuple(float(v) for v in out)
+
+    def bicgstab_info(self):
+        """{"launches_per_iteration", "dots_in_product": the products' epilogue yields ``rtilde . v`` and ``t . s``, "live"}"""
+        out = (C.c_int * 3)()
+        self.check(self.lib.lz_bicgstab_info(self._h, out))
+        return {"launches_per_iteration": int(out[0]), "dots_in_product": bool(out[1]), "live": bool(out[2])}
 
     # -- least-squares solves (lanczos_amd.lsmr): seven vectors of their own on the rectangular (gk) matrix; A is that matrix (p x q) or,
     # with ``transposed``, its transpose

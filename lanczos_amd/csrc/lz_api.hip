@@ -523,6 +523,7 @@ int lz_destroy(lz_handle h) {
   expm_free(h);
   minres_free(h);
   lsmr_free(h);
+  bicgstab_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

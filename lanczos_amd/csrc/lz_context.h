@@ -170,6 +170,24 @@ struct LsmrState {
   int done = 0;
 };
 
+// BiCGSTAB (lz_bicgstab.hip; lanczos_amd.bicgstab): A x = b on the real square matrix set, symmetric or not.  No basis: six padded
+// vectors of ld doubles each behind vec, in this order - X, R (the residual; s = r - alpha v between the two products of an
+// iteration, in place), RT (the shadow residual r~), P, V (= A p), T (= A s) - and the small device state of lz_bicgstab.hip.
+struct BicgstabState {
+  double* vec = nullptr;   // 6 * ld doubles; [rows, ld) of each is zero
+  double* ds = nullptr;    // scalars (kBicgstabDoubles)
+  int* di = nullptr;       // done, iteration counter, code, exit kind ... (kBicgstabInts)
+  double* part = nullptr;  // the products' x_own . y partials, then four sets of the passes' own
+  size_t part_cap = 0;
+  double* hist = nullptr;  // |s|, |r| of every iteration
+  int hist_cap = 0;        // in iterations (two doubles each)
+  int64_t ld = 0;
+  bool live = false;       // lz_bicgstab_begin / lz_bicgstab_set_state ran on the matrix now set
+  bool fresh = false;      // the head tests of the coming iteration have not been applied yet (the next lz_bicgstab_run does, with its atol)
+  int steps = 0;           // iterations done (the device's counter, as of the last synchronisation)
+  int done = 0;
+};
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -313,6 +331,7 @@ struct lz_context {
   ExpmState ex;  // the propagator's basis (lz_expm_*): freed by expm_free
   MinresState mr;  // the linear solver's vectors (lz_minres_*): freed by minres_free, dropped by every matrix setter (z_drop_matrix)
   LsmrState ls;    // the least-squares solver's vectors (lz_lsmr_*): freed by lsmr_free, dropped by lz_gk_set_csr / lz_gk_set_dense
+  BicgstabState bc;  // the non-symmetric solver's vectors (lz_bicgstab_*): freed by bicgstab_free, dropped by every matrix setter (z_drop_matrix)
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -437,6 +456,9 @@ void minres_free(lz_handle h);
 
 // LSMR (lz_lsmr.hip): releases everything h->ls owns (lz_destroy)
 void lsmr_free(lz_handle h);
+
+// BiCGSTAB (lz_bicgstab.hip): releases everything h->bc owns (lz_destroy)
+void bicgstab_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.
