@@ -767,6 +767,71 @@ int lz_bicgstab_step_time(lz_handle h, int reps, double* ms_out);
  * r~ . v); out[1] = 1 where the products' epilogue yields r~ . v and t . s; out[2] = 1 while a state is live */
 int lz_bicgstab_info(lz_handle h, int* out);
 
+/* ---- restarted GMRES (lanczos_amd.gmres; Saad & Schultz 1986) -------------------------------------------------------------------
+ * A x = b for the REAL square matrix set, scipy.sparse.linalg.gmres' rules: with m the restart length, a cycle is
+ *     V[0] = r / |r|, S = |r| e_0;  for j = 0 .. m - 1: w = A V[j], w against V[0 .. j] (the Hessenberg column), h1 = |w|,
+ *       breakdown where h1 <= eps h0 (h0 = |A V[j]|), the stored rotations on the column, the new rotation (LAPACK lartg), S,
+ *       presid = |S[j + 1]|, the inner exit on presid <= ptol or on breakdown
+ *     y = the pseudo-solve of the cols x cols triangle, x += y . V[:cols], r = b - A x, rnorm = |r|
+ *     rnorm <= atol: converged;  behind a breakdown: the end;  else ptol_max_factor = max(eps, 0.25 f) where presid <= ptol, min(1, 1.5 f)
+ *       where not, ptol = presid min(f, atol / rnorm)
+ * The first test of a solve is |r| < atol and the first ptol is |b| min(1, atol / |b|).  The orthogonalisation is the basis layer's
+ * (lz_trl_extend's step: classical Gram-Schmidt with the DGKS-gated second pass, no host synchronisation), not SciPy's modified
+ * Gram-Schmidt: results agree to rounding, not bit for bit.  The product is the matrix's own, never the polynomial of
+ * lz_trl_set_filter / lz_trl_set_series.  A basis of m + 1 rows (at least 3) and the vectors x and b of its own: the thick-restart
+ * basis and every other state on the handle are untouched; every setter of the square matrix drops the state.  Everything around the
+ * step runs on the device - one one-block kernel per step, and at a cycle's end the solve, the update of x (which reads cols from
+ * device memory and never a row >= cols), the product, the residual pass (which writes the whole padding of w as zero) and the
+ * cycle's tests - so lz_gmres_run enqueues steps, cycle ends and restarts without a synchronisation.  Behind an inner exit the
+ * steps that are still enqueued change nothing: cols, S, the rotations and R are frozen and the rows they write (>= cols) are
+ * scratch.  No atomics: the same input gives the same bits.  One rank only: LZ_ERR_STATE with no real square matrix, on a handle
+ * with a communicator and with LZ_FLAG_REORTH_PARTIAL / LZ_FLAG_ONE_REDUCE; every call behind lz_gmres_begin answers LZ_ERR_STATE
+ * before it and after a matrix setter. */
+/* allocate and zero the basis (max(restart, 2) + 1 rows), x and b; |b| on the device; r = b - A x0 by one product (x0 NULL: r = b, no
+ * product) and the partials of |r|^2.  The first test needs atol: the first lz_gmres_run applies it.  1 <= restart <= min(128, n),
+ * else LZ_ERR_ARG.  b, x0: n doubles. */
+int lz_gmres_begin(lz_handle h, int restart, const double* b, const double* x0);
+/* first the first test of a state fresh from lz_gmres_begin, then - where the last synchronisation showed an inner exit inside a
+ * cycle - that cycle's end, then up to `steps` inner steps with the end of a cycle enqueued wherever the host can foresee it
+ * (cols == restart), then one synchronisation.  Every test runs on the device against atol_eff (the caller's max(atol, rtol |b|));
+ * behind the done flag every launch of this section returns at once (the products of the rest of the call still run; their output
+ * is not read).  A call on a state that is done enqueues nothing.  state_out (16 doubles, may be NULL): inner steps in total, done,
+ * converged, breakdown, the inner-exit flag, cols, cycles ended, presid, ptol, ptol_max_factor, rnorm (the true |b - A x| of the last
+ * cycle end), |b|, the column the host's loop makes next, three spares. */
+int lz_gmres_run(lz_handle h, int steps, double atol_eff, double* state_out);
+/* the first test where it is due, then the end of the cycle under way whatever its length (cols >= 1; nothing where cols == 0), then
+ * one synchronisation: SciPy's legacy exit in the middle of a cycle, and the tests' way to one solve-and-update.  state_out as above. */
+int lz_gmres_end_cycle(lz_handle h, double atol_eff, double* state_out);
+/* presid_out[i] = presid of inner step i, i < count; cycles_out[3 c .. 3 c + 3) = rnorm, cols and the ptol cycle c ran under,
+ * c < ncycles.  The counts may pass what was done, up to what lz_gmres_run was asked for so far (both histories hold 1024 at least):
+ * an entry that was not made reads zero.  Either pointer may be NULL where its count is 0. */
+int lz_gmres_history(lz_handle h, double* presid_out, int count, double* cycles_out, int ncycles);
+/* LZ_GMRES_X, _W (the work vector: the residual b - A x behind a cycle end), _B: n host doubles, or with LZ_GMRES_RAW the padded
+ * device vector as it is (lz_padded_rows(n) doubles) - the tests' look at the padding.  LZ_GMRES_Y: restart doubles, the last solve's
+ * y (zero from cols on).  LZ_GMRES_ROWS: the restart + 1 basis rows with their padding, lz_padded_rows(n) doubles apart.
+ * LZ_GMRES_SMALL: restart^2 + 5 restart + 14 doubles - R (column j at j restart, rows 0 .. j), the rotations' c, their s,
+ * S (restart + 1), then cols, ptol, ptol_max_factor, presid, rnorm, |b|, the inner-exit flag, breakdown, done, converged, inner steps,
+ * cycles (lz_gmres_set_state reads up to here: restart^2 + 3 restart + 13), then what the last step handed to k_gmres_column: its
+ * coefficients (restart slots, j + 1 used), h1, and the self slots of pass 1's dots (restart; the step that made column j left
+ * h0^2 at index j). */
+enum { LZ_GMRES_X = 0, LZ_GMRES_W = 1, LZ_GMRES_B = 2, LZ_GMRES_Y = 3, LZ_GMRES_ROWS = 4, LZ_GMRES_SMALL = 5, LZ_GMRES_RAW = 8 };
+int lz_gmres_get(lz_handle h, int which, double* out);
+/* upload a whole state (allocates and zeroes as lz_gmres_begin does): x and b, n doubles each; w with its padding
+ * (lz_padded_rows(n) doubles); basis rows 0 .. nrows - 1 with their padding, lz_padded_rows(n) doubles apart (rows 0 ..
+ * min(cols, restart - 1) at least); small in LZ_GMRES_SMALL's layout.  No test is pending behind it: the next lz_gmres_run makes
+ * column cols, or begins with the cycle's end where the inner-exit flag is set.  Tests drive one step, one solve-and-update and one
+ * cycle end from chosen numbers with it. */
+int lz_gmres_set_state(lz_handle h, int restart, const double* x, const double* b, const double* w, const double* rows, int nrows,
+                       const double* small);
+/* ms_out[0 .. 5) = the device times (hipEvents) of the product A V[cols - 1], of the Gram-Schmidt step against cols rows (both
+ * passes), of k_gmres_update at cols rows, of launch_trl_cgs at cols rows (the yardstick: the same bytes) and of k_gmres_residual:
+ * each the mean of reps launches behind one warm-up launch.  Needs a state inside a cycle with cols >= 1 and no flag set; the state
+ * is spent afterwards (LZ_ERR_STATE until the next lz_gmres_begin).  The measurements of tools/gmres_probe.py */
+int lz_gmres_step_time(lz_handle h, int reps, double* ms_out);
+/* out[0] = launches per inner step, the product counted as one (11); out[1] = launches per cycle end (6); out[2] = 1 while a state
+ * is live; out[3] = its restart length */
+int lz_gmres_info(lz_handle h, int* out);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (lanczos_amd.svds; Baglama & Reichel 2005) ------------------------
  * Every function of this section replaces a part of scipy.sparse.linalg.svds on the host: singular triplets of a rectangular or
  * non-symmetric sparse matrix that lives on the device.  The host runs the outer loop (SVD of the m x m projected matrix B, restart

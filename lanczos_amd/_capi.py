@@ -217,6 +217,14 @@ SIGNATURES = {
     "lz_bicgstab_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
     "lz_bicgstab_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_bicgstab_step_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_gmres_begin": (C.c_int, [_P, C.c_int, _D, _D]),
+    "lz_gmres_run": (C.c_int, [_P, C.c_int, C.c_double, _D]),
+    "lz_gmres_end_cycle": (C.c_int, [_P, C.c_double, _D]),
+    "lz_gmres_history": (C.c_int, [_P, _D, C.c_int, _D, C.c_int]),
+    "lz_gmres_get": (C.c_int, [_P, C.c_int, _D]),
+    "lz_gmres_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, C.c_int, _D]),
+    "lz_gmres_step_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_gmres_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_lsmr_begin": (C.c_int, [_P, C.c_int, _D, _D, C.c_double]),
     "lz_lsmr_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double, _D]),
     "lz_lsmr_get": (C.c_int, [_P, C.c_int, _D]),
@@ -1220,6 +1228,103 @@ class Handle:
         out = (C.c_int * 3)()
         self.check(self.lib.lz_bicgstab_info(self._h, out))
         return {"launches_per_iteration": int(out[0]), "dots_in_product": bool(out[1]), "live": bool(out[2])}
+
+    # -- restarted GMRES (lanczos_amd.gmres): a basis of restart + 1 rows, x and b of their own on the real square matrix set
+    GMRES_WHICH = {"x": 0, "w": 1, "b": 2, "y": 3, "rows": 4, "small": 5}
+    GMRES_STATE = ("iterations", "done", "converged", "breakdown", "inner", "cols", "cycles", "presid", "ptol", "factor", "rnorm", "bnorm",
+                   "hcol")
+    GMRES_SCALARS = ("cols", "ptol", "factor", "presid", "rnorm", "bnorm", "inner", "breakdown", "done", "converged", "iters", "cycles")
+
+    def gmres_begin(self, restart, b, x0=None):
+        """``r = b - A x0`` (``x0`` None: ``r = b``) and ``|b|``; a fresh state whose first test the first ``gmres_run`` applies"""
+        b = f64(b)
+        assert b.shape == (self.rows,)
+        if x0 is not None:
+            x0 = f64(x0)
+            assert x0.shape == (self.rows,)
+        self.check(self.lib.lz_gmres_begin(self._h, int(restart), dptr(b), dptr(x0) if x0 is not None else None))
+        self._gmres_m = int(restart)
+
+    def _gmres_st(self, out):
+        st = dict(zip(self.GMRES_STATE, (float(v) for v in out)))
+        for k in ("iterations", "cols", "cycles", "hcol"):
+            st[k] = int(st[k])
+        for k in ("done", "converged", "breakdown", "inner"):
+            st[k] = bool(st[k])
+        return st
+
+    def gmres_run(self, steps, atol_eff):
+        """up to ``steps`` inner steps, cycle ends and restarts included, with no host synchronisation between them -> a dict of
+        ``GMRES_STATE``"""
+        out = np.zeros(16)
+        self.check(self.lib.lz_gmres_run(self._h, int(steps), float(atol_eff), dptr(out)))
+        return self._gmres_st(out)
+
+    def gmres_end_cycle(self, atol_eff):
+        """the end of the cycle under way whatever its length -> a dict of ``GMRES_STATE``"""
+        out = np.zeros(16)
+        self.check(self.lib.lz_gmres_end_cycle(self._h, float(atol_eff), dptr(out)))
+        return self._gmres_st(out)
+
+    def gmres_history(self, count, ncycles):
+        """``(presid of inner steps 0 .. count - 1, (ncycles, 3): rnorm, cols, ptol of every cycle)``"""
+        hist, cyc = np.zeros(int(count)), np.zeros((int(ncycles), 3))
+        self.check(self.lib.lz_gmres_history(self._h, dptr(hist) if count else None, int(count), dptr(cyc) if ncycles else None, int(ncycles)))
+        return hist, cyc
+
+    def gmres_get(self, which, raw=False):
+        """``"x"``, ``"w"``, ``"b"`` (``n`` doubles; ``raw``: the padded device vector), ``"y"`` (restart), ``"rows"`` (``(restart + 1,
+        padded n)``) or ``"small"``: a dict of ``R`` (row ``j`` is column ``j`` of the triangle), ``gc``, ``gs``, ``S``, ``GMRES_SCALARS`` and the
+        last step's inputs to k_gmres_column: ``proj``, ``h1``, ``h0sq`` (index ``j``: of the step that made column ``j``)"""
+        m, pad = self._gmres_m, self.padded_rows(self.rows)
+        w = self.GMRES_WHICH[which]
+        if w <= 2:
+            out = np.empty(pad if raw else self.rows)
+        elif which == "y":
+            out = np.empty(m)
+        elif which == "rows":
+            out = np.empty((m + 1, pad))
+        else:
+            out = np.empty(m * m + 5 * m + 14)
+        self.check(self.lib.lz_gmres_get(self._h, w | (8 if raw and w <= 2 else 0), dptr(out)))
+        if which != "small":
+            return out
+        small = {"R": out[: m * m].reshape(m, m).copy(), "gc": out[m * m: m * m + m].copy(), "gs": out[m * m + m: m * m + 2 * m].copy(),
+                 "S": out[m * m + 2 * m: m * m + 3 * m + 1].copy()}
+        small.update(zip(self.GMRES_SCALARS, (float(v) for v in out[m * m + 3 * m + 1:])))
+        tail = out[m * m + 3 * m + 13:]
+        small.update({"proj": tail[:m].copy(), "h1": float(tail[m]), "h0sq": tail[m + 1:].copy()})
+        return small
+
+    def gmres_set_state(self, restart, x, b, w, rows, small):
+        """upload a whole state: ``x``, ``b`` (``n``), ``w`` (``n`` or padded), basis rows (``(nrows, n)`` or padded), ``small`` as
+        ``gmres_get("small")`` returns it"""
+        m, pad = int(restart), self.padded_rows(self.rows)
+        x, b = f64(x), f64(b)
+        assert x.shape == (self.rows,) and b.shape == (self.rows,)
+        wp = np.zeros(pad)
+        wp[: len(w)] = w
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+        rp = np.zeros((rows.shape[0], pad))
+        rp[:, : rows.shape[1]] = rows
+        packed = np.concatenate([np.asarray(small["R"], dtype=np.float64).reshape(m * m), f64(small["gc"]), f64(small["gs"]), f64(small["S"]),
+                                 np.array([float(small[k]) for k in self.GMRES_SCALARS])])
+        assert packed.shape == (m * m + 3 * m + 13,)
+        self.check(self.lib.lz_gmres_set_state(self._h, m, dptr(x), dptr(b), dptr(wp), dptr(rp), int(rp.shape[0]), dptr(packed)))
+        self._gmres_m = m
+
+    def gmres_step_time(self, reps=20):
+        """device milliseconds of ``(A V[cols - 1], the Gram-Schmidt step at cols rows, k_gmres_update, launch_trl_cgs at cols rows,
+        k_gmres_residual)`` (means of ``reps`` launches); spends the state"""
+        out = np.zeros(5)
+        self.check(self.lib.lz_gmres_step_time(self._h, int(reps), dptr(out)))
+        return tuple(float(v) for v in out)
+
+    def gmres_info(self):
+        """{"launches_per_step", "launches_per_cycle_end", "live", "restart"}"""
+        out = (C.c_int * 4)()
+        self.check(self.lib.lz_gmres_info(self._h, out))
+        return {"launches_per_step": int(out[0]), "launches_per_cycle_end": int(out[1]), "live": bool(out[2]), "restart": int(out[3])}
 
     # -- least-squares solves (lanczos_amd.lsmr): seven vectors of their own on the rectangular (gk) matrix; A is that matrix (p x q) or,
     # with ``transposed``, its transpose

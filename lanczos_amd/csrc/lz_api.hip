@@ -524,6 +524,7 @@ int lz_destroy(lz_handle h) {
   minres_free(h);
   lsmr_free(h);
   bicgstab_free(h);
+  gmres_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

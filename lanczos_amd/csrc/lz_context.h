@@ -188,6 +188,27 @@ struct BicgstabState {
   int done = 0;
 };
 
+// Restarted GMRES (lz_gmres.hip; lanczos_amd.gmres): A x = b on the real square matrix set.  A basis of its own, max(m, 2) + 1 rows
+// (m: the restart length), beside h->trl, h->z.B and h->ex.B, so eigsh's and eigs' thick-restart basis survives a solve on the same
+// handle; B.w is the work vector of the steps and the residual b - A x of the cycle ends.  x and b: two padded vectors behind vec.
+struct GmresState {
+  OrthBasis B;
+  OrthWork wk;              // small arrays: see gmres_small_layout in lz_gmres.hip; part also takes the products' partials
+  int m = 0;                // the restart length the basis was allocated for
+  double* vec = nullptr;    // 2 * B.ld doubles: x, b; [rows, ld) of each is zero
+  int* di = nullptr;        // done, inner exit, breakdown, converged, cols, steps, cycles (kGmresInts)
+  double* rpart = nullptr;  // the partials of |b - A x|^2
+  double* hist = nullptr;   // presid of every inner step
+  int hist_cap = 0;
+  double* chist = nullptr;  // rnorm, cols, ptol of every cycle
+  int chist_cap = 0;        // in cycles (three doubles each)
+  bool live = false;        // lz_gmres_begin / lz_gmres_set_state ran on the matrix now set
+  bool fresh = false;       // the first test has not been applied yet (the next lz_gmres_run does, with its atol)
+  bool pending = false;     // the last synchronisation showed an inner exit inside a cycle: the next call begins with that cycle's end
+  int hcol = 0;             // the column the next step of the host's loop makes (the device's cols wherever no flag is set)
+  int iters = 0, cycles = 0, done = 0;  // the device's counters, as of the last synchronisation
+};
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -332,6 +353,7 @@ struct lz_context {
   MinresState mr;  // the linear solver's vectors (lz_minres_*): freed by minres_free, dropped by every matrix setter (z_drop_matrix)
   LsmrState ls;    // the least-squares solver's vectors (lz_lsmr_*): freed by lsmr_free, dropped by lz_gk_set_csr / lz_gk_set_dense
   BicgstabState bc;  // the non-symmetric solver's vectors (lz_bicgstab_*): freed by bicgstab_free, dropped by every matrix setter (z_drop_matrix)
+  GmresState gm;     // the restarted solver's basis and vectors (lz_gmres_*): freed by gmres_free, dropped by every matrix setter (z_drop_matrix)
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -459,6 +481,9 @@ void lsmr_free(lz_handle h);
 
 // BiCGSTAB (lz_bicgstab.hip): releases everything h->bc owns (lz_destroy)
 void bicgstab_free(lz_handle h);
+
+// GMRES (lz_gmres.hip): releases everything h->gm owns (lz_destroy)
+void gmres_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.

@@ -119,6 +119,7 @@ int z_drop_matrix(lz_handle h) {
   z.kind = 0;
   h->mr.live = false;  // every matrix setter comes through here: a new matrix drops the MINRES state (lz_minres.hip)
   h->bc.live = false;  // ... and the BiCGSTAB state (lz_bicgstab.hip)
+  h->gm.live = false;  // ... and the GMRES state (lz_gmres.hip)
   LZ_TRY(dev_free(h, z.rowptr));
   LZ_TRY(dev_free(h, z.colidx));
   LZ_TRY(dev_free(h, z.vals));
