@@ -142,7 +142,12 @@ int lz_set_options(lz_handle h, int flags);
  *       the pair walk on long vectors (A/B).  Where the pair form applies, n >= 6 and n <= 512, the automatic choice takes the
  *       GROUP form instead - one walk over the basis per four steps, lz_last_one_sweep_quads; 6, 7, 8 and 9 never do; 10 the
  *       one-sweep loop at any size with groups; 11 the same with 8 instead of 4 positions per lane in the group walk on long
- *       vectors (A/B))
+ *       vectors (A/B).  The chain of three steps before a group's walk works in the units of z - the chain vectors stay unscaled
+ *       in their basis rows, the plain coded product runs on them, one launch adds ||z||^2 and z . A z, and x = z / b is formed by
+ *       division wherever it is read (16 launches per group) - and the second-stage sums, post and the chat prediction behind the
+ *       walk run on a side stream beside the closing product and the next chain (same arithmetic, same bits); 12 the group form at any
+ *       size with the scaled chain through the scale-on-read SpMV (19 launches per group, everything on the main stream; A/B), 13 the
+ *       group form at any size with the unscaled chain and no side stream (A/B))
  *   16  rows per chunk of the CHUNKED Ritz mode (0 auto: chunked only when Y does not fit beside the basis; > 0 forces it: tests)
  *   11  two-sided Gram-Schmidt links (0 / 1: streaming kernel + fold kernel per link)
  *   17  fixed-K (stencil) SpMV layout: 0 auto (CSR-order kernel with products staged through LDS; the ELL-ordered second copy -

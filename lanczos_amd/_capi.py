@@ -49,7 +49,8 @@ TUNE_NO_SKEW = 12           # 1 = no row-stride skew
 TUNE_POISON_BASIS = 13      # 1 = NaN-poison a fresh basis allocation (test knob)
 TUNE_SPMV_PLAN = 14         # irregular SpMV plan (0 auto, 1 never two-phase, 2 always)
 TUNE_LOOP = 15              # loop structure (0 auto, 1 six launches per step always, 6 the one-sweep loop at any size (never pairs), 7 the same, never fused,
-                            # 8 the one-sweep loop at any size with pair walks, 9 the same with 16 positions per lane in the pair walk)
+                            # 8 the one-sweep loop at any size with pair walks, 9 the same with 16 positions per lane in the pair walk,
+                            # 10 / 11 with group walks, 4 / 8 positions per lane; 12 groups with the scaled chain, 13 groups without the side stream: A/B)
 TUNE_RITZ_CHUNK_ROWS = 16   # rows per chunk of the chunked Ritz mode (> 0 forces it)
 TUNE_FIXED_LAYOUT = 17      # fixed-K SpMV layout (0 auto: row-class coded ELL where the rows fall into classes, else CSR order and ELL only in the partial loop;
                             # 1 never ELL; 2 / 3 uncoded ELL always, one / two rows per lane; 4 offsets-only coding)

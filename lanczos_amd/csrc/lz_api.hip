@@ -135,7 +135,7 @@ bool roctx_on() {
 }  // namespace
 
 // ---- profiling events ---------------------------------------------------
-Scope::Scope(lz_handle h_, int cls_, double bytes, double flops) : h(h_), cls(cls_) {
+Scope::Scope(lz_handle h_, int cls_, double bytes, double flops, hipStream_t stream) : h(h_), cls(cls_), st(stream ? stream : h_->stream) {
   if (roctx_on()) {
     g_roctx.push(kClassNames[cls]);
     marked = true;
@@ -157,13 +157,13 @@ Scope::Scope(lz_handle h_, int cls_, double bytes, double flops) : h(h_), cls(cl
         return;
       }
     }
-    hipEventRecord(a, h->stream);
+    hipEventRecord(a, st);
   }
 }
 Scope::~Scope() {
   if (marked) g_roctx.pop();
   if (on) {
-    hipEventRecord(b, h->stream);
+    hipEventRecord(b, st);
     h->events.push_back({cls, a, b});
   }
 }
@@ -473,6 +473,7 @@ int lz_destroy(lz_handle h) {
   if (!h) return LZ_OK;
   hipSetDevice(h->dev);
   hipStreamSynchronize(h->stream);
+  if (h->os_stream) hipStreamSynchronize(h->os_stream);  // (before any buffer it may still read is freed)
   if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
   big_free(h->csr.rowptr);
   big_free(h->csr.colidx);
@@ -510,6 +511,14 @@ int lz_destroy(lz_handle h) {
   big_free(h->d_xfull);
   big_free(h->d_om);
   big_free(h->d_os);
+  big_free(h->d_ospart);
+  if (h->os_stream) {
+    hipStreamSynchronize(h->os_stream);
+    hipStreamDestroy(h->os_stream);
+    hipEventDestroy(h->e_os_walk);
+    hipEventDestroy(h->e_os_alpha);
+    hipEventDestroy(h->e_os_ready);
+  }
   big_free(h->d_osi);
   big_free(h->d_tap);
   big_free(h->d_omi);
@@ -565,7 +574,7 @@ int lz_set_options(lz_handle h, int flags) {
 
 int lz_set_tuning(lz_handle h, int index, int value) {
   if (!h) return LZ_ERR_ARG;
-  if (index < 0 || index >= 24) return fail(h, LZ_ERR_ARG, "lz_set_tuning: knob index out of range");
+  if (index < 0 || index >= kTuneKnobs) return fail(h, LZ_ERR_ARG, "lz_set_tuning: knob index out of range");
   // The timing-only ablation arms (kernel variants that computed wrong results on purpose, for one-off measurements: knob 1 >= 20,
   // knob 3, knob 9 >= 10) were deleted in round 5; their results are in profiles/r01 .. r04.
   if ((index == 1 && value >= 20) || (index == 3 && value != 0) || (index == 9 && value >= 10))
@@ -574,7 +583,7 @@ int lz_set_tuning(lz_handle h, int index, int value) {
   // Retired A/B arms (built, measured slower, kept bit-identity-tested in the kernel-bench build): the one-kernel /
   // one-launch-per-step engines (15 = 2, 3, 5), the persistent and LDS-staged Ritz GEMMs (9 >= 2), the ticket / deferred-fold
   // two-sided links (11 >= 2), the row-block-group interleaving of the two-phase SpMV (22 >= 2: round 5, 8-110 % slower)
-  if ((index == 15 && value >= 2 && (value < 6 || value > 11)) || (index == 9 && value >= 2) || (index == 11 && value >= 2) || (index == 22 && value >= 2))
+  if ((index == 15 && value >= 2 && (value < 6 || value > 13)) || (index == 9 && value >= 2) || (index == 11 && value >= 2) || (index == 22 && value >= 2))
     return fail(h, LZ_ERR_ARG, "lz_set_tuning: this A/B arm was retired from the product library (build with KBENCH=1)");
 #endif
   if (value < 0) return fail(h, LZ_ERR_ARG, "lz_set_tuning: negative value");

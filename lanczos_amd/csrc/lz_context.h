@@ -209,13 +209,15 @@ struct GmresState {
   int iters = 0, cycles = 0, done = 0;  // the device's counters, as of the last synchronisation
 };
 
+constexpr int kTuneKnobs = 24;  // lz_set_tuning's indices 0 .. 23
+
 struct lz_context {
   int dev = 0;
   hipStream_t stream = nullptr;
   std::string err;
   std::string name;
   int flags = 0;
-  int tune[24] = {0};  // A/B knobs, see lz_set_tuning
+  int tune[kTuneKnobs] = {0};  // A/B knobs, see lz_set_tuning
 
   // partition
   int64_t Mg = 0, row0 = 0, rows = 0, ncols_ext = 0;
@@ -311,10 +313,19 @@ struct lz_context {
   int r_state = 0;      // what d_r holds after the last run: 0 nothing usable, 1 the residual entering step n, 2 y = A v_{n-1} (three-term pending)
   Xfer* xfer = nullptr;        // staging ring of the large device -> host copies (lz_xfer.hip), created at the first one
   double* h_pinned = nullptr;  // 8 pinned doubles for the per-step scalar read-back of the host-decided partial-reorth loop (tune[18] == 1)
-  double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n), the group form's predictions (4 (n + 4)); os_n = its n
+  double* d_os = nullptr;      // one-sweep loop: G (n x n), H (n x n), c_hat (n + 1), correction g (2n), max |e| per step (n), the group form's predictions (4 (n + 4)), the group chain's ||z||^2 partials (2048) and b_3 (8); os_n = its n
   int* d_osi = nullptr;        //   ... [0] gate of the correcting sweep, [1] gate trips of the run, [3] / [4] a pair's / a group's leftover exceeded tau
   int os_n = 0;
   int os_step_n = 0;           //   ... the n of the state lz_os_state_set left in d_os (0: none; a run lays d_os out for its own n)
+  // The group form's side stream (one_sweep_quad_iter; knob 15 = 13 keeps it on the main stream): behind a group walk the second-stage sums, post and the chat prediction
+  // run on os_stream beside the closing product and the next chain.  os_side_pending: such work is in flight and e_os_ready not yet
+  // waited for - whatever reads G, H, chat, the flags, elog or d_c next joins first (one_sweep_join).  d_ospart: the alpha partials of
+  // the chain's and the closing products (d_part still holds the walk's while the side stream adds them up).
+  hipStream_t os_stream = nullptr;
+  hipEvent_t e_os_walk = nullptr, e_os_alpha = nullptr, e_os_ready = nullptr;
+  bool os_side_pending = false;
+  double* d_ospart = nullptr;
+  size_t ospart_cap = 0;
   // lz_os_step's tap: check_launch copies the first tap_count doubles of d_part to d_tap behind the launch named tap_what (the walk of
   // the step: later launches of the same step reuse the head of d_part).  nullptr outside lz_os_step.
   const char* tap_what = nullptr;
@@ -426,7 +437,8 @@ struct Scope {
   hipEvent_t a = nullptr, b = nullptr;
   bool on;
   bool marked = false;
-  Scope(lz_handle h_, int cls_, double bytes, double flops);
+  hipStream_t st;  // the stream the bracket is recorded on
+  Scope(lz_handle h_, int cls_, double bytes, double flops, hipStream_t stream = nullptr);  // nullptr: h->stream
   ~Scope();
 };
 int drain_events(lz_handle h);

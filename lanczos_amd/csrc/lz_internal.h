@@ -293,7 +293,8 @@ int launch_os_sweep(int mode, double* V, int64_t ldv, int64_t len, int j, const 
 void launch_os_post(const double* d, const double* chat, double* G, double* H, int n, int j, double* nrm2, double tau, double* g, int* ist,
                     double* elog, bool fused, hipStream_t s);
 // one block: sum_out[0] = sum(part[0 .. np)) in k_final_sum's grouping - ||w_{j+1}||^2 behind the three-term kernel, or (fused) alpha_j
-// behind the SpMV - and then, when `predict`, chat[0..j] of step j + 1 (fused: not divided by sqrt(nrm2)) and H[:, j]'s alpha / beta entries
+// behind the SpMV - and then, when `predict`, chat[0..j] of step j + 1 (fused: not divided by sqrt(nrm2)) and H[:, j]'s alpha / beta entries.
+// fused with part == nullptr: the predictions alone, alpha_j read from its slot (nothing is summed, sum_out is not written)
 void launch_os_sum_predict(const double* part, int np, double* sum_out, const double* G, double* H, int n, int j, const double* alpha_j,
                            const double* beta_j, double* chat, bool fused, bool predict, hipStream_t s);
 // Pair form (run_loop_one_sweep_pair): one walk per two steps, j >= 2 the first step of the pair; the arithmetic is one_sweep_pair_lanczos's
@@ -327,8 +328,10 @@ int os_quad_ldp(int j);
 int os_quad_sweep_blocks(int64_t len, bool wide8);
 void launch_os_quad_predict(const double* part, int np, double* nrm2, const double* chat, const double* G, const double* H, int n, int j,
                             const double* alpha, const double* beta, double* gout, int ldg, hipStream_t s);
-int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* nrm2, double* part,
-                         bool wide8, hipStream_t s);
+// bz == nullptr: rows j .. j+2 hold x_0 .. x_2 and z holds z_3; else (the chain in the units of z) rows j .. j+3 hold the unscaled
+// z_0 .. z_3, bz[t] = b_t (t < 3) and z is not read
+int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* bz, const double* nrm2,
+                         double* part, bool wide8, hipStream_t s);
 // returns the error of the per-kernel LDS-limit raise (hipFuncSetAttribute), if that was needed and failed
 hipError_t launch_os_quad_post(const double* d, int ldp, const double* g, int ldg, double* G, double* H, int n, int j, const double* nrm2,
                                const double* alpha, double* beta, double tau, int* ist, double* elog, hipStream_t s);
@@ -356,6 +359,14 @@ void launch_onereduce_finish(const double* buf, int ldp, double* alpha_last, dou
 // r = (r - alpha v_j) - beta v_jm1 ; part[b] = partial ||r||^2 ; returns number of partials
 int launch_three_term(double* r, const double* vj, const double* vjm1, const double* alpha, const double* beta,
                       int64_t len, double* part, hipStream_t s);
+// the group chain in the units of z: out = (y - alpha zt) - bt xm (mode 0, k_three_term's expression, out of place), or
+// out = (y / bt - alpha (zt / bt)) - bt xm' with xm' = xm (mode 1) or xm / bm (mode 2); part[b] = partial ||out||^2; returns the partials
+int launch_three_term_z(int mode, double* out, const double* y, const double* zt, const double* xm, const double* alpha, const double* bt,
+                        const double* bm, int64_t len, double* part, hipStream_t s);
+// one block: beta_slot[0] = sqrt(sum(zpart[0 .. nz))), alpha_slot[0] = sum(apart[0 .. na)) / sum(zpart[0 .. nz)) (k_final_sum's grouping)
+void launch_final_sum_chain(const double* zpart, int nz, const double* apart, int na, double* beta_slot, double* alpha_slot, hipStream_t s);
+// one block: out[0] = sum(part[0 .. np)) (k_final_sum), root_out[0] = sqrt(nrm2[0])
+void launch_final_sum_root(const double* part, int np, double* out, const double* nrm2, double* root_out, hipStream_t s);
 // gather x[idx[k]] -> buf[k]
 void launch_gather(const double* x, const int32_t* idx, int64_t n, double* buf, hipStream_t s);
 

@@ -480,8 +480,19 @@ int run_small_engine(lz_handle h, int n, const double* v0_local, bool steps, boo
 // Where the matrix has a scale-on-read SpMV the fused form below runs instead (lz_set_tuning(h, 15, 7): this one always).
 struct OneSweepState {
   double *G, *H, *chat, *g, *elog, *gq;  // gq: the group form's predictions, 4 runs of n + 4
+  double* zp;                            // the ||z||^2 partials of the group chain's three-term passes (kChainParts)
+  double* b3;                            // b_3 of the group before, for the next group's opening pass while post is on the side stream
   int nb;
 };
+constexpr size_t kChainParts = 2048;  // (launch_three_term_z's grid limit)
+// The main stream waits for what the side stream of the last group left to do (second-stage sums, post, the chat prediction): called
+// immediately before the first launch, copy or memset on the main stream that touches G, H, chat, the flags, elog or d_c.
+static int one_sweep_join(lz_handle h) {
+  if (!h->os_side_pending) return LZ_OK;
+  h->os_side_pending = false;
+  LZ_HIP(h, hipStreamWaitEvent(h->stream, h->e_os_ready, 0));
+  return LZ_OK;
+}
 // where the state of an n-step run lies in d_os
 static void one_sweep_view(lz_handle h, int n, OneSweepState& st) {
   st.nb = os_sweep_blocks(h->rows_pad);
@@ -491,9 +502,23 @@ static void one_sweep_view(lz_handle h, int n, OneSweepState& st) {
   st.g = st.chat + n + 1;
   st.elog = st.g + 2 * n + 2;
   st.gq = st.elog + n + 1;
+  st.zp = st.gq + (size_t)4 * (n + 4);
+  st.b3 = st.zp + kChainParts;
 }
 static int one_sweep_setup(lz_handle h, int n, OneSweepState& st, int pair_blocks = 0) {
-  const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8 + (size_t)4 * (n + 4);
+  const size_t os_doubles = (size_t)2 * n * n + (size_t)5 * n + 8 + (size_t)4 * (n + 4) + kChainParts + 8;
+  LZ_TRY(one_sweep_join(h));  // (only behind a run that ended in an error: nothing of it may still be writing the state)
+  if (!h->os_stream) {
+    LZ_HIP(h, hipStreamCreateWithFlags(&h->os_stream, hipStreamNonBlocking));
+    LZ_HIP(h, hipEventCreateWithFlags(&h->e_os_walk, hipEventDisableTiming));
+    LZ_HIP(h, hipEventCreateWithFlags(&h->e_os_alpha, hipEventDisableTiming));
+    LZ_HIP(h, hipEventCreateWithFlags(&h->e_os_ready, hipEventDisableTiming));
+  }
+  const size_t ospart = (size_t)(h->rows / kTPB) + 64;  // (the ELL products leave one alpha partial per block of kTPB rows or more)
+  if (h->ospart_cap < ospart) {
+    LZ_TRY(dev_alloc(h, h->d_ospart, ospart));
+    h->ospart_cap = ospart;
+  }
   if (h->os_n < n) {
     LZ_TRY(dev_alloc(h, h->d_os, os_doubles));
     LZ_TRY(dev_alloc(h, h->d_osi, 8));
@@ -579,6 +604,7 @@ bool one_sweep_fused_applies(lz_handle h, int n) {
 // one step of the fused form: sweep / post / gated correction, SpMV, alpha sum + the next step's predictions
 static int one_sweep_fused_iter(lz_handle h, int n, int j, const OneSweepState& st) {
   double* vj = basis_row(h, j);
+  LZ_TRY(one_sweep_join(h));  // (behind a group: its state)
   LZ_TRY(one_sweep_step(h, n, j, st, j > 0));
   int npa = 0;
   if (j == 0) {  // step 0 is the unfused form's: V[0] is in place, a plain SpMV
@@ -598,6 +624,7 @@ static int one_sweep_fused_iter(lz_handle h, int n, int j, const OneSweepState& 
 // after the last step of the fused and the pair form: r = (A v_{n-1} - alpha_{n-1} v_{n-1}) - beta_{n-2} v_{n-2}, ||r||^2 - the
 // residual entering step n
 static int one_sweep_fused_tail(lz_handle h, int n) {
+  LZ_TRY(one_sweep_join(h));  // (a run that ends on a group: beta_{n-1} is post's, and the run's end must be behind everything)
   LZ_TRY(step_three_term(h, n - 1, n - 2, h->d_alpha + (n - 1), beta_slot(h, n, n - 1), true));
   h->r_state = 1;
   return LZ_OK;
@@ -633,6 +660,7 @@ static int one_sweep_pair_iter(lz_handle h, int n, int j, const OneSweepState& s
   double* pp = st.g + n + 1;
   const int* scale = h->d_osi + 2;  // (stays 0: the SpMVs always scale on read)
   h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1);
+  LZ_TRY(one_sweep_join(h));  // (behind a group: its state)
   // w_j = (y - alpha_{j-1} v_{j-1}) - beta_{j-1} v_{j-2} -> d_r, ||w_j||^2 -> d_nrm2
   LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
   int npa = 0;
@@ -690,11 +718,15 @@ int run_loop_one_sweep_pair(lz_handle h, int n) {
 //   chain    three plain Lanczos steps with no walk - x_0 = w_j / b_0 and, for t < 3, y_t = A x_t, a_t = x_t . y_t,
 //            z = (y_t - a_t x_t) - b_t x_{t-1}, b_{t+1} = ||z||, x_{t+1} = z / b_{t+1} - by the launches of a step that does not sweep: the
 //            scaling SpMV (which stores x_t into row j + t), the alpha sum, k_three_term, the ||.||^2 sum.  alpha_{j+t} = a_t, beta = b_t.
+//            That is knob 15 = 12; the default keeps the chain in the units of z (see one_sweep_quad_iter): the same steps on the unscaled
+//            z_t in rows j .. j+3, three launches less and 8 M bytes less per product.
 //   predict  the omega-recurrence over the extended set [V_0 .. V_{j-1}, x_0 .. x_3] with the full H: every dot of x_t against the rows
 //            before it, to O(eps^2), from G, H, chat and the chain's scalars (one block; it also sums the last ||z||^2)
 //   walk     rows 0 .. j-1 once, four running sums and four dots per position; its epilogue finishes v_j .. v_{j+3}
 //   post     the leftovers against the gate, G[:, j .. j+3], H[:, j-1 .. j+2] (one block)
 //   closing  the plain SpMV on the corrected V[j+3]; its alpha sum predicts the next chat as after any step
+// With the unscaled chain the second-stage sums, post and the chat prediction run on a side stream (knob 15 = 13: on the main stream):
+// nothing reads G, H, chat, the flags or elog before the next group's predict kernel, a chain of streaming kernels later (one_sweep_join).
 // z differs from the two-pass loop's w_{j+t} by a vector of span(V_0 .. V_{j+t-1}) plus O(eps^2), and projecting that span out of either
 // gives the same v_{j+t}: coefficients and basis equal the two-pass loop's to rounding.  8 j M + 64 M bytes of walk per group where two
 // pair walks move 16 j M + 80 M.  Steps 0 and 1 are the single fused form's; a tail of two steps is a pair, a tail of one or three runs
@@ -709,51 +741,119 @@ static int one_sweep_quad_iter(lz_handle h, int n, int j, const OneSweepState& s
   const double M = (double)h->rows;
   const int ldg = n + 4;
   h->prof_iter = iter_sampled(h, j) || iter_sampled(h, j + 1) || iter_sampled(h, j + 2) || iter_sampled(h, j + 3);
-  // the chain: w_j -> d_r; then x_t = src / b_t -> V[j + t], y_t -> the other residual buffer, z in place there
-  LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
-  double* src = h->d_r;
-  double* dst = h->d_r2;
+  const bool zchain = h->tune[15] != 12;  // (12: the chain of scaled vectors through the scaling SpMV, 19 launches per group - A/B)
+  // Behind the walk the second-stage sums, post and the chat prediction run on the side stream: nothing before the next group's predict
+  // kernel reads what they leave (knob 15 = 13: on the main stream - A/B; the scaled chain reuses d_part at once and always keeps them there)
+  const bool side = zchain && h->tune[15] != 13;
+  if (!zchain) LZ_TRY(one_sweep_join(h));
+  const double* z = nullptr;      // where z_3 lies
+  const double* zpart = nullptr;  // the partials of ||z_3||^2
   int npz = 0;
-  for (int t = 0; t < 3; ++t) {
-    int npa = 0;
-    LZ_TRY(step_scaling_spmv(h, n, j + t, src, dst, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
-    LZ_TRY(step_final_sum(h, npa, h->d_alpha + (j + t), "final_sum(alpha)"));
-    // z = (y_t - a_t x_t) - b_t x_{t-1}; the last ||z||^2 is summed by the predict kernel
-    LZ_TRY(step_three_term(h, j + t, j + t - 1, h->d_alpha + (j + t), h->d_beta + (j + t - 1), t < 2, &npz, dst));
-    std::swap(src, dst);
+  if (zchain) {
+    // The chain in the units of z: rows j .. j+3 hold the unscaled z_0 .. z_3 until the walk finishes them, and x_t = z_t / b_t is formed by
+    // division wherever a pass reads it (the bits the scaling SpMV stores).  z_0 = w_j goes straight into row j; step t: the plain coded
+    // product y' = A z_t -> d_r with the partials of z_t . y', ONE launch for both sums (b_t = ||z_t||, a_t = z_t . y' / ||z_t||^2), then
+    // z_{t+1} = (y' / b_t - a_t (z_t / b_t)) - b_t x_{t-1} -> row j + t + 1.  Three launches less than the scaled chain and 17 M bytes per
+    // product instead of 25 M.
+    // The products leave their partials in d_ospart: the side stream of the group before may still be adding up the walk's in d_part.
+    // For the same reason the opening takes beta_{j-1} = b_3 of that group from st.b3 (the same bits post stores into the beta slot).
+    const double* b_open = h->os_side_pending ? st.b3 : h->d_beta + (j - 2);
+    auto three_term_z = [&](int mode, int t) {  // t = -1: the opening
+      Scope sc(h, LZ_K_THREE, 32.0 * M, (mode == 0 ? 6.0 : mode == 1 ? 8.0 : 9.0) * M);
+      npz = launch_three_term_z(mode, basis_row(h, j + t + 1), h->d_r, basis_row(h, j + t), basis_row(h, j + t - 1), h->d_alpha + (j + t),
+                                mode == 0 ? b_open : h->d_beta + (j + t - 1), mode == 2 ? h->d_beta + (j + t - 2) : nullptr, h->rows_pad, st.zp,
+                                h->stream);
+      return check_launch(h, mode == 0 ? "three_term(chain opening)" : "three_term(chain)");
+    };
+    LZ_TRY(three_term_z(0, -1));
+    for (int t = 0; t < 3; ++t) {
+      double* zt = basis_row(h, j + t);
+      int npa = 0;
+      {
+        Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true), spmv_flops(h));
+        npa = launch_spmv_ell(h->csr, zt, h->d_r, zt, h->d_ospart, h->stream);
+        LZ_TRY(check_launch(h, "spmv(ell, chain)"));
+      }
+      {
+        Scope sc(h, LZ_K_FINAL, 0, 0);
+        launch_final_sum_chain(st.zp, npz, h->d_ospart, npa, h->d_beta + (j + t - 1), h->d_alpha + (j + t), h->stream);
+        LZ_TRY(check_launch(h, "final_sum(chain)"));
+      }
+      LZ_TRY(three_term_z(t == 0 ? 1 : 2, t));  // the last ||z||^2 is summed by the predict kernel
+    }
+    z = basis_row(h, j + 3);
+    zpart = st.zp;
+  } else {
+    // the chain: w_j -> d_r; then x_t = src / b_t -> V[j + t], y_t -> the other residual buffer, z in place there
+    LZ_TRY(step_three_term(h, j - 1, j - 2, h->d_alpha + (j - 1), h->d_beta + (j - 2), true));
+    double* src = h->d_r;
+    double* dst = h->d_r2;
+    for (int t = 0; t < 3; ++t) {
+      int npa = 0;
+      LZ_TRY(step_scaling_spmv(h, n, j + t, src, dst, h->d_osi + 2, &npa));  // (d_osi[2] stays 0: always scale on read)
+      LZ_TRY(step_final_sum(h, npa, h->d_alpha + (j + t), "final_sum(alpha)"));
+      // z = (y_t - a_t x_t) - b_t x_{t-1}; the last ||z||^2 is summed by the predict kernel
+      LZ_TRY(step_three_term(h, j + t, j + t - 1, h->d_alpha + (j + t), h->d_beta + (j + t - 1), t < 2, &npz, dst));
+      std::swap(src, dst);
+    }
+    z = src;  // (d_r2: three steps from d_r)
+    zpart = h->d_part;
   }
-  const double* z = src;  // (d_r2: three steps from d_r)
   const int ldp = os_quad_ldp(j);
+  LZ_TRY(one_sweep_join(h));  // the state of the group before: predict reads G, H and chat, the walk overwrites d_part
   {
     Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_os_quad_predict(h->d_part, npz, h->d_nrm2, st.chat, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + (j - 1), st.gq, ldg, h->stream);
+    launch_os_quad_predict(zpart, npz, h->d_nrm2, st.chat, st.G, st.H, n, j, h->d_alpha + j, h->d_beta + (j - 1), st.gq, ldg, h->stream);
     LZ_TRY(check_launch(h, "one-sweep group predict"));
   }
   {
     Scope sc(h, LZ_K_UPDATE, 8.0 * j * M + 64.0 * M, 16.0 * (j + 1) * M);
-    launch_os_quad_sweep(h->d_V, h->ldv, h->rows_pad, j, st.gq, ldg, z, h->d_nrm2, h->d_part, wide8, h->stream);
+    launch_os_quad_sweep(h->d_V, h->ldv, h->rows_pad, j, st.gq, ldg, z, zchain ? h->d_beta + (j - 1) : nullptr, h->d_nrm2, h->d_part, wide8, h->stream);
     LZ_TRY(check_launch(h, "one-sweep group walk"));
   }
+  hipStream_t ps = side ? h->os_stream : h->stream;  // where the second-stage sums and post run
+  if (side) {
+    LZ_HIP(h, hipEventRecord(h->e_os_walk, h->stream));
+    LZ_HIP(h, hipStreamWaitEvent(h->os_stream, h->e_os_walk, 0));
+    h->os_side_pending = true;  // (from here on: an error below leaves it set, and the next setup or read-back joins)
+  }
   {
-    Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_final_rows_t(h->d_part, nbq, 4 * ldp, 3 * ldp + j + 4, h->d_c, h->stream);
+    Scope sc(h, LZ_K_FINAL, 0, 0, ps);
+    launch_final_rows_t(h->d_part, nbq, 4 * ldp, 3 * ldp + j + 4, h->d_c, ps);
     LZ_TRY(check_launch(h, "final_rows(one-sweep group)"));
     LZ_HIP(h, launch_os_quad_post(h->d_c, ldp, st.gq, ldg, st.G, st.H, n, j, h->d_nrm2, h->d_alpha + j, h->d_beta + (j - 1), kOneSweepTau, h->d_osi,
-                                  st.elog, h->stream));
+                                  st.elog, ps));
     LZ_TRY(check_launch(h, "one-sweep group post"));
   }
   {  // closing: y = A V[j+3] -> d_r (V[j+3] is in place: the plain ELL product), alpha_{j+3} and the next chat
     double* vj = basis_row(h, j + 3);
+    double* apart = zchain ? h->d_ospart : h->d_part;
     int npa = 0;
     {
       Scope sc(h, LZ_K_SPMV, spmv_bytes(h, true), spmv_flops(h));
-      npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, h->d_part, h->stream);
+      npa = launch_spmv_ell(h->csr, vj, h->d_r, vj, apart, h->stream);
       LZ_TRY(check_launch(h, "spmv(ell)"));
     }
-    Scope sc(h, LZ_K_FINAL, 0, 0);
-    launch_os_sum_predict(h->d_part, npa, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true,
-                          j + 4 < n, h->stream);
-    LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+    if (side) {
+      {  // alpha_{j+3} on the main stream (the next opening pass reads it, and b_3), the chat prediction behind post on the side stream
+        Scope sc(h, LZ_K_FINAL, 0, 0);
+        launch_final_sum_root(apart, npa, h->d_alpha + (j + 3), h->d_nrm2, st.b3, h->stream);
+        LZ_TRY(check_launch(h, "final_sum(alpha, b3)"));
+      }
+      LZ_HIP(h, hipEventRecord(h->e_os_alpha, h->stream));
+      LZ_HIP(h, hipStreamWaitEvent(h->os_stream, h->e_os_alpha, 0));
+      if (j + 4 < n) {
+        Scope sc(h, LZ_K_FINAL, 0, 0, ps);
+        launch_os_sum_predict(nullptr, 0, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true, true, ps);
+        LZ_TRY(check_launch(h, "one-sweep predict(side)"));
+      }
+      LZ_HIP(h, hipEventRecord(h->e_os_ready, h->os_stream));
+    } else {
+      Scope sc(h, LZ_K_FINAL, 0, 0);
+      launch_os_sum_predict(apart, npa, h->d_alpha + (j + 3), st.G, st.H, n, j + 3, h->d_alpha + (j + 3), h->d_beta + (j + 2), st.chat, true,
+                            j + 4 < n, h->stream);
+      LZ_TRY(check_launch(h, "final_sum(alpha) + one-sweep predict"));
+    }
   }
   h->last_os_quads += 1;
   return LZ_OK;
@@ -853,6 +953,7 @@ int one_sweep_step_run(lz_handle h, int form, int j, bool wide, int* blocks) {
   h->last_os_pairs = pairs;
   h->last_os_quads = quads;
   LZ_TRY(rc);
+  LZ_TRY(one_sweep_join(h));
   LZ_HIP(h, hipStreamSynchronize(h->stream));
   if (blocks) *blocks = nb;
   return LZ_OK;
@@ -863,6 +964,7 @@ int one_sweep_state_get(lz_handle h, int form, int j, double* G, double* H, doub
   if (h->os_step_n != n || !h->d_os) return fail(h, LZ_ERR_STATE, "one-sweep step: no state set for this basis (lz_os_state_set after lz_basis_alloc)");
   OneSweepState st;
   one_sweep_view(h, n, st);
+  LZ_TRY(one_sweep_join(h));
   auto get = [&](void* dst, const void* src, size_t bytes) {
     return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
   };
@@ -888,6 +990,7 @@ int one_sweep_state_get(lz_handle h, int form, int j, double* G, double* H, doub
 // raw rows j0 .. j0 + count - 1 with their padding (rows_pad doubles each) and the first part_count doubles the last step's walk left in
 // d_part (its tap)
 int one_sweep_raw_get(lz_handle h, int j0, int count, double* rows, double* part, int64_t part_count) {
+  LZ_TRY(one_sweep_join(h));
   if (rows) {
     if (count < 1 || j0 < 0 || j0 + count > h->n) return fail(h, LZ_ERR_ARG, "lz_os_raw_get: rows out of range");
     LZ_HIP(h, hipMemcpy2DAsync(rows, (size_t)h->rows_pad * sizeof(double), h->d_V + (int64_t)j0 * h->ldv, (size_t)h->ldv * sizeof(double),
@@ -942,7 +1045,7 @@ Loop choose_loop(lz_handle h, int n, const QtwPlan* plan = nullptr) {
   const bool one_sweep_ok = one_rank && full_fused && default_kernels && !(f & LZ_FLAG_OVERLAP_HALO) && n >= 2 && n <= kOneSweepMaxN;
   // (7: never the fused form; 6: never the pair form; 8 / 9: the pair form where it applies, 8 / 16 positions per lane in its walk - A/B;
   // 10 / 11: the group form where it applies, 4 / 8 positions per lane in its walk - A/B)
-  if (h->tune[15] >= 6 && h->tune[15] <= 11 && one_sweep_ok) return LOOP_ONE_SWEEP;
+  if (h->tune[15] >= 6 && h->tune[15] <= 13 && one_sweep_ok) return LOOP_ONE_SWEEP;
   if (!knob_auto || !full_fused || !default_kernels) return LOOP_SIX;
   if (one_rank && qp.G <= 8 && n <= 4096 && h->part_cap >= fused_coff(h) + (size_t)(n + 16) * (size_t)qp.G) return LOOP_FUSED_SMALL;
   if (!(f & LZ_FLAG_OVERLAP_HALO) && h->rows_pad <= kThreeTermFusedMaxRows) return LOOP_THREE_TERM_FUSED;

@@ -1311,6 +1311,105 @@ int launch_three_term(double* r, const double* vj, const double* vjm1, const dou
   return (int)g;
 }
 
+// The group chain in the units of z (one_sweep_quad_iter, lz_loops.hip): the chain vectors stay unscaled in their basis rows, and
+// x = z / b is formed by IEEE division wherever a pass reads one - the same bits the scaling SpMV used to store.  Out of place:
+// `out` is the next basis row, none of the inputs.  MODE 0, the opening: out = (y - alpha zt) - beta xm, k_three_term's expression
+// (zt = V[j-1], xm = V[j-2], beta in `bt`).  MODE 1 / 2, chain step t: out = (y / b_t - alpha (zt / b_t)) - b_t xm' with zt = z_t,
+// b_t in `bt`, and xm' = xm = V[j-1] (MODE 1, t = 0: a finished row) or xm / b_{t-1} (MODE 2: xm = z_{t-1}, b_{t-1} in `bm`).
+// part[b] = block b's share of ||out||^2.  Padding positions are 0 in every input and leave as 0.
+template <int MODE>
+__global__ __launch_bounds__(kTPB) void k_three_term_z(double* __restrict__ out, const double* __restrict__ y, const double* __restrict__ zt,
+                                                      const double* __restrict__ xm, const double* __restrict__ alpha,
+                                                      const double* __restrict__ bt, const double* __restrict__ bm, int64_t n2,
+                                                      double* __restrict__ part) {
+  __shared__ double sm[kTPB / 64];
+  const double a = alpha[0];
+  const double b = bt[0];
+  const double bp = MODE == 2 ? bm[0] : 1.0;
+  double2* o2 = reinterpret_cast<double2*>(out);
+  const double2* y2 = reinterpret_cast<const double2*>(y);
+  const double2* v2 = reinterpret_cast<const double2*>(zt);
+  const double2* m2 = reinterpret_cast<const double2*>(xm);
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kTPB + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kTPB) {
+    double2 x = y2[i];
+    double2 v, m;
+    if (MODE == 0) {  // finished rows, read here for the last time before the walk: streamed
+      v = ld_stream<1>(v2 + i);
+      m = ld_stream<1>(m2 + i);
+    } else {  // rows of this chain, just written
+      v = v2[i];
+      m = m2[i];
+      x.x = x.x / b;
+      x.y = x.y / b;
+      v.x = v.x / b;
+      v.y = v.y / b;
+    }
+    if (MODE == 2) {
+      m.x = m.x / bp;
+      m.y = m.y / bp;
+    }
+    x.x = x.x - v.x * a;
+    x.y = x.y - v.y * a;
+    x.x = x.x - m.x * b;
+    x.y = x.y - m.y * b;
+    o2[i] = x;  // plain store: the row is re-read by the very next kernel
+    acc = fma(x.x, x.x, acc);
+    acc = fma(x.y, x.y, acc);
+  }
+  acc = block_sum(acc, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+int launch_three_term_z(int mode, double* out, const double* y, const double* zt, const double* xm, const double* alpha, const double* bt,
+                        const double* bm, int64_t len, double* part, hipStream_t s) {
+  const int64_t n2 = len >> 1;
+  int64_t g = (n2 + kTPB - 1) / kTPB;  // (k_three_term's grid)
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+#define LZ_TTZ_GO(MM) hipLaunchKernelGGL(k_three_term_z<MM>, dim3((int)g), dim3(kTPB), 0, s, out, y, zt, xm, alpha, bt, bm, n2, part)
+  switch (mode) {
+    case 0: LZ_TTZ_GO(0); break;
+    case 1: LZ_TTZ_GO(1); break;
+    default: LZ_TTZ_GO(2); break;
+  }
+#undef LZ_TTZ_GO
+  return (int)g;
+}
+
+// One block behind a chain product on the unscaled z_t: both sums are wanted at the same moment, so one launch adds both partial runs,
+// each in k_final_sum's grouping: b_t = sqrt(||z_t||^2) (zpart) -> beta_slot, a_t = (z_t . A z_t) / ||z_t||^2 (apart) -> alpha_slot.
+// (nrm2[0] is left alone: the post kernel of the group before may still be reading it on the side stream.)
+__global__ __launch_bounds__(kFinalThreads) void k_final_sum_chain(const double* __restrict__ zpart, int nz, const double* __restrict__ apart,
+                                                                  int na, double* __restrict__ beta_slot, double* __restrict__ alpha_slot) {
+  __shared__ double sm[2][kFinalThreads / 64];
+  const double zz = final_sum_1024(zpart, nz, sm[0]);
+  const double za = final_sum_1024(apart, na, sm[1]);
+  if (threadIdx.x == 0) {
+    beta_slot[0] = sqrt(zz);
+    alpha_slot[0] = za / zz;
+  }
+}
+void launch_final_sum_chain(const double* zpart, int nz, const double* apart, int na, double* beta_slot, double* alpha_slot, hipStream_t s) {
+  hipLaunchKernelGGL(k_final_sum_chain, dim3(1), dim3(kFinalThreads), 0, s, zpart, nz, apart, na, beta_slot, alpha_slot);
+}
+
+// One block behind a group's closing product when post runs on the side stream: out[0] = sum(part[0 .. np)) (k_final_sum) and
+// root_out[0] = sqrt(nrm2[0]) - b_3, the bits k_os_quad_post stores into its beta slot, for the next group's opening pass, which must
+// not wait for post.
+__global__ __launch_bounds__(kFinalThreads) void k_final_sum_root(const double* __restrict__ part, int np, double* __restrict__ out,
+                                                                 const double* __restrict__ nrm2, double* __restrict__ root_out) {
+  __shared__ double sm[kFinalThreads / 64];
+  const double t = final_sum_1024(part, np, sm);
+  if (threadIdx.x == 0) {
+    out[0] = t;
+    root_out[0] = sqrt(nrm2[0]);
+  }
+}
+void launch_final_sum_root(const double* part, int np, double* out, const double* nrm2, double* root_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_final_sum_root, dim3(1), dim3(kFinalThreads), 0, s, part, np, out, nrm2, root_out);
+}
+
 // One-reduce partial loop, behind the SpMV of step j: r'' = y - beta v_{j-1} (k_three_term's expression) and, in the same pass,
 // the block partials of the three self terms the next step's ||r||^2 is made of - r''.r'' -> part[b], u.r'' -> part[G + b],
 // u.u -> part[2 G + b] with u = v_j - so that a step without a sweep needs no pass 1 at all.
@@ -1733,6 +1832,8 @@ void launch_os_post(const double* d, const double* chat, double* G, double* H, i
 // ||w_{j+1}||^2 from its partials), k_final_sum's grouping; then, when `predict`, the next step's predictions
 //   c_hat_i = ((A V_i) . v_j - alpha_j G[i, j] - beta_j G[i, j-1]) / bn,  (A V_i) . v_j = sum_{l <= i+1} H[l, i] G[l, j]  (i < j),  alpha_j  (i = j)
 // with bn = sqrt(||w_{j+1}||^2), or 1 in the fused form (whose sweep works in the units of w), and column j of H.
+// predict == 2 (fused form only): the predictions alone - alpha_j is read from its slot, where a launch before this one has summed it
+// (the group form's side stream), and part / sum_out are not touched.
 template <bool FUSED>
 __global__ __launch_bounds__(kFinalThreads) void k_os_sum_predict(const double* __restrict__ part, int np, double* __restrict__ sum_out,
                                                                  const double* __restrict__ G, double* __restrict__ H, int n, int j,
@@ -1740,10 +1841,14 @@ __global__ __launch_bounds__(kFinalThreads) void k_os_sum_predict(const double* 
                                                                  double* __restrict__ chat, int predict) {
   __shared__ double sm[kFinalThreads / 64];
   __shared__ double s_sum;
-  const double t = final_sum_1024(part, np, sm);
-  if (threadIdx.x == 0) {
-    sum_out[0] = t;
-    s_sum = t;
+  if (predict == 2) {
+    if (threadIdx.x == 0) s_sum = alpha_j[0];
+  } else {
+    const double t = final_sum_1024(part, np, sm);
+    if (threadIdx.x == 0) {
+      sum_out[0] = t;
+      s_sum = t;
+    }
   }
   if (!predict) return;
   __syncthreads();
@@ -1765,7 +1870,9 @@ __global__ __launch_bounds__(kFinalThreads) void k_os_sum_predict(const double* 
 
 void launch_os_sum_predict(const double* part, int np, double* sum_out, const double* G, double* H, int n, int j, const double* alpha_j,
                            const double* beta_j, double* chat, bool fused, bool predict, hipStream_t s) {
-  if (fused)
+  if (fused && !part)  // (the predictions alone)
+    hipLaunchKernelGGL(k_os_sum_predict<true>, dim3(1), dim3(kFinalThreads), 0, s, part, 0, sum_out, G, H, n, j, alpha_j, beta_j, chat, 2);
+  else if (fused)
     hipLaunchKernelGGL(k_os_sum_predict<true>, dim3(1), dim3(kFinalThreads), 0, s, part, np, sum_out, G, H, n, j, alpha_j, beta_j, chat, predict ? 1 : 0);
   else
     hipLaunchKernelGGL(k_os_sum_predict<false>, dim3(1), dim3(kFinalThreads), 0, s, part, np, sum_out, G, H, n, j, alpha_j, beta_j, chat, predict ? 1 : 0);
@@ -2244,8 +2351,8 @@ __device__ __forceinline__ bool quad_writer(int lane) { return (lane & (64 / NV 
 // valid address and zeroed, so they add nothing (what they read may be mid-update: it is discarded).
 template <int P, int RU>
 __global__ __launch_bounds__(kTPB) void k_os_quad_sweep(double* __restrict__ V, int64_t ldv, int n2, int j, const double* __restrict__ g, int ldg,
-                                                       const double* __restrict__ zbuf, const double* __restrict__ nrm2, int ldp,
-                                                       double* __restrict__ part) {
+                                                       const double* __restrict__ zbuf, const double* __restrict__ bz,
+                                                       const double* __restrict__ nrm2, int ldp, double* __restrict__ part) {
   extern __shared__ double keep[];  // [kTPB / 64][4 ldp]: this block's per-wave dots
   constexpr int NV = 4 * RU;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2264,11 +2371,21 @@ __global__ __launch_bounds__(kTPB) void k_os_quad_sweep(double* __restrict__ V, 
   double2 x[4][P];
   double sx[4][P], sy[4][P];
   {
-    const double2* z2 = reinterpret_cast<const double2*>(zbuf);
+    // bz (the chain in the units of z): rows j .. j+3 hold the unscaled z_0 .. z_3 and bz[t] = b_t - x_t = z_t / b_t is formed here, by
+    // the division the scaling SpMV did when it stored x_t; else rows j .. j+2 hold x_0 .. x_2 and zbuf holds z_3
+    const double2* z2 = bz ? V2 + (int64_t)(j + 3) * ld2 : reinterpret_cast<const double2*>(zbuf);
+    double bt[3] = {1.0, 1.0, 1.0};
+    if (bz) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) bt[t] = bz[t];
+    }
 #pragma unroll
     for (int p = 0; p < P; ++p) {
 #pragma unroll
-      for (int t = 0; t < 3; ++t) x[t][p] = V2[(int64_t)(j + t) * ld2 + pos[p]];
+      for (int t = 0; t < 3; ++t) {
+        x[t][p] = V2[(int64_t)(j + t) * ld2 + pos[p]];
+        if (bz) x[t][p] = make_double2(x[t][p].x / bt[t], x[t][p].y / bt[t]);  // block-uniform
+      }
       const double2 zz = z2[pos[p]];
       x[3][p] = make_double2(zz.x / b3, zz.y / b3);
 #pragma unroll
@@ -2383,15 +2500,15 @@ int os_quad_sweep_blocks(int64_t len, bool wide8) {
 }
 int os_quad_ldp(int j) { return qtw_ldp(j + 4); }
 
-int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* nrm2, double* part,
-                         bool wide8, hipStream_t s) {
+int launch_os_quad_sweep(double* V, int64_t ldv, int64_t len, int j, const double* g, int ldg, const double* z, const double* bz, const double* nrm2,
+                         double* part, bool wide8, hipStream_t s) {
   const int64_t n2 = len >> 1;
   const int P = os_quad_sweep_p(n2, wide8);
   const int grid = (int)((n2 + (int64_t)kTPB * P - 1) / ((int64_t)kTPB * P));
   const int ldp = os_quad_ldp(j);
   const size_t lds = os_quad_lds_bytes(ldp);  // <= kOneSweepQuadLds (os_quad_max_ldp): within what a kernel may ask for by default
 #define LZ_OSQ_GO(PP, RR) \
-  hipLaunchKernelGGL((k_os_quad_sweep<PP, RR>), dim3(grid), dim3(kTPB), lds, s, V, ldv, (int)n2, j, g, ldg, z, nrm2, ldp, part)
+  hipLaunchKernelGGL((k_os_quad_sweep<PP, RR>), dim3(grid), dim3(kTPB), lds, s, V, ldv, (int)n2, j, g, ldg, z, bz, nrm2, ldp, part)
   switch (P) {
     case 8: LZ_OSQ_GO(8, 1); break;
     case 4: LZ_OSQ_GO(4, 2); break;

@@ -16,7 +16,11 @@ There is no correcting sweep and no re-normalisation in a group: a leftover abov
 and the steps left over behind the last group are the single fused form's, as in one_sweep_pair_lanczos.  The device kernels
 (k_os_quad_predict / k_os_quad_sweep / k_os_quad_post, lanczos_amd/csrc/lz_reorth.hip) restate this arithmetic at m = 4.
 
-    python tools/one_sweep_group_prototype.py [--m 4]
+The device's default chain works in the units of z (chain="unscaled"): the product runs on the unscaled z_t, b_t = ||z_t|| and
+a_t = z_t . A z_t / ||z_t||^2 come out of one pair of sums behind it, z_{t+1} = (A z_t / b_t - a_t (z_t / b_t)) - b_t x_{t-1}, and
+x_t = z_t / b_t is formed by division wherever it is read.  Same leftovers (tests/test_one_sweep_chain_host.py).
+
+    python tools/one_sweep_group_prototype.py [--m 4] [--chain unscaled]
 """
 from __future__ import annotations
 
@@ -84,8 +88,11 @@ def group_post(G, Hm, g, D, mm, vv, a, b, j, m, n):
     return e_old, e_in
 
 
-def one_sweep_group_lanczos(H, n, m=4, seed=99, v0=None, tau=1e-14):
-    """Returns (alpha, beta, V, stats); stats: groups, abandoned, e_old / e_in (per first step of a group), trips (the single steps'), G."""
+def one_sweep_group_lanczos(H, n, m=4, seed=99, v0=None, tau=1e-14, chain="scaled"):
+    """Returns (alpha, beta, V, stats); stats: groups, abandoned, e_old / e_in (per first step of a group), trips (the single steps'), G.
+    chain: "scaled" - every chain vector is normalised before its product, as described above - or "unscaled": the device's default."""
+    if chain not in ("scaled", "unscaled"):
+        raise ValueError("chain must be 'scaled' or 'unscaled'")
     H = scipy.sparse.csr_matrix(H)
     M = H.shape[0]
     V = np.zeros((n, M))
@@ -127,14 +134,29 @@ def one_sweep_group_lanczos(H, n, m=4, seed=99, v0=None, tau=1e-14):
             a, b = np.zeros(m), np.zeros(m)
             X = np.zeros((m, M))
             w = (y - alpha[j - 1] * V[j - 1]) - bet[j - 1] * V[j - 2]
-            b[0] = np.sqrt(np.dot(w, w))
-            X[0] = w / b[0]
-            for t in range(m - 1):
-                yt = H @ X[t]
-                a[t] = np.dot(X[t], yt)
-                z = (yt - a[t] * X[t]) - b[t] * (X[t - 1] if t else V[j - 1])
-                b[t + 1] = np.sqrt(np.dot(z, z))
-                X[t + 1] = z / b[t + 1]
+            if chain == "unscaled":
+                # the chain in the units of z (one_sweep_quad_iter's default): the product runs on the unscaled z_t, both sums are taken
+                # behind it, and x_t = z_t / b_t is formed by division wherever it is read - in the three-term pass and in the walk
+                Z = np.zeros((m, M))
+                Z[0] = w
+                for t in range(m - 1):
+                    yt = H @ Z[t]
+                    nz = np.dot(Z[t], Z[t])
+                    b[t] = np.sqrt(nz)
+                    a[t] = np.dot(Z[t], yt) / nz
+                    Z[t + 1] = (yt / b[t] - a[t] * (Z[t] / b[t])) - b[t] * (Z[t - 1] / b[t - 1] if t else V[j - 1])
+                b[m - 1] = np.sqrt(np.dot(Z[m - 1], Z[m - 1]))
+                for t in range(m):
+                    X[t] = Z[t] / b[t]
+            else:
+                b[0] = np.sqrt(np.dot(w, w))
+                X[0] = w / b[0]
+                for t in range(m - 1):
+                    yt = H @ X[t]
+                    a[t] = np.dot(X[t], yt)
+                    z = (yt - a[t] * X[t]) - b[t] * (X[t - 1] if t else V[j - 1])
+                    b[t + 1] = np.sqrt(np.dot(z, z))
+                    X[t + 1] = z / b[t + 1]
             # 2. the predictions
             g = group_predict(G, Hm, chat, a, b, j, m)
             # 3. the one walk over rows 0 .. j-1 and its epilogue
@@ -203,9 +225,9 @@ def one_sweep_group_lanczos(H, n, m=4, seed=99, v0=None, tau=1e-14):
     return alpha, bet[1:], V, stats
 
 
-def report(name, H, n, m, v0=None):
+def report(name, H, n, m, v0=None, chain="scaled"):
     a0, b0, V0 = proto.two_pass_lanczos(H, n, v0=v0)
-    a1, b1, V1, st = one_sweep_group_lanczos(H, n, m, v0=v0)
+    a1, b1, V1, st = one_sweep_group_lanczos(H, n, m, v0=v0, chain=chain)
     scale = np.abs(proto.tridiag_eigs(a0, b0)).max()
     orth = np.abs(V1 @ V1.T - np.eye(n)).max()
     orth0 = np.abs(V0 @ V0.T - np.eye(n)).max()
@@ -216,13 +238,14 @@ def report(name, H, n, m, v0=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, default=4)
+    ap.add_argument("--chain", default="scaled", choices=["scaled", "unscaled"], help="unscaled: the chain in the units of z (the device's default)")
     args = ap.parse_args()
     print("| case | n | m | max e_old | max e_in | max\\|VVᵀ−I\\| (two-pass) | max\\|Δα\\|/scale | max\\|Δβ\\|/scale | |")
     print("|" + "---|" * 9)
     for m in sorted({2, args.m, 6}):
-        print(report("lap2d 300 x 200", proto.lap2d(300, 200), 200, m), flush=True)
+        print(report("lap2d 300 x 200", proto.lap2d(300, 200), 200, m, chain=args.chain), flush=True)
     for name, H, n, v0 in proto.fixtures():
-        print(report(name, H, n, args.m, v0=v0), flush=True)
+        print(report(name, H, n, args.m, v0=v0, chain=args.chain), flush=True)
 
 
 if __name__ == "__main__":
