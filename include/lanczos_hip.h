@@ -772,6 +772,55 @@ int lz_bicgstab_step_time(lz_handle h, int reps, double* ms_out);
  * r~ . v); out[1] = 1 where the products' epilogue yields r~ . v and t . s; out[2] = 1 while a state is live */
 int lz_bicgstab_info(lz_handle h, int* out);
 
+/* ---- symmetric positive definite linear solves (lanczos_amd.cg; Hestenes & Stiefel 1952) -----------------------------------------
+ * A x = b for the REAL square matrix set, taken as symmetric positive definite (neither is tested), scipy.sparse.linalg.cg scalar
+ * for scalar, with an optional diagonal preconditioner d (z = d o r; d NULL: z = r).  With k = 0, 1, ... SciPy's `iteration` and
+ * rho = r . z, iteration k is
+ *     head test: |r| < atol (code 0)
+ *     p = z + (rho / rho_prev) p                                                  (k = 0: p = z)
+ *     q = A p,  pq = p . q (pq == 0 or alpha not finite: -1),  alpha = rho / pq,  x += alpha p,  r -= alpha q,  rho_prev = rho
+ * Five padded vectors of its own (x, r, p, q, d): every other state on the handle is untouched; every setter of the square matrix
+ * drops the state.  The product is the handle's in whatever plan the matrix has, called with x_own = p: its x_own . y epilogue
+ * yields p . q on every plan.  Beside it an iteration is four launches: k_cg_alpha (one block: pq, the breakdown test, alpha, the
+ * first iteration with pq <= 0), k_cg_r (r -= alpha q, the partials of r . r and r . z, z formed on the fly: 24 B a row, 32 with d),
+ * k_cg_scalars (one block: |r|, the history, the head test of the NEXT iteration - so an iteration that ends with |r| < atol
+ * reports 0 at once -, rho, beta, the counter, the done flag) and k_cg_p (x += alpha p, then p = z + beta p from the same load of
+ * p: 40 B a row, 48 with d; the iteration that raised the done flag still updates x).  No atomics: the same input gives the same
+ * bits.  One rank only: LZ_ERR_STATE with no real square matrix, on a handle with a communicator and with LZ_FLAG_REORTH_PARTIAL /
+ * LZ_FLAG_ONE_REDUCE; every call behind lz_cg_begin answers LZ_ERR_STATE before it and after a matrix setter. */
+/* replaces r = b - A x0, z = M r, p = z, rho = r . z ahead of SciPy's loop: allocate and zero all five vectors, r by one product
+ * (x0 NULL: r = b, no product), p = d o r, the partials of r . r and r . z in one pass.  The head test of iteration 0 needs atol: the
+ * first lz_cg_run applies it.  b, x0, d: n doubles; d NULL: no preconditioner; d is not validated (the caller's: finite, positive). */
+int lz_cg_begin(lz_handle h, const double* b, const double* x0, const double* d);
+/* replaces the body of SciPy's loop: first the head test of a state fresh from lz_cg_begin / lz_cg_set_state, then up to iters
+ * iterations without a host synchronisation, then one synchronisation.  Every test runs on the device against atol_eff (the
+ * caller's max(atol, rtol |b|)); the first that is met sets the done flag and every later launch of this section returns at once
+ * (the products of the rest of the call still run; their output is not read).  A call on a state that is done enqueues nothing.
+ * state_out (16 doubles, may be NULL): iterations that updated x in total, done, code (0, -1), exit kind (0 none yet, 1 converged,
+ * 2 breakdown), 1 where a head test set the flag (0: inside an iteration - x did not move), the recurrence's |r| at the last head
+ * test, rho, rho_prev, alpha, beta, pq, the first iteration with pq <= 0 (-1: none), four spares. */
+int lz_cg_run(lz_handle h, int iters, double atol_eff, double* state_out);
+/* replaces the norm(r) of SciPy's head test as a record: out[i] = |r| at the head test of iteration i, i < count.  count may pass
+ * the tests done, up to the iterations lz_cg_run was asked for so far plus one (the history holds 1024 at least): a test that did
+ * not run, or that lz_cg_set_state skipped, reads zero. */
+int lz_cg_history(lz_handle h, double* out, int count);
+/* replaces reading SciPy's x (and r, p, q in a debugger): a vector of the state as n host doubles.  which | LZ_CG_RAW: the padded
+ * device vector as it is (lz_padded_rows(n) doubles) - the tests' look at the padding. */
+enum { LZ_CG_X = 0, LZ_CG_R = 1, LZ_CG_P = 2, LZ_CG_Q = 3, LZ_CG_D = 4, LZ_CG_RAW = 8 };
+int lz_cg_get(lz_handle h, int which, double* out);
+/* replaces SciPy's locals at the head of iteration k >= 0 (allocates and zeroes as lz_cg_begin does): x, r, p - already p_k, the
+ * direction iteration k multiplies -, n doubles each; d or NULL; scalars[1] = rho = r . z.  |r| is formed on the device, and the
+ * first lz_cg_run applies the head test of iteration k.  The history of iterations 0 .. k - 1 reads zero.  Tests drive one iteration,
+ * and the breakdown exit, from chosen numbers with it. */
+int lz_cg_set_state(lz_handle h, int k, const double* x, const double* r, const double* p, const double* d, const double* scalars);
+/* ms_out[0 .. 3) = the device times (hipEvents) of the product q = A p, of k_cg_r and of k_cg_p: each the mean of reps launches
+ * behind one warm-up launch.  Needs a state that has run at least one iteration and is not done; the state is spent afterwards
+ * (LZ_ERR_STATE until the next lz_cg_begin).  The measurements of tools/cg_probe.py */
+int lz_cg_step_time(lz_handle h, int reps, double* ms_out);
+/* out[0] = launches per iteration, the product counted as one (5); out[1] = 1 where the live state has a preconditioner; out[2] = 1
+ * while a state is live */
+int lz_cg_info(lz_handle h, int* out);
+
 /* ---- restarted GMRES (lanczos_amd.gmres; Saad & Schultz 1986) -------------------------------------------------------------------
  * A x = b for the REAL square matrix set, scipy.sparse.linalg.gmres' rules: with m the restart length, a cycle is
  *     V[0] = r / |r|, S = |r| e_0;  for j = 0 .. m - 1: w = A V[j], w against V[0 .. j] (the Hessenberg column), h1 = |w|,

@@ -21,7 +21,8 @@ from .minres import minres
 from .lsmr import lsmr
 from .bicgstab import bicgstab
 from .gmres import gmres
+from .cg import cg
 
-__all__ = ["Lanczos", "IrrLanczos", "Hamiltonian", "StencilOperator", "eigsh", "svds", "eigs", "expm_multiply", "minres", "lsmr", "bicgstab", "gmres", "LanczosHipError", "load_library", "FLAG_PROFILE", "FLAG_QTW_MFMA", "FLAG_QTW_VALU",
+__all__ = ["Lanczos", "IrrLanczos", "Hamiltonian", "StencilOperator", "eigsh", "svds", "eigs", "expm_multiply", "minres", "lsmr", "bicgstab", "gmres", "cg", "LanczosHipError", "load_library", "FLAG_PROFILE", "FLAG_QTW_MFMA", "FLAG_QTW_VALU",
            "FLAG_SPMV_SCALAR", "FLAG_FUSED_NORM", "FLAG_REORTH_PARTIAL"]
 __version__ = "0.1.0"

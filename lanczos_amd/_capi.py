@@ -218,6 +218,13 @@ SIGNATURES = {
     "lz_bicgstab_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D]),
     "lz_bicgstab_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lz_bicgstab_step_time": (C.c_int, [_P, C.c_int, _D]),
+    "lz_cg_begin": (C.c_int, [_P, _D, _D, _D]),
+    "lz_cg_run": (C.c_int, [_P, C.c_int, C.c_double, _D]),
+    "lz_cg_history": (C.c_int, [_P, _D, C.c_int]),
+    "lz_cg_get": (C.c_int, [_P, C.c_int, _D]),
+    "lz_cg_set_state": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D]),
+    "lz_cg_info": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lz_cg_step_time": (C.c_int, [_P, C.c_int, _D]),
     "lz_gmres_begin": (C.c_int, [_P, C.c_int, _D, _D]),
     "lz_gmres_run": (C.c_int, [_P, C.c_int, C.c_double, _D]),
     "lz_gmres_end_cycle": (C.c_int, [_P, C.c_double, _D]),
@@ -1229,6 +1236,71 @@ class Handle:
         out = (C.c_int * 3)()
         self.check(self.lib.lz_bicgstab_info(self._h, out))
         return {"launches_per_iteration": int(out[0]), "dots_in_product": bool(out[1]), "live": bool(out[2])}
+
+    # -- symmetric positive definite linear solves (lanczos_amd.cg): five vectors of their own on the real square matrix set
+    CG_VECTORS = {"x": 0, "r": 1, "p": 2, "q": 3, "d": 4}
+    CG_STATE = ("iterations", "done", "code", "exit", "head", "rnorm", "rho", "rho_prev", "alpha", "beta", "pq", "indefinite_at")
+    CG_EXITS = {0: None, 1: "converged", 2: "breakdown"}
+
+    def cg_begin(self, b, x0=None, d=None):
+        """``r = b - A x0`` (``x0`` None: ``r = b``), ``p = d r`` (``d`` None: ``p = r``); a fresh state whose head test the first
+        ``cg_run`` applies"""
+        b = f64(b)
+        assert b.shape == (self.rows,)
+        if x0 is not None:
+            x0 = f64(x0)
+            assert x0.shape == (self.rows,)
+        if d is not None:
+            d = f64(d)
+            assert d.shape == (self.rows,)
+        self.check(self.lib.lz_cg_begin(self._h, dptr(b), dptr(x0) if x0 is not None else None, dptr(d) if d is not None else None))
+
+    def cg_run(self, iters, atol_eff):
+        """up to ``iters`` iterations with no host synchronisation between them -> a dict of ``CG_STATE`` (the totals, how the state
+        ended - ``exit`` is None, ``"converged"`` or ``"breakdown"`` - and the last iteration's scalars; ``indefinite_at`` is None or
+        the first iteration with ``p . q <= 0``)"""
+        out = np.zeros(16)
+        self.check(self.lib.lz_cg_run(self._h, int(iters), float(atol_eff), dptr(out)))
+        st = dict(zip(self.CG_STATE, (float(v) for v in out)))
+        st["iterations"], st["done"], st["code"], st["head"] = int(out[0]), bool(out[1]), int(out[2]), bool(out[4])
+        st["exit"] = self.CG_EXITS[int(out[3])]
+        st["indefinite_at"] = None if out[11] < 0 else int(out[11])
+        return st
+
+    def cg_history(self, count):
+        """``|r|`` at the head tests of iterations ``0 .. count - 1``"""
+        out = np.zeros(int(count))
+        self.check(self.lib.lz_cg_history(self._h, dptr(out), int(count)))
+        return out
+
+    def cg_get(self, which, raw=False):
+        """a vector of the state (``"x"``, ``"r"``, ``"p"``, ``"q"``, ``"d"``) as ``n`` doubles; ``raw``: the padded device vector"""
+        out = np.empty(self.padded_rows(self.rows) if raw else self.rows)
+        self.check(self.lib.lz_cg_get(self._h, self.CG_VECTORS[which] | (8 if raw else 0), dptr(out)))
+        return out
+
+    def cg_set_state(self, k, x, r, p, d, scalars):
+        """the state iteration ``k`` (from 0) starts from: ``p`` is already ``p_k``; ``d`` may be None; ``scalars`` = (rho,)"""
+        vecs = [f64(a) for a in (x, r, p)]
+        assert all(a.shape == (self.rows,) for a in vecs)
+        if d is not None:
+            d = f64(d)
+            assert d.shape == (self.rows,)
+        sc = f64(scalars)
+        assert sc.shape == (1,)
+        self.check(self.lib.lz_cg_set_state(self._h, int(k), *(dptr(a) for a in vecs), dptr(d) if d is not None else None, dptr(sc)))
+
+    def cg_step_time(self, reps=20):
+        """device milliseconds of ``(A p, k_cg_r, k_cg_p)`` (means of ``reps`` launches); spends the state"""
+        out = np.zeros(3)
+        self.check(self.lib.lz_cg_step_time(self._h, int(reps), dptr(out)))
+        return tuple(float(v) for v in out)
+
+    def cg_info(self):
+        """{"launches_per_iteration", "preconditioned": the live state has a diagonal ``d``, "live"}"""
+        out = (C.c_int * 3)()
+        self.check(self.lib.lz_cg_info(self._h, out))
+        return {"launches_per_iteration": int(out[0]), "preconditioned": bool(out[1]), "live": bool(out[2])}
 
     # -- restarted GMRES (lanczos_amd.gmres): a basis of restart + 1 rows, x and b of their own on the real square matrix set
     GMRES_WHICH = {"x": 0, "w": 1, "b": 2, "y": 3, "rows": 4, "small": 5}

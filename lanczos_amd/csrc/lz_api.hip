@@ -534,6 +534,7 @@ int lz_destroy(lz_handle h) {
   lsmr_free(h);
   bicgstab_free(h);
   gmres_free(h);
+  cg_free(h);
   big_free(h->poly.d_rot);
   big_free(h->poly.d_acc);
   big_free(h->poly.d_coef);

@@ -188,6 +188,26 @@ struct BicgstabState {
   int done = 0;
 };
 
+// Conjugate gradients (lz_cg.hip; lanczos_amd.cg): A x = b on the real square matrix set, taken as symmetric positive definite, with an
+// optional diagonal preconditioner.  No basis: five padded vectors of ld doubles each behind vec, in this order - X, R, P, Q (= A p),
+// D (the preconditioner's diagonal; zero and unread without one) - and the small device state of lz_cg.hip.
+struct CgState {
+  double* vec = nullptr;   // 5 * ld doubles; [rows, ld) of each is zero
+  double* ds = nullptr;    // scalars (kCgDoubles)
+  int* di = nullptr;       // done, iteration counter, code, exit kind ... (kCgInts)
+  double* part = nullptr;  // the product's x_own . y partials, then two sets of the passes' own
+  size_t part_cap = 0;
+  double* hist = nullptr;  // |r| at every head test
+  int hist_cap = 0;
+  int64_t ld = 0;
+  bool live = false;       // lz_cg_begin / lz_cg_set_state ran on the matrix now set
+  bool fresh = false;      // the head test of the coming iteration has not been applied yet (the next lz_cg_run does, with its atol)
+  bool given = false;      // rho of the fresh state was uploaded (lz_cg_set_state), not formed on the device
+  bool pre = false;        // D holds a preconditioner
+  int steps = 0;           // iterations done (the device's counter, as of the last synchronisation)
+  int done = 0;
+};
+
 // Restarted GMRES (lz_gmres.hip; lanczos_amd.gmres): A x = b on the real square matrix set.  A basis of its own, max(m, 2) + 1 rows
 // (m: the restart length), beside h->trl, h->z.B and h->ex.B, so eigsh's and eigs' thick-restart basis survives a solve on the same
 // handle; B.w is the work vector of the steps and the residual b - A x of the cycle ends.  x and b: two padded vectors behind vec.
@@ -365,6 +385,7 @@ struct lz_context {
   LsmrState ls;    // the least-squares solver's vectors (lz_lsmr_*): freed by lsmr_free, dropped by lz_gk_set_csr / lz_gk_set_dense
   BicgstabState bc;  // the non-symmetric solver's vectors (lz_bicgstab_*): freed by bicgstab_free, dropped by every matrix setter (z_drop_matrix)
   GmresState gm;     // the restarted solver's basis and vectors (lz_gmres_*): freed by gmres_free, dropped by every matrix setter (z_drop_matrix)
+  CgState cg;        // the conjugate-gradient solver's vectors (lz_cg_*): freed by cg_free, dropped by every matrix setter (z_drop_matrix)
   bool prof_iter = true;  // false while lz_run skips an iteration under profile sampling (tune[7])
   lz_timings acc;
 };
@@ -496,6 +517,9 @@ void bicgstab_free(lz_handle h);
 
 // GMRES (lz_gmres.hip): releases everything h->gm owns (lz_destroy)
 void gmres_free(lz_handle h);
+
+// CG (lz_cg.hip): releases everything h->cg owns (lz_destroy)
+void cg_free(lz_handle h);
 
 // Gram-Schmidt basis layer (lz_orth.hip): what lz_trl_*, lz_gk_* and lz_ztrl_* all do with an OrthBasis, real or planar complex, and
 // its OrthWork.  Row counts and indices are in rows of the basis' kind; coefficients of a complex basis are interleaved complex.

@@ -120,6 +120,7 @@ int z_drop_matrix(lz_handle h) {
   h->mr.live = false;  // every matrix setter comes through here: a new matrix drops the MINRES state (lz_minres.hip)
   h->bc.live = false;  // ... and the BiCGSTAB state (lz_bicgstab.hip)
   h->gm.live = false;  // ... and the GMRES state (lz_gmres.hip)
+  h->cg.live = false;  // ... and the CG state (lz_cg.hip)
   LZ_TRY(dev_free(h, z.rowptr));
   LZ_TRY(dev_free(h, z.colidx));
   LZ_TRY(dev_free(h, z.vals));
