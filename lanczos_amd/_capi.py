@@ -1021,7 +1021,8 @@ class Handle:
         rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
         colidx = np.ascontiguousarray(colidx, dtype=np.int32)
         vals = c128(vals)
-        assert len(rowptr) == int(n) + 1 and len(colidx) == len(vals) == int(rowptr[-1])
+        # (SciPy allows ``indices`` / ``data`` longer than ``indptr[-1]``: the entries behind it are not the matrix)
+        assert len(rowptr) == int(n) + 1 and min(len(colidx), len(vals)) >= int(rowptr[-1])
         self.check(self.lib.lz_set_csr_cplx(self._h, int(n), int(rowptr[-1]), i32ptr(rowptr), i32ptr(colidx), dptr(vals)))
         self.rows = int(n)
         self.matrix_uploads += 1

@@ -45,7 +45,10 @@ def abs_matvec(A, x):
     ax = np.abs(np.asarray(x, dtype=np.complex128))
     if sp.issparse(A):
         A = sp.csr_matrix(A)
-        return np.asarray(abs(A) @ ax, dtype=LD), np.diff(A.indptr)
+        # |A| entry by entry as stored.  (SciPy's ``abs(A)`` sums duplicate entries first - IN PLACE, in the arrays that
+        # ``sp.csr_matrix(A)`` shares with the caller's matrix; for a canonical matrix the two are the same numbers.)
+        stored = sp.csr_matrix((np.abs(A.data), A.indices, A.indptr), shape=A.shape)
+        return np.asarray(stored @ ax, dtype=LD), np.diff(A.indptr)
     return np.asarray(np.abs(A) @ ax, dtype=LD), np.full(A.shape[0], A.shape[1])
 
 

@@ -82,7 +82,10 @@ def _spectrum(k, pairs, rng):
 def _reference(A, V, re, im):
     """(residual norms in longdouble, the bound 4 nnz_row eps | |A||x| + |lambda||x| |)"""
     k, rows = len(re), A.shape[0]
-    Al, absA = sp.csr_matrix(A), abs(sp.csr_matrix(A))
+    Al = sp.csr_matrix(A)
+    # |A| entry by entry as stored (SciPy's abs() first sums a matrix's duplicate entries, in place, in arrays that Al and A share;
+    # for a canonical matrix these are the same numbers)
+    absA = sp.csr_matrix((np.abs(Al.data), Al.indices, Al.indptr), shape=Al.shape)
     coo = Al.tocoo()
 
     def mul(x):  # A x in longdouble

@@ -16,6 +16,18 @@ from lanczos_amd import partition, synthetic
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _noncanonical_graph():
+    """a graph Laplacian with real values as a user may hold it: rows unsorted and with unsummed duplicates
+    (tests/noncanonical_reference.py; no explicit zeros at random columns, which would end the structural symmetry that the halo
+    plan demands); a rank's local product adds its stored entries in the stored order, like the global one"""
+    from noncanonical_reference import noncanonical
+
+    G = synthetic.random_graph_laplacian(3000, 9000, seed=5).to_scipy()
+    G.data = G.data + np.random.default_rng(6).uniform(-0.25, 0.25, G.nnz)
+    B = noncanonical(G, seed=7, zeros=False)
+    return synthetic.CSR(B.indptr, B.indices, B.data, B.shape)
+
+
 def test_row_bounds():
     assert partition.row_bounds(10_000_000, 8) == [min(10_000_000, p * 1250016) for p in range(9)]
     assert partition.row_bounds(100, 1) == [0, 100]
@@ -29,6 +41,8 @@ def test_row_bounds():
     (lambda: synthetic.laplacian_3d_7pt(12, 11, 10), "halo"),
     (lambda: synthetic.random_graph_laplacian(3000, 9000, seed=5), "auto"),
     (lambda: synthetic.random_graph_laplacian(3000, 9000, seed=5), "halo"),
+    (_noncanonical_graph, "auto"),
+    (_noncanonical_graph, "halo"),
 ])
 def test_plans_reproduce_the_global_spmv(world, build, mode):
     A = build()
